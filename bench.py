@@ -2,9 +2,12 @@
 """Benchmark of the KARIOS matching hot path on MI355X (BASELINE.json metric).
 
 `python bench.py --gpus N --steps K --warmup W`: the LAST stdout line is ONE small JSON object (< 6 KB, `benchkit/summary.py`) - the
-driver's contract keys, `roofline`, `cpu_baseline`, one-number summaries of the side objects and the in-run gates.  Everything else
-(stage tables, gates, sensitivity workloads, configs 3 / 4 / 5 in full) is `detail`: written to `bench_detail.json` (under
-`gpurun_out/` when that directory exists) and printed on EARLIER stdout lines as `detail <name> <json>`.  With N > 1 and no launcher
+driver's contract keys and one-number summaries.  A plain run (any N) does only what `value` needs: set up, warm up, time EXACTLY K bare
+steps (no HIP events inside them), print the line (`roofline` and `cpu_baseline` null).  `--full` adds everything else the bench
+measures: the roofline and stage tables (HIP events in the timed steps, passes of their own), the CPU baseline and the in-run oracle
+gates, the side legs (configs 3 / 4 / 5, sensitivity workloads, `weak_pairs` at N > 1, ...).  Whatever is measured is `detail`: written
+to the detail file (`--detail-file`) and printed on EARLIER stdout lines as `detail <name> <json>`.  `--dump-outputs DIR` (N = 1, config
+2): the frames the timed steps returned, the last one of each distinct pair they reached, DIR/*.npy.  With N > 1 and no launcher
 environment the process SPAWNS N ranks itself (before anything touches the GPU); under an external launcher
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`) WORLD_SIZE must equal --gpus.
 
@@ -18,7 +21,8 @@ N > 1: `value` = BASELINE config 4 as a FIXED workload - 4 bands x tile_size 549
 round-robin to the ranks, batched per rank, ONE all-gather of the 16 frame blocks per step: STRONG scaling (`benchkit/config4.py`).
 The band-per-rank stream of independent pairs (weak scaling, exchange without the host in the loop) is the side number `weak_pairs`.
 
-Modules: benchkit/{headline,config4,legs,sensitivity,cpu,model,summary,launcher}.py.  `--config 3` prints the config-3 line of its own.
+Modules: benchkit/{headline,config4,legs,sensitivity,cpu,model,summary,launcher}.py.  `--config 3` prints the config-3 line of its own
+(with its roofline and crop gate, `--full` or not).
 """
 from __future__ import annotations
 
@@ -52,6 +56,10 @@ def parse(argv=None):
     for leg in ("in-flight", "cpu-baseline", "end-to-end", "full-scoring", "config3", "config4", "config5", "one-pair", "sensitivity", "auto-ksize", "weak-pairs"):
         ap.add_argument(f"--no-{leg}", action="store_true")
     ap.add_argument("--headline-only", action="store_true", help="profiler runs: only the headline's kernels")
+    ap.add_argument("--full", action="store_true", help="also the roofline, the CPU baseline, the in-run gates and every side leg (a plain run: "
+                    "the headline's timed steps alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the frames of the timed steps (each distinct pair's last) as "
+                    "DIR/<name>.npy (N = 1, config 2)")
     ap.add_argument("--cpu-runs", type=int, default=4, help="timed oracle passes: pass k runs (and gates) distinct pair k %% pairs")
     ap.add_argument("--depth", type=int, default=2, help="submissions still pending when submit() returns (FrameStream depth, <= 2 on one context)")
     ap.add_argument("--pairs-per-submission", type=int, default=4, choices=(1, 2, 4),
@@ -61,9 +69,16 @@ def parse(argv=None):
                     help="library contexts (streams + workspace) the N = 1 headline's submissions go to in turn, each with its own software pipeline "
                          "(the rasters are shared).  Default 1: submitted in turn from ONE thread two contexts measure 0.93 ms per pair against 0.87 "
                          "(three: 0.99); a thread per context (tools/two_contexts_probe.py) gains 4 % over one context (0.785 against 0.822)")
-    ap.add_argument("--timed-stage", default="auto", help="stage bracketed by HIP events inside the timed region (auto: the largest kernel; none)")
+    ap.add_argument("--timed-stage", default="auto", help="--full: stage bracketed by HIP events inside the timed region (auto: the largest "
+                    "kernel; none).  A plain run brackets nothing")
     ap.add_argument("--detail-file", default=None, help="where the full detail goes (default: gpurun_out/bench_detail.json if that directory exists, else ./bench_detail.json)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.timed_stage != "auto" and not a.full:
+        ap.error("--timed-stage needs --full (a plain run times bare steps)")
+    if a.dump_outputs and (a.gpus != 1 or a.config != 2):
+        ap.error("--dump-outputs: the N = 1 headline (config 2) only")
     if a.headline_only:
         for leg in ("in_flight", "cpu_baseline", "end_to_end", "full_scoring", "config3", "config4", "config5", "one_pair", "sensitivity", "auto_ksize", "weak_pairs"):
             setattr(a, "no_" + leg, True)
@@ -184,7 +199,7 @@ def main():
     c4_is_value = world > 1 and not a.no_config4 and S == 10980          # (the same on every rank)
     if c4_is_value:
         # ---------------------------------------------------------------- N > 1: value = config 4, strong scaling
-        c4 = config4(dev, rank, world, env.coll_dev, a.steps, batched=True, warmup=a.warmup, timed_stage="min_eigen")
+        c4 = config4(dev, rank, world, env.coll_dev, a.steps, batched=True, warmup=a.warmup, timed_stage="min_eigen" if a.full else None)
         if rank == 0:
             from benchkit.model import roofline_units
             detail = dict(common, value=c4["value"], ms_per_step=c4["ms_per_step"], scaling="strong",
@@ -192,10 +207,11 @@ def main():
                                   "units": 16, "units_per_rank": c4["units_per_rank"], "pairs_per_step": 4,
                                   "parallelism": f"16 independent units round-robin over {world} ranks, batched per rank, flat all-gather of the frame blocks"},
                           units_per_rank=c4["units_per_rank"], matched_keypoints_per_sec=c4["matched_keypoints_per_sec"],
-                          matched_keypoints_per_pair=c4["matched_keypoints_per_step"] // 4, roofline=roofline_units(c4), cpu_baseline=None, config4=c4)
+                          matched_keypoints_per_pair=c4["matched_keypoints_per_step"] // 4, roofline=roofline_units(c4) if a.full else None,
+                          cpu_baseline=None, config4=c4)
         torch.cuda.empty_cache()
 
-    if not (c4_is_value and a.no_weak_pairs):
+    if not (c4_is_value and (a.no_weak_pairs or not a.full)):
         # ---------------------------------------------------------------- the stream of independent band pairs (value at N = 1)
         import copy
         data, pairs, t_gen = headline.make_pairs(env, S, G)
@@ -207,7 +223,9 @@ def main():
         head = headline.run(aa, env, conf, pairs, S, more_pairs=[headline.pairs_on(c, data, S) for c in extra_ctxs])
         for c in extra_ctxs:
             c.close()
-        last_frames = head.pop("last_frames")
+        last_frames, timed_frames = head.pop("last_frames"), head.pop("timed_frames")
+        if a.dump_outputs and solo:
+            dump_outputs(a.dump_outputs, timed_frames)
         if rank == 0:
             head_cfg = {"workload": f"BASELINE config 2: {G} distinct S2-sized pairs {S}x{S} u16 resident in HBM, one per step, {G} per batched submission, KLT + ZNCC",
                         "pairs_per_step": world, "pairs_per_submission": head["pairs_per_submission"], "distinct_pairs_resident": head["distinct_pairs_resident"],
@@ -219,12 +237,12 @@ def main():
                 detail["synth_seconds"] = round(t_gen, 2)
             else:
                 detail["weak_pairs"] = dict(head, steps=aa.steps, config=head_cfg, scaling="weak")
-        if solo:
+        if solo and a.full:
             run_solo_legs(a, env, conf, detail, data, pairs, last_frames, S, G)
         del pairs, data
         torch.cuda.empty_cache()
 
-    if world == 1 and not a.no_config4 and S == 10980:
+    if world == 1 and a.full and not a.no_config4 and S == 10980:
         k4 = max(3, min(8, a.steps // 3))
         c4 = config4(dev, rank, world, env.coll_dev, k4, batched=True)
         # A/B: the rank's units through ONE batched submission against unit by unit on one / three library contexts
@@ -233,7 +251,7 @@ def main():
         c4["contexts_in_flight_ab"] = {"batched": {"ms_per_step": c4["ms_per_step"]}, "1": {"ms_per_step": c4_one["ms_per_step"]},
                                        "3": {"ms_per_step": c4_three["ms_per_step"]}, "note": "same 16 units, same box, back to back"}
         detail["config4"] = c4
-    if solo and not a.no_cpu_baseline:
+    if solo and a.full and not a.no_cpu_baseline:
         from benchkit.cpu import cpu_baseline
         cb = cpu_baseline(env.host_pair, env.n_host_pairs, dict(maxCorners=conf.maxCorners), a.cpu_runs, gpu_frames=env.last_frames,
                           scored_frame=env.scored_frame)
@@ -246,12 +264,34 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         sens = os.path.join(ROOT, SENS_FILE)
-        if os.path.exists(sens):
+        if a.full and os.path.exists(sens):
             try:
                 detail["oracle_sensitivity"] = dict(json.load(open(sens)), source=f"precomputed: {SENS_FILE} (tools/investigations/oracle_sensitivity.py, round 2)")
             except Exception:
                 pass
         emit(detail, a)
+
+
+def dump_outputs(out_dir, timed_frames):
+    """--dump-outputs: what a caller of the timed path received - the DataFrame of the last timed step of every distinct pair the timed
+    steps reached (every distinct pair once K >= the pairs per submission) - one array per column as DIR/pair<b>_<column>.npy,
+    float32 / float64 as computed (the row labels as float64, exact).
+    Every array is finite: a column with NaN entries (`zncc_score` of the rows below the confidence threshold or without variance)
+    is written with 0 there, beside DIR/pair<b>_<column>_finite.npy (1 where the value is finite, else 0)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for b, f in sorted(timed_frames.items()):
+        if f is None:
+            continue
+        cols = {"index": f.index.to_numpy()}
+        cols.update({c: f[c].to_numpy() for c in f.columns})
+        for name, v in cols.items():
+            v = np.array(v, dtype=v.dtype if v.dtype in (np.float32, np.float64) else np.float64)
+            stem = os.path.join(out_dir, f"pair{b}_{name.replace(' ', '_')}")
+            finite = np.isfinite(v)
+            if not finite.all():
+                np.save(stem + "_finite.npy", finite.astype(np.float32))
+                v[~finite] = 0
+            np.save(stem + ".npy", v)
 
 
 def run_solo_legs(a, env, conf, detail, data, pairs, last_frames, S, G):

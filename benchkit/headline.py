@@ -50,7 +50,9 @@ def run(a, env, conf, pairs, S: int, more_pairs=()):
     """W warm-up steps, settle, EXACTLY K timed steps between fences (barrier + synchronize), max over ranks.
     `more_pairs`: the same pairs on further library contexts (`pairs_on`) - consecutive submissions then go to the contexts in turn:
     each context runs its own software pipeline (csrc/api_units.hip) and the GPU interleaves them (N = 1 without the exchange only).
-    -> dict of everything measured (rank 0 fills the roofline), including `last_frames` (pair index -> DataFrame of its last step)."""
+    `a.full`: also the roofline's stage events inside the timed region and the untimed stage passes after it (a plain run times bare steps).
+    -> dict of everything measured (rank 0 fills the roofline with `a.full`), including `last_frames` (pair index -> DataFrame of its
+    last step) and `timed_frames` (the same for the pairs the timed steps reached, from their last timed step)."""
     import torch
     import torch.distributed as dist
     from karios_amd.parallel import RankBlockExchange
@@ -188,20 +190,23 @@ def run(a, env, conf, pairs, S: int, more_pairs=()):
     # run HERE, in front of the probe steps and a second settle, which bring clocks and caches back under load
     gc.collect()
     gc.disable()
-    every.set_option("profile_stage", -1)
-    every.set_profiling(True)
-    stage_sum.clear()
-    run_steps(2 * G)
-    take(stream.drain())
-    fence()
-    probe = {k: v for k, v in stage_sum.items() if k in ("stretch_laplacian_mask", "min_eigen", "lk_fwd_bwd") and v > 0}
-    timed_stage = max(probe, key=probe.get) if probe else "min_eigen"
-    if a.timed_stage not in ("auto", "none"):
-        timed_stage = a.timed_stage
-    every.set_option("profile_stage", stage_names.index(timed_stage))
-    every.set_option("profile_every", 2)            # the timed steps are SAMPLED: every second submission records the stage's two events
-    if a.timed_stage == "none":
-        every.set_profiling(False)
+    # --full only: the roofline's stage (probe steps, HIP events sampled inside the timed region); a plain run times the steps bare
+    timed_stage = None
+    if a.full:
+        every.set_option("profile_stage", -1)
+        every.set_profiling(True)
+        stage_sum.clear()
+        run_steps(2 * G)
+        take(stream.drain())
+        fence()
+        probe = {k: v for k, v in stage_sum.items() if k in ("stretch_laplacian_mask", "min_eigen", "lk_fwd_bwd") and v > 0}
+        timed_stage = max(probe, key=probe.get) if probe else "min_eigen"
+        if a.timed_stage not in ("auto", "none"):
+            timed_stage = a.timed_stage
+        every.set_option("profile_stage", stage_names.index(timed_stage))
+        every.set_option("profile_every", 2)            # the timed steps are SAMPLED: every second submission records the stage's two events
+        if a.timed_stage == "none":
+            every.set_profiling(False)
     t_s2, prev2, settle["post_gc_windows"] = time.perf_counter(), None, 0
     while True:
         fence()
@@ -223,6 +228,7 @@ def run(a, env, conf, pairs, S: int, more_pairs=()):
         ex.finish()
         ex.reset_counts()
     fence()
+    first_timed = step_no[0]
     cpu0 = (time.thread_time(), stream.worker_cpu_s, time.process_time())
     t0 = time.perf_counter()
     marks = [(t0, 0)]
@@ -259,26 +265,28 @@ def run(a, env, conf, pairs, S: int, more_pairs=()):
     timed_launch_ms = stage_sum.get(timed_stage, 0.0) / max(1, timed_samples)
     redone_timed = totals["redone"]
     last_frames = dict(totals["last"])
-    # untimed pass: every stage bracketed
-    every.set_profiling(True)
-    every.set_option("profile_stage", -1)
-    every.set_option("profile_every", 1)
-    stage_steps = max(G, min(a.steps, 12) // G * G)
-    stage_sum.clear()
-    run_steps(stage_steps)
-    take(stream.drain())
-    fence()
-    stage_piped = {k: v / stage_steps for k, v in stage_sum.items()}
-    # ... and the same pass with the software pipeline OFF: every kernel with the GPU to itself (plus the second stream's pyramids /
-    # min-max, as in rounds 1 - 5) - what a kernel costs, against what it takes while it shares the GPU with the other lane's chains
-    piped_before = ctx.get_option("units_pipeline", 0)
-    every.set_option("units_pipeline", 0)
-    stage_sum.clear()
-    run_steps(stage_steps)
-    take(stream.drain())
-    fence()
-    every.set_option("units_pipeline", piped_before)
-    every.set_profiling(False)
+    timed_frames = {b: last_frames[b] for b in sorted({k % P for k in range(first_timed, step_no[0])})}     # (K < P: the pairs the timed steps reached)
+    if a.full:
+        # untimed pass: every stage bracketed
+        every.set_profiling(True)
+        every.set_option("profile_stage", -1)
+        every.set_option("profile_every", 1)
+        stage_steps = max(G, min(a.steps, 12) // G * G)
+        stage_sum.clear()
+        run_steps(stage_steps)
+        take(stream.drain())
+        fence()
+        stage_piped = {k: v / stage_steps for k, v in stage_sum.items()}
+        # ... and the same pass with the software pipeline OFF: every kernel with the GPU to itself (plus the second stream's pyramids /
+        # min-max, as in rounds 1 - 5) - what a kernel costs, against what it takes while it shares the GPU with the other lane's chains
+        piped_before = ctx.get_option("units_pipeline", 0)
+        every.set_option("units_pipeline", 0)
+        stage_sum.clear()
+        run_steps(stage_steps)
+        take(stream.drain())
+        fence()
+        every.set_option("units_pipeline", piped_before)
+        every.set_profiling(False)
     stream.close()
     if ex is not None:
         ex.finish()                    # (the untimed pass armed the frame sink again: gathered, sink off)
@@ -303,11 +311,18 @@ def run(a, env, conf, pairs, S: int, more_pairs=()):
     out = {"value": mpx_per_s, "ms_per_step": ms_per_step, "seconds": dt, "pairs_per_submission": G, "distinct_pairs_resident": P, "depth": depth,
            "matched_keypoints_per_sec": n_kp_total / dt, "exchange": exchange, "host_cpu_ms_per_step": host_cpu,
            "speculative_tiles_redone": int(redone_timed), "settle": settle, "step_spread": step_spread, "last_frames": last_frames,
+           "timed_frames": timed_frames,
            "python_gc": "disabled during the timed steps"}
     if env.rank == 0:
         frames = [f for f in last_frames.values() if f is not None]
         n_init = int(round(np.mean(list(totals["n_init"].values())))) if totals["n_init"] else int(stats.n_init)
         n_cand = int(round(np.mean(list(totals["n_cand"].values())))) if totals["n_cand"] else int(stats.n_candidates)
+        out.update({
+            "matched_keypoints_per_pair": int(round(np.mean([len(f) for f in frames]))) if frames else 0,
+            "matched_keypoints_by_pair": {str(b): (0 if f is None else len(f)) for b, f in sorted(last_frames.items())},
+            "n_init": n_init, "n_candidates": n_cand,
+            "median_dx_dy": (None if not frames else [float(np.median(frames[0]["dx"])), float(np.median(frames[0]["dy"]))])})
+    if env.rank == 0 and a.full:
         n_zncc = int(round(np.mean([(f["score"].to_numpy() >= 0.4).sum() for f in frames]))) if frames else 0
         stage_alone = {k: v / stage_steps for k, v in stage_sum.items()}
         stage_ms = dict(stage_piped)
@@ -340,10 +355,6 @@ def run(a, env, conf, pairs, S: int, more_pairs=()):
             if roof.get("traffic"):
                 roof["traffic"] = roof["traffic"] * G
         out.update({
-            "matched_keypoints_per_pair": int(round(np.mean([len(f) for f in frames]))) if frames else 0,
-            "matched_keypoints_by_pair": {str(b): (0 if f is None else len(f)) for b, f in sorted(last_frames.items())},
-            "n_init": n_init, "n_candidates": n_cand,
-            "median_dx_dy": (None if not frames else [float(np.median(frames[0]["dx"])), float(np.median(frames[0]["dy"]))]),
             "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
             "stage_ms_alone": {k: round(v, 4) for k, v in stage_alone.items()},
             "stage_ms_note": f"per PAIR.  stage_ms: the pipelined loop ({timed_stage}: HIP events on {timed_samples} submissions of the timed region, every "

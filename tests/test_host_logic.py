@@ -373,6 +373,38 @@ def test_bench_refuses_a_world_size_that_differs_from_gpus():
     assert r.returncode == 2 and "WORLD_SIZE=4" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_refuses_what_a_run_cannot_time_or_dump(tmp_path):
+    """`--steps` is the number of timed steps (at least one); `--dump-outputs` writes the N = 1 headline's frames (config 2) only; a
+    plain run brackets no stage, so `--timed-stage` needs `--full` - each refused before any rank starts or anything touches the GPU."""
+    for args, why in ((["--steps", "0"], "--steps"), (["--gpus", "2", "--dump-outputs", str(tmp_path)], "--dump-outputs"),
+                      (["--timed-stage", "min_eigen"], "--timed-stage"), (["--gpus", "2", "--timed-stage", "none"], "--timed-stage"),
+                      (["--config", "3", "--dump-outputs", str(tmp_path)], "--dump-outputs")):
+        r = _run_bench(args)
+        assert r.returncode == 2 and why in r.stderr and r.stdout.strip() == "", (args, r.stderr)
+    assert os.listdir(tmp_path) == []
+
+
+def test_bench_dump_outputs_writes_every_column_of_the_last_frames_as_float(tmp_path):
+    """`bench.dump_outputs`: one .npy per pair and column (the row labels included), float32 / float64 as computed, integers widened
+    to float64 exactly; every array finite - a column with NaN (`zncc_score` below the threshold) holds 0 there and gets a `_finite`
+    mask beside it, so nothing is lost; a pair without a frame writes nothing."""
+    sys.path.insert(0, ROOT)
+    import bench
+    f = pd.DataFrame({"x0": np.array([3, 17], np.float32), "dx": np.array([0.5, -0.25], np.float32), "zncc_score": np.array([0.9, np.nan]),
+                      "radial error": np.array([0.5, 0.25], np.float32), "n": np.array([1, 2], np.int32)}, index=np.array([7, 2 ** 40], np.int64))
+    bench.dump_outputs(str(tmp_path / "out"), {2: f, 0: None})
+    got = {n: np.load(tmp_path / "out" / n) for n in sorted(os.listdir(tmp_path / "out"))}
+    assert sorted(got) == ["pair2_dx.npy", "pair2_index.npy", "pair2_n.npy", "pair2_radial_error.npy", "pair2_x0.npy", "pair2_zncc_score.npy",
+                           "pair2_zncc_score_finite.npy"]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert got["pair2_x0.npy"].dtype == np.float32 and got["pair2_zncc_score.npy"].dtype == np.float64
+    np.testing.assert_array_equal(got["pair2_index.npy"], [7.0, 2.0 ** 40])
+    np.testing.assert_array_equal(got["pair2_n.npy"], [1.0, 2.0])
+    np.testing.assert_array_equal(got["pair2_zncc_score.npy"], [0.9, 0.0])
+    np.testing.assert_array_equal(got["pair2_zncc_score_finite.npy"], [1.0, 0.0])
+    assert np.isnan(f["zncc_score"].to_numpy()[1])                       # (the frame itself is left as computed)
+
+
 # ---------------------------------------------------------------------------- FrameStream (host logic with a stand-in pair)
 class _FakePair:
     """Duck type of ResidentPair for the stream's host logic: `match_tile_raw` hands back a finished block at once."""

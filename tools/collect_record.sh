@@ -1,9 +1,9 @@
 #!/bin/bash
-# Copy what tools/round_end.sh left under gpurun_out/ into profiles/ (run HERE, after the gpurun call) and fold the PMC passes.
+# Copy what tools/round_end.sh left into profiles/ (run HERE, once its results are back) and fold the PMC passes.
 #   bash tools/collect_record.sh <tag>
-TAG=${1:-r06}
-for n in bench_$TAG.json bench_${TAG}_detail.json bench_${TAG}_default.json bench_${TAG}_default_detail.json bench_${TAG}_config3.json bench_${TAG}_config3_detail.json; do cp gpurun_out/$n profiles/$n; done
-cp gpurun_out/bench_$TAG.out profiles/bench_${TAG}_stdout.txt
+TAG=${1:-r06}; D=${RECORD_DIR:-bench_records}     # (the bench records of tools/final_measure.sh)
+for n in bench_$TAG.json bench_${TAG}_detail.json bench_${TAG}_default.json bench_${TAG}_default_detail.json bench_${TAG}_config3.json bench_${TAG}_config3_detail.json; do cp $D/$n profiles/$n; done
+cp $D/bench_$TAG.out profiles/bench_${TAG}_stdout.txt
 for f in config2 config2_driver_flags config2_one_pair_per_submission config3 config4_batched config4_pipelined_loop e2e_shape_batched entry_points kernels_alone phase_fp64; do
   cp gpurun_out/${TAG}_kernel_stats_$f.md profiles/
 done

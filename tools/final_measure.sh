@@ -4,18 +4,25 @@
 # config 3 and of the entry points the loop does not reach, and the PMC passes (separate --pmc runs, kernel trace only).  Results
 # under gpurun_out/ (the summaries are copied to profiles/ by hand).  Every profiler run sits under `timeout`.
 R=$PWD; TAG=${1:-r06}; COMMIT=${2:-unknown}
-# (the LAST stdout line is the driver's record; the `detail <name> {...}` lines above it and the detail file are kept beside it)
-python bench.py --gpus 1 --steps 20 --warmup 5 --detail-file gpurun_out/bench_${TAG}_detail.json > gpurun_out/bench_${TAG}.out 2> gpurun_out/bench_${TAG}.err; tail -1 gpurun_out/bench_${TAG}.out > gpurun_out/bench_${TAG}.json
-python bench.py --detail-file gpurun_out/bench_${TAG}_default_detail.json > gpurun_out/bench_${TAG}_default.out 2> gpurun_out/bench_${TAG}_default.err; tail -1 gpurun_out/bench_${TAG}_default.out > gpurun_out/bench_${TAG}_default.json
-python bench.py --config 3 --steps 10 --warmup 2 --detail-file gpurun_out/bench_${TAG}_config3_detail.json > gpurun_out/bench_${TAG}_config3.out 2> gpurun_out/bench_${TAG}_config3.err; tail -1 gpurun_out/bench_${TAG}_config3.out > gpurun_out/bench_${TAG}_config3.json
+# (the LAST stdout line is the driver's record; the `detail <name> {...}` lines above it and the detail file are kept beside it, in
+# $RECORD_DIR - default bench_records/ - which tools/collect_record.sh reads.  --full: the records carry the roofline, the CPU baseline,
+# the in-run gates and every side leg)
+D=${RECORD_DIR:-bench_records}; mkdir -p $D
+record() {   # record <name> [bench.py args]: one bench run -> $D/<name>.{out,err,json} + $D/<name>_detail.json
+  n=$1; shift
+  python bench.py "$@" --detail-file $D/${n}_detail.json > $D/$n.out 2> $D/$n.err; tail -1 $D/$n.out > $D/$n.json
+}
+record bench_${TAG} --full --gpus 1 --steps 20 --warmup 5
+record bench_${TAG}_default --full
+record bench_${TAG}_config3 --config 3 --steps 10 --warmup 2
 cd /tmp && export TMPDIR=/tmp
 prof() {   # prof <tag> <script> [args]: rocprofv3 kernel statistics (csv) of `python3 <script> args`
   t=$1; shift
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_${TAG}_$t -o $t -- python3 "$@" > $R/gpurun_out/prof_${TAG}_$t.log 2>&1
 }
-prof c2 $R/bench.py --headline-only --steps 60 --warmup 5
-prof c2drv $R/bench.py --gpus 1 --steps 20 --warmup 5 --headline-only      # (the driver's flags, the headline object alone)
-prof c2one $R/bench.py --pairs-per-submission 1 --headline-only --steps 20 --warmup 5
+prof c2 $R/bench.py --full --headline-only --steps 60 --warmup 5
+prof c2drv $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --headline-only      # (the driver's flags, the headline object alone)
+prof c2one $R/bench.py --full --pairs-per-submission 1 --headline-only --steps 20 --warmup 5
 prof c4loop $R/tools/config4_probe.py
 prof alone $R/tools/blocking_workload.py 12
 prof c4 $R/tools/units_probe.py config4 4
@@ -47,7 +54,7 @@ python tools/two_contexts_probe.py 1 2 > gpurun_out/${TAG}_contexts_probe.log 2>
 python tools/config4_probe.py > gpurun_out/${TAG}_config4_probe.log 2>&1
 python tools/auto_ksize_probe.py > gpurun_out/${TAG}_auto_ksize.json 2> /dev/null
 python tools/fuzz_pipeline.py --rounds 100000 --seed 500000 --budget-s 240 > gpurun_out/${TAG}_fuzz_pipeline.log 2>&1
-tail -1 gpurun_out/bench_${TAG}.json | cut -c1-300
+tail -1 $D/bench_${TAG}.json | cut -c1-300
 head -30 gpurun_out/${TAG}_kernel_stats_config2.md
 head -24 gpurun_out/${TAG}_kernel_stats_kernels_alone.md
 head -24 gpurun_out/${TAG}_kernel_stats_config4_batched.md
