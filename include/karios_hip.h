@@ -44,7 +44,8 @@ enum {
     KM_E_NOMEM = -3,
     KM_E_UNSUPPORTED = -4,
     KM_E_NO_DEVICE = -5,
-    KM_E_INTERNAL = -6
+    KM_E_INTERNAL = -6,
+    KM_E_NO_CONVERGENCE = -7   /* km_find_transform_ecc*: NaN correlation or lambda_d <= 0 (cv2.error StsNoConv) */
 };
 
 /* KLTConfiguration fields (core/configuration.py:36-50) + the fixed LK criteria of
@@ -439,6 +440,47 @@ int km_exclusive_scan_u32(km_ctx *ctx, const unsigned *in, unsigned *out, size_t
  * *left_band = 1: a window needed rows outside the band (halo too small for this displacement) */
 int km_band_track_dev(km_ctx *ctx, const uint8_t *d_lap_ref, const uint8_t *d_lap_mon, int H, int W, int oy, int H_image,
                       const km_klt_params *prm, const float *p0, int n, float *p1, float *p0r, int *left_band);
+
+/* ---- Global align step (karios/matcher/global_align.py; api_align.hip, k_align.hip) ---------------------------------------------
+ * The arithmetic is OpenCV 4.8's, restated in tests/align_restatement.py (the definition the kernels are tested against).
+ *
+ * cv2.warpPerspective(src, M, (dW, dH), flags, BORDER_CONSTANT, border_value) of a single-channel KM_U8 / KM_F32 image:
+ * interpolation 0 = INTER_NEAREST, 1 = INTER_LINEAR; inverse != 0: M maps destination -> source (WARP_INVERSE_MAP), else M is
+ * inverted first (3 x 3 closed form in fp64).  Positions are quantised to 1/32 px as OpenCV does.  The host form writes a
+ * contiguous dH x dW destination. */
+int km_warp_perspective(km_ctx *ctx, const void *src, int dtype, int sH, int sW, ptrdiff_t src_stride, void *dst, int dH, int dW,
+                        int interpolation, int inverse, double border_value, const double M[9]);
+int km_warp_perspective_dev(km_ctx *ctx, const void *d_src, int dtype, int sH, int sW, ptrdiff_t src_stride, void *d_dst, int dH,
+                            int dW, ptrdiff_t dst_stride, int interpolation, int inverse, double border_value, const double M[9]);
+/* _sobel_magnitude: 3 x 3 Sobel of a uint8 image (REFLECT_101), magnitude, divided by its maximum (unchanged when that is 0);
+ * out: contiguous H x W float32 */
+int km_sobel_magnitude(km_ctx *ctx, const uint8_t *img, int H, int W, ptrdiff_t stride, float *out);
+int km_sobel_magnitude_dev(km_ctx *ctx, const uint8_t *d_img, int H, int W, ptrdiff_t stride, float *d_out);
+/* cv2.findTransformECC(template, input, map, MOTION_HOMOGRAPHY, (COUNT | EPS, max_iter, eps), mask, gauss_filt_size): template
+ * hs x ws and input hd x wd (KM_U8 or KM_F32, same type), mask: NULL or hd x wd uint8 (> 0 = valid).  map: float32 3 x 3, in and
+ * out (host memory in both forms).  gauss_filt_size 5 only (KM_E_UNSUPPORTED otherwise).  *cc = the last correlation
+ * coefficient, *iterations = iterations run.  KM_E_NO_CONVERGENCE where OpenCV raises StsNoConv. */
+int km_find_transform_ecc(km_ctx *ctx, const void *template_image, const void *input_image, int dtype, int hs, int ws,
+                          ptrdiff_t template_stride, int hd, int wd, ptrdiff_t input_stride, const uint8_t *mask, ptrdiff_t mask_stride,
+                          float map[9], int max_iter, double eps, int gauss_filt_size, double *cc, int *iterations);
+int km_find_transform_ecc_dev(km_ctx *ctx, const void *d_template_image, const void *d_input_image, int dtype, int hs, int ws,
+                              ptrdiff_t template_stride, int hd, int wd, ptrdiff_t input_stride, const uint8_t *d_mask,
+                              ptrdiff_t mask_stride, float map[9], int max_iter, double eps, int gauss_filt_size, double *cc,
+                              int *iterations);
+/* _refine_with_ecc for n initial 3 x 3 fp64 matrices (mon -> ref) on uint8 mon (hm x wm) / ref (hr x wr): mon pre-warped onto ref's
+ * canvas with (float)init, candidates with fewer than 1000 non-zero pixels skipped, ECC on the Sobel magnitudes (the template's
+ * computed once) from the identity with mask = pre-warped mon > 0.  Per candidate (host arrays): final = residual @ init (fp64,
+ * 9 values), the float32 residual (9), cc, iterations, valid pixels and status (KM_ECC_*).  The call itself returns KM_OK when
+ * a candidate only failed to converge. */
+#define KM_ECC_CONVERGED 0
+#define KM_ECC_SKIPPED 1         /* fewer than 1000 valid pixels after the pre-warp: no ECC launch */
+#define KM_ECC_NO_CONVERGENCE 2  /* findTransformECC would raise: the reference returns (None, nan) */
+int km_refine_ecc_candidates(km_ctx *ctx, const uint8_t *mon, int hm, int wm, ptrdiff_t mon_stride, const uint8_t *ref, int hr, int wr,
+                             ptrdiff_t ref_stride, int n, const double *inits, int max_iter, double eps, double *final_out,
+                             float *residual_out, double *cc_out, int *iterations_out, int64_t *valid_out, int *status_out);
+int km_refine_ecc_candidates_dev(km_ctx *ctx, const uint8_t *d_mon, int hm, int wm, ptrdiff_t mon_stride, const uint8_t *d_ref, int hr,
+                                 int wr, ptrdiff_t ref_stride, int n, const double *inits, int max_iter, double eps, double *final_out,
+                                 float *residual_out, double *cc_out, int *iterations_out, int64_t *valid_out, int *status_out);
 
 #ifdef __cplusplus
 }

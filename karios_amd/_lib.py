@@ -21,7 +21,9 @@ _DTYPES = {np.dtype("uint8"): KM_U8, np.dtype("uint16"): KM_U16, np.dtype("int16
 
 
 class KariosHipError(RuntimeError):
-    """A libkarios_hip call returned a negative status (cv2.error equivalent)."""
+    """A libkarios_hip call returned a negative status (cv2.error equivalent); `code` is that status (KM_E_*)."""
+
+    code = None
 
 
 class KltParams(C.Structure):
@@ -53,6 +55,8 @@ class KmUnit(C.Structure):
 
 UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
 E_UNSUPPORTED = -4             # KM_E_UNSUPPORTED
+E_NO_CONVERGENCE = -7          # KM_E_NO_CONVERGENCE
+ECC_CONVERGED, ECC_SKIPPED, ECC_NO_CONVERGENCE = 0, 1, 2   # KM_ECC_*
 
 _vp, _i, _d, _sz, _pd = C.c_void_p, C.c_int, C.c_double, C.c_ssize_t, C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int)
@@ -132,6 +136,14 @@ SIGNATURES = {
     "km_dn_keep_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _vp, _i, _vp, _i, _pd, _pd, _vp]),
     "km_phase_shift_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _pd]),
     "km_shift_image_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _i, _vp]),
+    "km_warp_perspective": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _i, _i, _i, _i, _d, _pd]),
+    "km_warp_perspective_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _i, _i, _sz, _i, _i, _d, _pd]),
+    "km_sobel_magnitude": (_i, [_vp, _vp, _i, _i, _sz, _vp]),
+    "km_sobel_magnitude_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp]),
+    "km_find_transform_ecc": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _sz, _vp, _sz, _vp, _i, _d, _i, _pd, _pi]),
+    "km_find_transform_ecc_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _sz, _vp, _sz, _vp, _i, _d, _i, _pd, _pi]),
+    "km_refine_ecc_candidates": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "km_refine_ecc_candidates_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -313,7 +325,9 @@ class Context:
     def check(self, rc: int, what: str):
         if rc != 0:
             msg = self.lib.km_last_error(self.handle)
-            raise KariosHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err = KariosHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err.code = rc
+            raise err
 
     def close(self):
         if getattr(self, "handle", None):

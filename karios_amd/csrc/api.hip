@@ -106,6 +106,30 @@ extern "C" {
 
 int km_version(void) { return 101; }
 
+// Weak defaults of the global-align entry points.  The library's api_align.hip defines them (its strong definitions replace these
+// at link time); a build of the host half without the align kernels (the sanitizer build of tests/hoststub) answers KM_E_UNSUPPORTED.
+#define KM_ALIGN_ABSENT(name) return km_fail(c, KM_E_UNSUPPORTED, name ": built without api_align.hip")
+__attribute__((weak)) int km_warp_perspective(km_ctx *c, const void *, int, int, int, ptrdiff_t, void *, int, int, int, int, double, const double *)
+{ KM_ALIGN_ABSENT("warp_perspective"); }
+__attribute__((weak)) int km_warp_perspective_dev(km_ctx *c, const void *, int, int, int, ptrdiff_t, void *, int, int, ptrdiff_t, int, int, double,
+                                                  const double *)
+{ KM_ALIGN_ABSENT("warp_perspective"); }
+__attribute__((weak)) int km_sobel_magnitude(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, float *) { KM_ALIGN_ABSENT("sobel_magnitude"); }
+__attribute__((weak)) int km_sobel_magnitude_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, float *) { KM_ALIGN_ABSENT("sobel_magnitude"); }
+__attribute__((weak)) int km_find_transform_ecc(km_ctx *c, const void *, const void *, int, int, int, ptrdiff_t, int, int, ptrdiff_t, const uint8_t *,
+                                                ptrdiff_t, float *, int, double, int, double *, int *)
+{ KM_ALIGN_ABSENT("find_transform_ecc"); }
+__attribute__((weak)) int km_find_transform_ecc_dev(km_ctx *c, const void *, const void *, int, int, int, ptrdiff_t, int, int, ptrdiff_t,
+                                                    const uint8_t *, ptrdiff_t, float *, int, double, int, double *, int *)
+{ KM_ALIGN_ABSENT("find_transform_ecc"); }
+__attribute__((weak)) int km_refine_ecc_candidates(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, const uint8_t *, int, int, ptrdiff_t, int,
+                                                   const double *, int, double, double *, float *, double *, int *, int64_t *, int *)
+{ KM_ALIGN_ABSENT("refine_ecc_candidates"); }
+__attribute__((weak)) int km_refine_ecc_candidates_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, const uint8_t *, int, int, ptrdiff_t, int,
+                                                       const double *, int, double, double *, float *, double *, int *, int64_t *, int *)
+{ KM_ALIGN_ABSENT("refine_ecc_candidates"); }
+#undef KM_ALIGN_ABSENT
+
 const char *km_last_error(km_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 
 int km_ctx_create(int device, km_ctx **out)

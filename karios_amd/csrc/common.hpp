@@ -98,6 +98,17 @@ enum km_slot {
     WS_F64_MASK,    //   ... which columns / column tiles the inverse needs on the Hermitian half plane
     WS_UNITS_LK,    // k_lk.hip: the per-unit argument table of a batched LK launch
     WS_UNITS_MM,    // api_units.hip: early min / max results of a batch ({min_ref, max_ref, min_mon, max_mon} per unit)
+    WS_AL_OUT,      // api_align.hip: destination of the host-API warp / Sobel forms
+    WS_AL_WARP,     //   uint8 pre-warped mon of a refinement candidate
+    WS_AL_TSOB,     //   Sobel magnitude of the template (ref)
+    WS_AL_SOB,      //   Sobel magnitude of the input (pre-warped mon)
+    WS_AL_T,        //   blurred template (float32)
+    WS_AL_I,        //   blurred input (float32)
+    WS_AL_TMP,      //   row pass of the Gaussian
+    WS_AL_PM,       //   blurred pre-mask (float32)
+    WS_AL_PLANE,    //   {image, gx, gy, pre-mask} float4 plane of the input
+    WS_AL_PART,     //   fp64 partials of an ECC iteration + the reduced sums
+    WS_AL_SCAL,     //   maximum of the Sobel magnitude, non-zero count
     WS_COUNT
 };
 

@@ -1,0 +1,152 @@
+"""Global align step -- mirror of `karios.matcher.global_align` (reference global_align.py) on the GPU.
+
+The caller keeps `_preprocess` (percentile stretch + CLAHE), SIFT, BFMatcher and `cv2.findHomography` on cv2; this module takes
+over from the RANSAC matrix on: the ECC refinement of every candidate (`refine_global_alignment`, the candidate loop of
+`detect_global_alignment`) and the renders of `apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).
+Every GPU call goes through `karios_amd.ops`.  The reference's arithmetic is kept as it is, casts included; INTEGRATION.md
+section 6 notes the direction in which it composes the ECC residual.
+"""
+from __future__ import annotations
+
+import logging
+from dataclasses import dataclass, field
+from typing import Optional
+
+import numpy as np
+
+from .. import ops
+
+logger = logging.getLogger(__name__)
+
+ECC_MAX_ITERS = 200
+ECC_EPS = 1e-6
+ECC_MIN_VALID = 1000   # _refine_with_ecc: "need >1000" (it skips below 1000)
+
+
+@dataclass
+class GlobalAlignment:
+    """Outcome of the global alignment: homography mon -> ref (global_align.py:68-85)."""
+
+    matrix: np.ndarray  # 3x3 homography, mon pixel coords -> ref pixel coords
+    n_inliers: int
+    n_matches: int
+    # (name, 3x3 matrix, ECC score) for every refinement candidate that converged, the chosen one included
+    candidates: list = field(default_factory=list)
+
+    @property
+    def score(self) -> float:
+        """RANSAC inlier ratio in [0, 1]."""
+        return self.n_inliers / self.n_matches if self.n_matches else 0.0
+
+
+def _prior_from_georefs(monitored, reference) -> Optional[np.ndarray]:
+    """3x3 homography mon pixel -> ref pixel implied by the two geotransforms (global_align.py:112-140); duck-typed: the images
+    need `projection`, `spatial_ref.IsSame`, `x_res`, `y_res`, `x_min`, `y_max`.  None without a usable prior."""
+    if not monitored.projection or not reference.projection:
+        return None
+    try:
+        if not monitored.spatial_ref.IsSame(reference.spatial_ref):
+            return None
+    except Exception:
+        return None
+    sx = monitored.x_res / reference.x_res
+    sy = monitored.y_res / reference.y_res
+    tx = (monitored.x_min - reference.x_min) / reference.x_res
+    ty = (monitored.y_max - reference.y_max) / reference.y_res
+    return np.array([[sx, 0.0, tx], [0.0, sy, ty], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+
+def _decompose(matrix: np.ndarray) -> str:
+    """Compact diagnostic string of a 3x3 homography (global_align.py:273-292)."""
+    sx = float(np.hypot(matrix[0, 0], matrix[0, 1]))
+    sy = float(np.hypot(matrix[1, 0], matrix[1, 1]))
+    rot = float(np.degrees(np.arctan2(matrix[1, 0], matrix[0, 0])))
+    persp = float(np.hypot(matrix[2, 0], matrix[2, 1]))
+    return (
+        f"rot={rot:+.3f}°  sx={sx:.4f} sy={sy:.4f}  "
+        f"tx={float(matrix[0,2]):+.2f} ty={float(matrix[1,2]):+.2f}  "
+        f"persp={persp:.6f}"
+    )
+
+
+def _sobel_magnitude(img: np.ndarray) -> np.ndarray:
+    """Sobel gradient magnitude normalised to [0, 1], float32 (global_align.py:295-306)."""
+    return ops.sobel_magnitude(img)
+
+
+def _refine_candidates(mon_u8, ref_u8, inits):
+    """_refine_with_ecc for several starting matrices in one call (the template's Sobel magnitude is computed once)
+    -> [(matrix or None, cc or nan)]."""
+    out = []
+    for init, (_final, cc, _it, valid, status, residual) in zip(
+            inits, ops.refine_ecc_candidates(mon_u8, ref_u8, [np.asarray(m) for m in inits], ECC_MAX_ITERS, ECC_EPS)):
+        if status == ops._lib.ECC_SKIPPED:
+            logger.warning("ECC skipped: pre-warped mon has only %d valid pixels (need >1000)", valid)
+            out.append((None, float("nan")))
+        elif status != ops._lib.ECC_CONVERGED:
+            logger.warning("findTransformECC raised: the algorithm stopped before its convergence")
+            out.append((None, float("nan")))
+        else:
+            # the reference's composition, kept as it is
+            out.append((residual.astype(np.float64) @ np.asarray(init).astype(np.float64), float(cc)))
+    return out
+
+
+def _refine_with_ecc(mon_u8: np.ndarray, ref_u8: np.ndarray, init: np.ndarray):
+    """Refine the mon -> ref homography with ECC on Sobel magnitudes (global_align.py:309-359)
+    -> (refined 3x3, ecc score), or (None, nan) on failure."""
+    return _refine_candidates(mon_u8, ref_u8, [init])[0]
+
+
+def refine_global_alignment(mon_u8, ref_u8, ransac_matrix, n_inliers, n_matches, prior=None) -> GlobalAlignment:
+    """The candidate loop of detect_global_alignment after RANSAC (global_align.py:233-270): ECC from the RANSAC matrix and
+    from the geotransform prior, the highest score wins (strict >), the RANSAC matrix stays when none converges."""
+    candidates = [("RANSAC", ransac_matrix)]
+    if prior is not None:
+        candidates.append(("prior", prior))
+    converged = []
+    best_matrix, best_ecc, best_source = None, -np.inf, ""
+    results = _refine_candidates(mon_u8, ref_u8, [m for _, m in candidates])
+    for (name, _init), (refined, ecc_score) in zip(candidates, results):
+        if refined is None:
+            logger.warning("ECC from %s: failed", name)
+            continue
+        logger.info("ECC from %s: %s  ECC=%.4f", name, _decompose(refined), ecc_score)
+        converged.append((name, refined, ecc_score))
+        if ecc_score > best_ecc:
+            best_ecc, best_matrix, best_source = ecc_score, refined, name
+    matrix = ransac_matrix
+    if best_matrix is not None:
+        logger.info("Selected alignment: ECC-refined from %s (ECC=%.4f)", best_source, best_ecc)
+        matrix = best_matrix
+    else:
+        logger.warning("All ECC refinements failed; keeping RANSAC estimate")
+    return GlobalAlignment(matrix=matrix, n_inliers=n_inliers, n_matches=n_matches, candidates=converged)
+
+
+def _array(img):
+    return img.array if hasattr(img, "array") else np.asarray(img)
+
+
+def render_global_alignment(monitored, reference, mask, alignment: GlobalAlignment):
+    """The numeric part of apply_global_alignment (global_align.py:415-506), without the GeoTIFF writes
+    -> (aligned mon, aligned mask or None, {candidate name: aligned mon of that candidate}).
+    monitored / reference / mask: arrays or images with `.array` (and `.no_data_value` for monitored)."""
+    mon_arr = _array(monitored)
+    rh, rw = _array(reference).shape
+    warp_m = alignment.matrix
+    nodata = getattr(monitored, "no_data_value", None)
+    border_mon = float(nodata) if nodata is not None else 0.0
+    mon_f32 = mon_arr.astype(np.float32)
+    aligned_mon = ops.warp_perspective(mon_f32, warp_m, (rw, rh), flags=ops.INTER_LINEAR,
+                                       border_value=border_mon).astype(mon_arr.dtype)
+    alternatives = {}
+    for cand_name, cand_matrix, _cand_ecc in alignment.candidates:
+        if cand_matrix is alignment.matrix or np.allclose(cand_matrix, alignment.matrix):
+            continue
+        alternatives[cand_name] = ops.warp_perspective(mon_f32, cand_matrix.astype(np.float32), (rw, rh), flags=ops.INTER_LINEAR,
+                                                       border_value=border_mon).astype(mon_arr.dtype)
+    aligned_mask = None
+    if mask is not None:
+        aligned_mask = ops.warp_perspective(_array(mask).astype(np.uint8), warp_m, (rw, rh), flags=ops.INTER_NEAREST, border_value=0)
+    return aligned_mon, aligned_mask, alternatives
