@@ -50,7 +50,10 @@ __device__ __forceinline__ int e2_scan(int v)
     v += e2_dpp<0x143, 0xc>(v);                                       // row_bcast:31 -> rows 2,3
     return v;
 }
-// correctly rounded float32 square root for x == 0 or x >= 2^-96 (see sqrt_rn_normal in k_dense.hip)
+// Correctly rounded float32 square root for x == 0 or x >= 2^-96 (the structure-tensor discriminant is 0 or >= 1e-18):
+// the hardware estimate (<= 1 ulp) corrected with two fused residuals - the sequence the compiler emits for sqrtf under
+// -fhip-fp32-correctly-rounded-divide-sqrt, without its rescaling of tiny arguments and its inf/zero special case
+// (for x == 0 the estimate is 0, both residual tests fail on NaN / 0 and 0 is returned).
 __device__ __forceinline__ float e2_sqrt(float x)
 {
     const float r = __builtin_amdgcn_sqrtf(x);

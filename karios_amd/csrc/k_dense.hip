@@ -1,25 +1,19 @@
 // Dense per-pixel kernels of the KARIOS matching path (gfx950):
 //   K1  NaN-aware min/max reduction            (reference klt.py:46)
 //   K2  uint8 stretch -> Laplacian -> auto mask (klt.py:42-49, 268-273, 433-434)
-//   K3  Sobel -> structure tensor -> box sum -> min eigenvalue (+ masked max)
+//   K3  Sobel -> structure tensor -> box sum -> min eigenvalue (+ masked max): the LDS-tiled general form
 //   K4  threshold + 3x3 local maxima + mask -> candidate keys
 //   K6  pyrDown 5x5
 //   K11 integer image shift                     (core/image.py:70-101)
-// All are HBM-bound stencils / reductions: LDS tiles with halo, integer-exact
-// arithmetic, no MFMA.
+// All are HBM-bound stencils / reductions, integer-exact arithmetic, no MFMA.  The marching K2 kernel and the K6 kernel - like the fused
+// K3+K4 (k_eig3.hip) and the integer ZNCC / MI kernels (k_zncc.hip, k_mi.hip) - are written for a batch of units (km_units,
+// api_units.hip); a single tile or pair runs as a batch of one unit.  K1 keeps a single-tile kernel of its own: the batched one carries
+// the `deep` path of background launches (58 instead of 20 VGPRs at 16 bits) and measured 85 instead of 75 us on a blocking 10980^2 tile.
 #include "common.hpp"
 
-// occupancy targets of the marching kernels (waves per SIMD; 0 = leave it to the register allocator)
-#ifndef KM_EIGM_WAVES
-#define KM_EIGM_WAVES 0
-#endif
+// occupancy target of the marching Laplacian kernel (waves per SIMD; 0 = leave it to the register allocator)
 #ifndef KM_LAPM_WAVES
 #define KM_LAPM_WAVES 0
-#endif
-#if KM_EIGM_WAVES
-#define KM_EIGM_OCC __attribute__((amdgpu_waves_per_eu(KM_EIGM_WAVES, KM_EIGM_WAVES)))
-#else
-#define KM_EIGM_OCC
 #endif
 #if KM_LAPM_WAVES
 #define KM_LAPM_OCC __attribute__((amdgpu_waves_per_eu(KM_LAPM_WAVES, KM_LAPM_WAVES)))
@@ -871,22 +865,17 @@ __device__ __forceinline__ unsigned opaque_lane_offset(unsigned x)
 }
 
 #define LAPM_VALID_OF(R) ((R) == 5 ? 240 : 248)      // output columns of a strip: 64 lanes x 4 columns less the halo lanes (two either side for radius 5)
-#ifndef LAPM_SPLIT
-#define LAPM_SPLIT 0   // 1: one image per wavefront (88 VGPRs, 5 waves/SIMD) - measured SLOWER (0.30 vs 0.264 ms: loop, address and mask work duplicated); 0: both images in one wave
-#endif
 #ifndef LAPM_PF
 #define LAPM_PF 3      // source rows in flight per wave
 #endif
 
-// SPLIT: the two images of a work item go to two different wavefronts (wave parity) - half the register ring per wave
-// (76 instead of 123 VGPRs: 6 instead of 4 waves per SIMD); the image-0 wave also loads image 1's raw row for the mask.
-template <int R, typename T, bool MASK, bool SPLIT>
+template <int R, typename T, bool MASK>
 __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const T *__restrict__ img1, int H, int W,
                                                ptrdiff_t stride0, ptrdiff_t stride1, const double *__restrict__ mm,
                                                const lap_coef &cf, int invert1, const nodata_t &nd,
                                                uint8_t *__restrict__ out0, uint8_t *__restrict__ out1,
                                                uint8_t *__restrict__ mask_out, unsigned *__restrict__ valid_partial, int nstrips,
-                                               int rows_per_item, int nitems, int wave_lin /* wave-uniform: this wavefront's work item (x 2 with SPLIT) */)
+                                               int rows_per_item, int wave_id /* wave-uniform: this wavefront's work item */)
 {
     typedef short short2v __attribute__((ext_vector_type(2)));
     // R = 5 (kernel 11; sum ks = 1024: a horizontal smoothing sum needs 18 bits, the ring holds 16-bit pairs): the kernels of size 11 are
@@ -899,11 +888,8 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
     constexpr int NR = 2 * RH + 1;
     constexpr int HALO = R == 5 ? 8 : 4, VALID = 256 - 2 * HALO;
     static_assert(VALID == LAPM_VALID_OF(R), "strip geometry");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave_id = SPLIT ? wave_lin >> 1 : wave_lin;           // work item (row arithmetic, loop control and row bases stay scalar)
-    const int img_sel = SPLIT ? __builtin_amdgcn_readfirstlane(wave_lin & 1) : -1;
-    if (wave_id >= nitems) { if (!SPLIT && MASK && lane == 0) valid_partial[wave_id] = 0u; return; }
-    const int rowblock = wave_id / nstrips, strip = wave_id - rowblock * nstrips;
+    const int lane = threadIdx.x & 63;
+    const int rowblock = wave_id / nstrips, strip = wave_id - rowblock * nstrips;   // (row arithmetic, loop control and row bases stay scalar)
     stretcher<T> st[2];
     st[0].init(mm, 0, nullptr); st[1].init(mm, 1, nullptr);
     // A width that is no multiple of 4 would leave the last strip's border lane straddling the right edge (the per-lane general path:
@@ -978,17 +964,13 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
     unsigned cnt = 0;
     uint8_t *outs[2] = {out0, out1};
     // FAST: every lane of the strip is an interior, aligned lane (wave-uniform) -> no per-lane fallbacks in the loop
-    auto march = [&](auto fast_tag, auto img_tag) {
+    auto march = [&](auto fast_tag) {
     constexpr bool FAST = decltype(fast_tag)::value;
-    constexpr int IMG = decltype(img_tag)::value;                   // -1: both images in this wave, 0 / 1: only that one
-    constexpr int I0 = IMG < 0 ? 0 : IMG, I1 = IMG < 0 ? 2 : IMG + 1;
-    constexpr bool LOAD0 = IMG != 1, LOAD1 = IMG != 0 || MASK;      // the mask needs both raw rows (image-0 wave)
     auto load_raw = [&](int m, T (&v)[2][4]) {
         const int r = km_reflect101(m, H);
         const T *r0 = img0 + (size_t)r * stride0, *r1 = img1 + (size_t)r * stride1;
         const unsigned lx = opaque_lane_offset(ugx_load * (unsigned)sizeof(T));   // byte offset of the lane's first column
-        if (!LOAD0) {
-        } else if (FAST) {   // uniform row base + unsigned 32-bit lane offset: no per-lane 64-bit address arithmetic; any row alignment
+        if (FAST) {   // uniform row base + unsigned 32-bit lane offset: no per-lane 64-bit address arithmetic; any row alignment
             __builtin_memcpy(v[0], (const char *)r0 + lx, 4 * sizeof(T));
         } else if (vec0) {
             if constexpr (sizeof(T) == 1) { uint32_t q = *(const uint32_t *)(r0 + gx0); __builtin_memcpy(v[0], &q, 4); }
@@ -998,8 +980,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
 #pragma unroll
             for (int k = 0; k < 4; k++) v[0][k] = r0[rc[k]];
         }
-        if (!LOAD1) {
-        } else if (FAST) {
+        if (FAST) {
             __builtin_memcpy(v[1], (const char *)r1 + lx, 4 * sizeof(T));
         } else if (vec1) {
             if constexpr (sizeof(T) == 1) { uint32_t q = *(const uint32_t *)(r1 + gx0); __builtin_memcpy(v[1], &q, 4); }
@@ -1021,7 +1002,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
     (void)hp;
     int ring[2][NR][4];
 #pragma unroll
-    for (int i = I0; i < I1; i++)
+    for (int i = 0; i < 2; i++)
 #pragma unroll
         for (int k = 0; k < NR; k++)
 #pragma unroll
@@ -1046,7 +1027,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 }
             if (m + LAPM_PF < y1 + R) load_raw(m + LAPM_PF, nxt[LAPM_PF - 1]);
             // ---- auto mask of source row m (it is an output row when y0 <= m < y1)
-            if constexpr (MASK && IMG != 1 && FAST && sizeof(T) == 2) {
+            if constexpr (MASK && FAST && sizeof(T) == 2) {
                 // packed form: a pixel pair is valid iff min(mon, ref, mon ^ nodata_mon, ref ^ nodata_ref) != 0 (unsigned)
                 if (m >= y0 && m < y1 && out_lane) {
                     uint2 qm, qr;
@@ -1062,7 +1043,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                     cnt += (unsigned)__popc(mp & cnt_mask);
                     __builtin_memcpy((mask_out + (size_t)m * W) + opaque_lane_offset(ugx), &mp, 4);
                 }
-            } else if constexpr (MASK && IMG != 1) {
+            } else if constexpr (MASK) {
                 if (m >= y0 && m < y1 && out_lane) {
                     uint32_t mp = 0;
 #pragma unroll
@@ -1080,7 +1061,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 }
             }
 #pragma unroll
-            for (int i = I0; i < I1; i++) {
+            for (int i = 0; i < 2; i++) {
                 // ---- stretch to uint8 (biased by -128 for the signed dot products)
                 uint32_t cw = 0;
 #pragma unroll
@@ -1126,7 +1107,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 const int yy = m - RH, yo = yy - 1;
                 if (yy >= y0 - 1) {
 #pragma unroll
-                    for (int i = I0; i < I1; i++) {
+                    for (int i = 0; i < 2; i++) {
                         int a[4], h[4];
 #pragma unroll
                         for (int o = 0; o < 4; o++) {
@@ -1165,7 +1146,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
             const int y = m - R;
             if (y >= y0 && out_lane) {
 #pragma unroll
-                for (int i = I0; i < I1; i++) {
+                for (int i = 0; i < 2; i++) {
                     uint32_t packed = 0;
 #pragma unroll
                     for (int o = 0; o < 4; o++) {
@@ -1194,39 +1175,17 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
     // of 4 is shifted (above); only a last strip of fewer than 4 columns (its left neighbour's border lane straddles the edge) and images of
     // a single strip still take the general path.
     const bool fast = (W % 4 == 0) || shifted || (strip * VALID - HALO + 4 * 64 <= W);
-    if constexpr (SPLIT) {
-        if (img_sel == 0) { if (fast) march(std::true_type{}, std::integral_constant<int, 0>{}); else march(std::false_type{}, std::integral_constant<int, 0>{}); }
-        else { if (fast) march(std::true_type{}, std::integral_constant<int, 1>{}); else march(std::false_type{}, std::integral_constant<int, 1>{}); }
-    } else {
-        if (fast) march(std::true_type{}, std::integral_constant<int, -1>{});
-        else march(std::false_type{}, std::integral_constant<int, -1>{});
-    }
+    if (fast) march(std::true_type{});
+    else march(std::false_type{});
     if constexpr (MASK) {
-        if (!SPLIT || img_sel == 0) {
-            const unsigned c64 = (unsigned)wave_sum_u64((unsigned long long)cnt);
-            if (lane == 0) valid_partial[wave_id] = c64;
-        }
+        const unsigned c64 = (unsigned)wave_sum_u64((unsigned long long)cnt);
+        if (lane == 0) valid_partial[wave_id] = c64;
     }
 }
 
-// work item = (row block, column strip), strips fastest: the 4 waves of a workgroup take 4 consecutive items
-template <int R, typename T, bool MASK, bool SPLIT>
-__global__ __launch_bounds__(256) KM_LAPM_OCC void lap_march_kernel(const T *__restrict__ img0, const T *__restrict__ img1, int H, int W,
-                                                        ptrdiff_t stride0, ptrdiff_t stride1, const double *__restrict__ mm,
-                                                        lap_coef cf, int invert1, nodata_t nd,
-                                                        uint8_t *__restrict__ out0, uint8_t *__restrict__ out1,
-                                                        uint8_t *__restrict__ mask_out, unsigned *__restrict__ valid_partial, int nstrips,
-                                                        int rows_per_item, int nitems)
-{
-    unsigned tile;
-    if (!km_xcd_tile((unsigned)((SPLIT ? 2 : 1) * nitems + 3) / 4u, tile)) return;
-    const int wave_lin = (int)tile * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // readfirstlane: the compiler must know it is wave-uniform
-    lap_march_item<R, T, MASK, SPLIT>(img0, img1, H, W, stride0, stride1, mm, cf, invert1, nd, out0, out1, mask_out, valid_partial, nstrips, rows_per_item,
-                                      nitems, wave_lin);
-}
-
-// batched units: the units' work items form ONE linear item space (unit u owns [item0[u], item0[u + 1])): a wavefront finds its unit
-// with a scalar scan of <= 16 bounds and then runs exactly the item of the single-unit kernel on that unit's rasters
+// The units' work items form ONE linear item space (unit u owns [item0[u], item0[u + 1])), a unit's items are (row block, column
+// strip), strips fastest: the 4 waves of a workgroup take 4 consecutive items.  A wavefront finds its unit with a scalar scan of <= 16
+// bounds and runs the item on that unit's rasters.  A single pair is a batch of one unit.
 struct lapm_units_args {
     const void *img0[KM_UNITS_MAX], *img1[KM_UNITS_MAX];
     ptrdiff_t s0[KM_UNITS_MAX], s1[KM_UNITS_MAX];
@@ -1247,61 +1206,94 @@ __global__ __launch_bounds__(256) KM_LAPM_OCC void lap_march_units_kernel(lapm_u
     if (wave_lin >= total) return;
     int u = 0;
     while (u + 1 < U.n && wave_lin >= U.item0[u + 1]) u++;
-    lap_march_item<R, T, MASK, false>((const T *)U.img0[u], (const T *)U.img1[u], U.H[u], U.W[u], U.s0[u], U.s1[u], U.mm[u], cf, invert1, nd, U.out0[u], U.out1[u],
-                                      U.mask[u], U.valid[u], U.nstrips[u], U.rows, U.item0[u + 1] - U.item0[u], wave_lin - U.item0[u]);
+    lap_march_item<R, T, MASK>((const T *)U.img0[u], (const T *)U.img1[u], U.H[u], U.W[u], U.s0[u], U.s1[u], U.mm[u], cf, invert1, nd, U.out0[u], U.out1[u],
+                               U.mask[u], U.valid[u], U.nstrips[u], U.rows, wave_lin - U.item0[u]);
 }
 
+template <typename T, bool MASK>
+static const void *lapm_kernel(int R)
+{
+    return R == 1 ? (const void *)lap_march_units_kernel<1, T, MASK> : R == 2 ? (const void *)lap_march_units_kernel<2, T, MASK>
+         : R == 3 ? (const void *)lap_march_units_kernel<3, T, MASK> : R == 4 ? (const void *)lap_march_units_kernel<4, T, MASK>
+         : (const void *)lap_march_units_kernel<5, T, MASK>;
+}
+
+// Rows per item and the units' item ranges: the value in [32, 160] that minimises whole rounds of resident waves x the work of one
+// item over ALL units' strips (km_pick_rows); the resident waves are 4 SIMDs per CU x the waves per SIMD the register budget of the
+// instantiation `fn` allows
+static void lapm_items(km_ctx *c, int R, const void *fn, lapm_units_args &A)
+{
+    int wg_per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_per_cu, fn, 256, 0) != hipSuccess || wg_per_cu < 1) wg_per_cu = 4;
+    const long slots = (long)c->n_cu * 4 * wg_per_cu;
+    int rows = 32;
+    {
+        double best = 1e300;
+        for (int r = 32; r <= 160; r++) {
+            long items = 0;
+            for (int u = 0; u < A.n; u++) items += (long)A.nstrips[u] * ((A.H[u] + r - 1) / r);
+            const long rounds = (items + slots - 1) / slots;
+            const double last = (double)(items - (rounds - 1) * slots) / (double)slots;
+            const double cost = ((double)(rounds - 1) + 0.5 + 0.5 * last) * (double)(r + 2 * R);
+            if (cost < best) { best = cost; rows = r; }
+        }
+    }
+    if (const char *e = km_dev_env("KARIOS_HIP_LAP_ROWS")) { const int v = atoi(e); if (v >= 8 && v <= 4096) rows = v; }   // tuning override
+    A.rows = rows;
+    A.item0[0] = 0;
+    for (int u = 0; u < A.n; u++) A.item0[u + 1] = A.item0[u] + A.nstrips[u] * ((A.H[u] + rows - 1) / rows);
+}
+
+template <typename T, bool MASK>
+static int lapm_launch(km_ctx *c, int R, const lapm_units_args &A, const lap_coef &cf, int invert1, const nodata_t &nd)
+{
+    const dim3 grid(km_xcd_grid((unsigned)(A.item0[A.n] + 3) / 4u));
+    switch (R) {
+    case 1: lap_march_units_kernel<1, T, MASK><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
+    case 2: lap_march_units_kernel<2, T, MASK><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
+    case 3: lap_march_units_kernel<3, T, MASK><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
+    case 4: lap_march_units_kernel<4, T, MASK><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
+    case 5: lap_march_units_kernel<5, T, MASK><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
+    default: return km_fail(c, KM_E_INTERNAL, "lap_march radius %d", R);
+    }
+    KM_LAUNCH_CHECK(c);
+    return KM_OK;
+}
+
+// one pair (kd_stretch_laplacian_pair): a batch of one unit
 template <typename T, bool MASK>
 static int launch_lap_march(km_ctx *c, int R, const T *a, const T *b, int H, int W, ptrdiff_t sa, ptrdiff_t sb, const double *mm,
                             const lap_coef &cf, int invert1, const nodata_t &nd, uint8_t *oa, uint8_t *ob,
                             uint8_t *mask, unsigned long long *valid_out)
 {
-    const int nstrips = (W + LAPM_VALID_OF(R) - 1) / LAPM_VALID_OF(R);
-    // resident waves: 4 SIMDs per CU x the waves per SIMD the register budget of this instantiation allows
-    auto slots_of = [&](const void *fn) -> long {
-        int wg_per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_per_cu, fn, 256, 0) != hipSuccess || wg_per_cu < 1) wg_per_cu = 4;
-        return (long)c->n_cu * 4 * wg_per_cu;
-    };
-    constexpr bool SPLIT = LAPM_SPLIT != 0;
-    const void *fn = R == 1 ? (const void *)lap_march_kernel<1, T, MASK, SPLIT> : R == 2 ? (const void *)lap_march_kernel<2, T, MASK, SPLIT>
-                   : R == 3 ? (const void *)lap_march_kernel<3, T, MASK, SPLIT> : R == 4 ? (const void *)lap_march_kernel<4, T, MASK, SPLIT>
-                   : (const void *)lap_march_kernel<5, T, MASK, SPLIT>;
-    int rows = km_pick_rows(H, (SPLIT ? 2 : 1) * nstrips, 2 * R, slots_of(fn), 32, 160);
-    if (const char *e = km_dev_env("KARIOS_HIP_LAP_ROWS")) { const int v = atoi(e); if (v >= 8 && v <= 4096) rows = v; }   // tuning override
-    const int nitems = nstrips * ((H + rows - 1) / rows);
-    const unsigned ntiles = (unsigned)((SPLIT ? 2 : 1) * nitems + 3) / 4u;
-    dim3 grid(km_xcd_grid(ntiles));
-    const size_t nwaves = SPLIT ? (size_t)nitems : (size_t)ntiles * 4;     // entries of the per-item valid counts
-    unsigned *valid = nullptr;
+    lapm_units_args A;
+    A.n = 1;
+    A.img0[0] = a; A.img1[0] = b; A.s0[0] = sa; A.s1[0] = sb; A.mm[0] = mm;
+    A.out0[0] = oa; A.out1[0] = ob; A.mask[0] = mask; A.valid[0] = nullptr;
+    A.H[0] = H; A.W[0] = W; A.nstrips[0] = (W + LAPM_VALID_OF(R) - 1) / LAPM_VALID_OF(R);
+    lapm_items(c, R, lapm_kernel<T, MASK>(R), A);     // (the occupancy of the instantiation that runs)
+    const unsigned nitems = (unsigned)A.item0[1];
     if (MASK) {
         // (a slot of its own: with the sum deferred to the second stream - below - the eigenvalue pass, which owns WS_PARTIAL, runs first)
-        valid = (unsigned *)km_ws(c, WS_LAP_VALID, ((size_t)ntiles * 4 + 4) * sizeof(unsigned));
-        if (!valid) return KM_E_NOMEM;
+        A.valid[0] = (unsigned *)km_ws(c, WS_LAP_VALID, ((size_t)nitems + 4) * sizeof(unsigned));
+        if (!A.valid[0]) return KM_E_NOMEM;
     }
-    switch (R) {
-    case 1: lap_march_kernel<1, T, MASK, SPLIT><<<grid, 256, 0, c->stream>>>(a, b, H, W, sa, sb, mm, cf, invert1, nd, oa, ob, mask, valid, nstrips, rows, nitems); break;
-    case 2: lap_march_kernel<2, T, MASK, SPLIT><<<grid, 256, 0, c->stream>>>(a, b, H, W, sa, sb, mm, cf, invert1, nd, oa, ob, mask, valid, nstrips, rows, nitems); break;
-    case 3: lap_march_kernel<3, T, MASK, SPLIT><<<grid, 256, 0, c->stream>>>(a, b, H, W, sa, sb, mm, cf, invert1, nd, oa, ob, mask, valid, nstrips, rows, nitems); break;
-    case 4: lap_march_kernel<4, T, MASK, SPLIT><<<grid, 256, 0, c->stream>>>(a, b, H, W, sa, sb, mm, cf, invert1, nd, oa, ob, mask, valid, nstrips, rows, nitems); break;
-    case 5: lap_march_kernel<5, T, MASK, SPLIT><<<grid, 256, 0, c->stream>>>(a, b, H, W, sa, sb, mm, cf, invert1, nd, oa, ob, mask, valid, nstrips, rows, nitems); break;
-    default: return km_fail(c, KM_E_INTERNAL, "lap_march radius %d", R);
-    }
-    KM_LAUNCH_CHECK(c);
+    if (int rc = lapm_launch<T, MASK>(c, R, A, cf, invert1, nd)) return rc;
     if (MASK) {
         if (c->defer_valid_sum) {
-            // the count of valid pixels is only read at the end of the unit (frame header, statistics): its one-workgroup sum leaves
-            // the critical path - klt_track_dev launches it on the second stream in front of the pyramids (kd_run_valid_sum)
-            c->valid_job_partial = valid; c->valid_job_n = (unsigned)nwaves; c->valid_job_out = valid_out; c->valid_job_pending = true;
+            // the count of valid pixels is only read at the end of the unit (frame header, statistics): its sum leaves the critical
+            // path - klt_track_dev launches it on the second stream in front of the pyramids (kd_run_valid_sum)
+            c->valid_job_partial = A.valid[0]; c->valid_job_n = nitems; c->valid_job_out = valid_out; c->valid_job_pending = true;
         } else {
-            sum_u32_kernel<<<1, 1024, 0, c->stream>>>(valid, (unsigned)nwaves, valid_out);
+            sum_u32_kernel<<<1, 1024, 0, c->stream>>>(A.valid[0], nitems, valid_out);
             KM_LAUNCH_CHECK(c);
         }
     }
     return KM_OK;
 }
 
-// the deferred sum of launch_lap_march, on whatever stream c->stream is at the moment
+// the deferred sum of launch_lap_march, on whatever stream c->stream is at the moment (one workgroup of 1024 threads: the single
+// wavefront of kd_valid_sum_units took 35 instead of 5 us over the ~3000 counts of a 10980^2 tile)
 int kd_run_valid_sum(km_ctx *c)
 {
     if (!c->valid_job_pending) return KM_OK;
@@ -1387,36 +1379,13 @@ static int launch_lap_march_units(km_ctx *c, int R, const km_units &U, const lap
         A.out0[u] = U.lap_ref[u]; A.out1[u] = U.lap_mon[u]; A.mask[u] = U.mask[u];
         A.H[u] = U.H[u]; A.W[u] = U.W[u]; A.nstrips[u] = (U.W[u] + LAPM_VALID_OF(R) - 1) / LAPM_VALID_OF(R);
     }
-    int wg_per_cu = 0;
-    const void *fn = R == 1 ? (const void *)lap_march_units_kernel<1, T, true> : R == 2 ? (const void *)lap_march_units_kernel<2, T, true>
-                   : R == 3 ? (const void *)lap_march_units_kernel<3, T, true> : R == 4 ? (const void *)lap_march_units_kernel<4, T, true>
-                   : (const void *)lap_march_units_kernel<5, T, true>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg_per_cu, fn, 256, 0) != hipSuccess || wg_per_cu < 1) wg_per_cu = 4;
-    const long slots = (long)c->n_cu * 4 * wg_per_cu;
-    // rows per item: the value in [32, 160] that minimises whole rounds of resident waves x the work of one item, over ALL units' strips
-    int rows = 32;
-    {
-        double best = 1e300;
-        for (int r = 32; r <= 160; r++) {
-            long items = 0;
-            for (int u = 0; u < U.n; u++) items += (long)A.nstrips[u] * ((U.H[u] + r - 1) / r);
-            const long rounds = (items + slots - 1) / slots;
-            const double last = (double)(items - (rounds - 1) * slots) / (double)slots;
-            const double cost = ((double)(rounds - 1) + 0.5 + 0.5 * last) * (double)(r + 2 * R);
-            if (cost < best) { best = cost; rows = r; }
-        }
-    }
-    if (const char *e = km_dev_env("KARIOS_HIP_LAP_ROWS")) { const int v = atoi(e); if (v >= 8 && v <= 4096) rows = v; }   // tuning override
-    A.rows = rows;
-    A.item0[0] = 0;
-    for (int u = 0; u < U.n; u++) A.item0[u + 1] = A.item0[u] + A.nstrips[u] * ((U.H[u] + rows - 1) / rows);
+    lapm_items(c, R, lapm_kernel<T, true>(R), A);
     const int total = A.item0[U.n];
     const int mask_wgs = 256;                         // workgroups per unit of the user-mask pack
     const size_t n_partial = U.has_user_mask ? (size_t)mask_wgs * U.n : (size_t)total + 4 * KM_UNITS_MAX;
     unsigned *valid = (unsigned *)km_ws(c, WS_LAP_VALID, n_partial * sizeof(unsigned));
     if (!valid) return KM_E_NOMEM;
     job->n = U.n;
-    const dim3 grid(km_xcd_grid((unsigned)(total + 3) / 4u));
     if (U.has_user_mask) {
         // the caller's mask: packed + counted here, the Laplacian pass derives none (MASK = false: it neither reads nor writes a mask)
         mask_units_args M;
@@ -1428,31 +1397,13 @@ static int launch_lap_march_units(km_ctx *c, int R, const km_units &U, const lap
         }
         mask_pack_units_kernel<<<dim3(mask_wgs, U.n), 256, 0, c->stream>>>(M);
         KM_LAUNCH_CHECK(c);
-        switch (R) {
-        case 1: lap_march_units_kernel<1, T, false><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-        case 2: lap_march_units_kernel<2, T, false><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-        case 3: lap_march_units_kernel<3, T, false><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-        case 4: lap_march_units_kernel<4, T, false><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-        case 5: lap_march_units_kernel<5, T, false><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-        default: return km_fail(c, KM_E_INTERNAL, "lap_march radius %d", R);
-        }
-        KM_LAUNCH_CHECK(c);
-        return KM_OK;
+        return lapm_launch<T, false>(c, R, A, cf, invert1, nd);
     }
     for (int u = 0; u < U.n; u++) {
         A.valid[u] = valid + A.item0[u];
         job->partial[u] = A.valid[u]; job->n_partial[u] = (unsigned)(A.item0[u + 1] - A.item0[u]); job->out[u] = &U.sc[u]->valid;
     }
-    switch (R) {
-    case 1: lap_march_units_kernel<1, T, true><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-    case 2: lap_march_units_kernel<2, T, true><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-    case 3: lap_march_units_kernel<3, T, true><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-    case 4: lap_march_units_kernel<4, T, true><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-    case 5: lap_march_units_kernel<5, T, true><<<grid, 256, 0, c->stream>>>(A, cf, invert1, nd); break;
-    default: return km_fail(c, KM_E_INTERNAL, "lap_march radius %d", R);
-    }
-    KM_LAUNCH_CHECK(c);
-    return KM_OK;
+    return lapm_launch<T, true>(c, R, A, cf, invert1, nd);
 }
 
 // The marching kernel at radius 5: every image's kernel as a 9-tap pass, kernel 11 as the 9-tap pass of kernel 9 + the 3 x 3 binomial
@@ -1675,49 +1626,6 @@ __global__ __launch_bounds__(256) void eig_kernel(const uint8_t *__restrict__ sr
     if (tid == 0) max_partial[blockIdx.y * gridDim.x + blockIdx.x] = max(max(s_key[0], s_key[1]), max(s_key[2], s_key[3]));
 }
 
-// ---- K3, fast path: one wavefront marches down a 64-column strip (64 - block - 1 output columns).
-// Each lane owns an image column.  Per row: 3-row register window -> Sobel with the two neighbour lanes
-// (DPP wave shifts) -> integer products -> horizontal box sum = difference of a wave prefix sum (DPP scan +
-// two ds_bpermute) -> vertical box sum = running sum over a `block`-deep register ring -> eigenvalue.
-// No LDS tiles, no barriers; exact integer arithmetic identical to the tiled kernel above.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_get0(int v)
-{
-    // full row mask: bound_ctrl makes the lanes without a source read 0, no register has to be cleared first
-    if constexpr (ROW_MASK == 0xf) return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, true);
-    else return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
-}
-
-// Correctly rounded float32 square root for x == 0 or x >= 2^-96 (the structure-tensor discriminant is 0 or >= 1e-18):
-// the hardware estimate (<= 1 ulp) corrected with two fused residuals - the sequence the compiler emits for sqrtf under
-// -fhip-fp32-correctly-rounded-divide-sqrt, without its rescaling of tiny arguments and its inf/zero special case
-// (for x == 0 the estimate is 0, both residual tests fail on NaN / 0 and 0 is returned).
-__device__ __forceinline__ float sqrt_rn_normal(float x)
-{
-    const float r = __builtin_amdgcn_sqrtf(x);
-    const float r_dn = __int_as_float(__float_as_int(r) - 1), r_up = __int_as_float(__float_as_int(r) + 1);
-    const float e_dn = __builtin_fmaf(-r_dn, r, x), e_up = __builtin_fmaf(-r_up, r, x);
-    float res = e_dn <= 0.f ? r_dn : r;
-    res = e_up > 0.f ? r_up : res;
-    return res;
-}
-
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += dpp_get0<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_get0<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_get0<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_get0<0x118, 0xf>(v);  // row_shr:8
-    v += dpp_get0<0x142, 0xa>(v);  // row_bcast:15 -> rows 1,3
-    v += dpp_get0<0x143, 0xc>(v);  // row_bcast:31 -> rows 2,3
-    return v;
-}
-
-#define EIG_RS 128  // output rows per wave segment
-#ifndef EIGM_CH
-#define EIGM_CH 3     // rows fetched ahead per batch (3: 78 VGPRs = 6 waves per SIMD at blockSize 15; 15: 104 VGPRs = 4 waves)
-#endif
-
 __device__ __forceinline__ float dpp_shr1(float v)  // value of lane-1 (0 for lane 0)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false));
@@ -1727,165 +1635,13 @@ __device__ __forceinline__ float dpp_shl1(float v)  // value of lane+1 (0 for la
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false));
 }
 
-// Writes the eig map + per-wave masked maxima (fallback of k_eig2.hip for images too small for its 128-column strips).
-template <int BLOCK>
-__global__ __launch_bounds__(256) KM_EIGM_OCC void eig_march_kernel(const uint8_t *__restrict__ src, const uint8_t *__restrict__ mask, int H, int W,
-                                                        double scale2, float *__restrict__ eig, unsigned int *__restrict__ max_partial,
-                                                        int nstrips, int gyw)
-{
-    constexpr int L = BLOCK / 2, Rr = BLOCK - 1 - L, VALID = 64 - BLOCK - 1;
-    constexpr int STRIDE = VALID;
-    const int lane = threadIdx.x & 63;
-    const int gxw = (nstrips + 3) / 4;                  // workgroups per row block (logical grid gxw x gyw, XCD-swizzled)
-    unsigned tile;
-    if (!km_xcd_tile((unsigned)(gxw * gyw), tile)) return;
-    const int bx = (int)tile % gxw, by = (int)tile / gxw;
-    const int strip = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform, known to the compiler
-    const int wave_id = by * (gxw * 4) + strip;
-    if (strip >= nstrips) { if (lane == 0) max_partial[wave_id] = 0u; return; }
-    const int xs = strip * STRIDE;
-    const int gx = xs - (L + 1) + lane;                  // image column of this lane (may be outside)
-    const int cx = km_reflect101(gx, W);                 // column the lane reads (REFLECT_101 of the image)
-    const bool xborder = (xs - (L + 1) < 0) || (xs - (L + 1) + 63 >= W);
-    // cov's own REFLECT_101 border: an outside column takes the products of the lane holding its mirror column
-    const int psrc = (cx - (xs - (L + 1))) * 4;
-    const bool out_lane = lane >= L + 1 && lane < L + 1 + VALID && gx < W;
-    const int hi_addr = min(lane + Rr, 63) * 4, lo_addr = max(lane - L - 1, 0) * 4;
-    const bool lo_zero = lane - L - 1 < 0;
-    const int y0 = by * EIG_RS, y1 = min(H, y0 + EIG_RS);
-    const uint8_t *col = src + cx;
-
-    int ring[BLOCK][3];
-#pragma unroll
-    for (int k = 0; k < BLOCK; k++) { ring[k][0] = 0; ring[k][1] = 0; ring[k][2] = 0; }
-    int V0 = 0, V1 = 0, V2 = 0;
-    int c1 = -1, c2 = -1;            // image rows cached in a1, a2
-    int a0 = 0, a1 = 0, a2 = 0;
-    float best = 0.f;
-    bool have = false;
-
-    for (int mbase = y0 - L; mbase < y1 + Rr; mbase += BLOCK) {
-        // steady state (no row mirrored in this group of BLOCK steps): issue all BLOCK row loads (and the mask
-        // bytes of the rows completed here) up front so their latency overlaps the arithmetic
-        const bool steady = mbase - 1 >= 0 && mbase + BLOCK <= H - 1;
-        // rows are fetched EIGM_CH at a time (source byte + mask byte of the row completed then): a deeper prefetch costs
-        // registers, i.e. resident waves, and the resident waves are what hides the latency of this kernel
-        constexpr int CH = BLOCK < EIGM_CH ? BLOCK : EIGM_CH;
-        int pre[CH], pmask[CH];
-        if (steady) {
-            if (!(c1 == mbase - 1 && c2 == mbase)) {
-                a1 = col[(size_t)(mbase - 1) * W]; a2 = col[(size_t)mbase * W];
-                c1 = mbase - 1; c2 = mbase;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < BLOCK; k++) {
-            if (k % CH == 0) {
-#pragma unroll
-                for (int j = 0; j < CH; j++) {
-                    if (k + j < BLOCK) {
-                        if (steady) pre[j] = col[(size_t)(mbase + k + j + 1) * W];
-                        pmask[j] = 1;
-                        const int yq = mbase + k + j - Rr;
-                        if (mask && out_lane && yq >= y0 && yq < y1) pmask[j] = mask[(size_t)yq * W + gx];
-                    }
-                }
-            }
-            const int m = mbase + k;                      // marching row (product row index, may be outside)
-            if (m >= y1 + Rr) continue;                   // (no break: the ring index must stay a compile-time constant)
-            if (steady) {
-                a0 = a1; a1 = a2; a2 = pre[k % CH];
-                c1 = m; c2 = m + 1;
-            } else {
-                const int r = km_reflect101(m, H);        // product row actually evaluated
-                const int n0 = km_reflect101(r - 1, H), n2 = km_reflect101(r + 1, H);
-                if (n0 == c1 && r == c2) {               // slide the window, one new row
-                    a0 = a1; a1 = a2; a2 = col[(size_t)n2 * W];
-                } else {
-                    a0 = col[(size_t)n0 * W]; a1 = col[(size_t)r * W]; a2 = col[(size_t)n2 * W];
-                }
-                c1 = r; c2 = n2;
-            }
-            // Sobel: vertical parts in-lane, horizontal parts from the neighbour lanes
-            const int t0 = a0 + 2 * a1 + a2, t1 = a2 - a0;
-            const int t0m = dpp_get0<0x138, 0xf>(t0), t0p = dpp_get0<0x130, 0xf>(t0);   // lane-1, lane+1
-            const int t1m = dpp_get0<0x138, 0xf>(t1), t1p = dpp_get0<0x130, 0xf>(t1);
-            const int dx = t0p - t0m, dy = t1m + 2 * t1 + t1p;
-            int pxx = __mul24(dx, dx), pxy = __mul24(dx, dy), pyy = __mul24(dy, dy);
-            if (xborder) {
-                pxx = __builtin_amdgcn_ds_bpermute(psrc, pxx);
-                pxy = __builtin_amdgcn_ds_bpermute(psrc, pxy);
-                pyy = __builtin_amdgcn_ds_bpermute(psrc, pyy);
-            }
-            // horizontal window [lane-L, lane+Rr] = S[lane+Rr] - S[lane-L-1]
-            const int s0 = wave_incl_scan(pxx), s1 = wave_incl_scan(pxy), s2 = wave_incl_scan(pyy);
-            int h0 = __builtin_amdgcn_ds_bpermute(hi_addr, s0), l0 = __builtin_amdgcn_ds_bpermute(lo_addr, s0);
-            int h1 = __builtin_amdgcn_ds_bpermute(hi_addr, s1), l1 = __builtin_amdgcn_ds_bpermute(lo_addr, s1);
-            int h2 = __builtin_amdgcn_ds_bpermute(hi_addr, s2), l2 = __builtin_amdgcn_ds_bpermute(lo_addr, s2);
-            if (lo_zero) { l0 = 0; l1 = 0; l2 = 0; }
-            h0 -= l0; h1 -= l1; h2 -= l2;
-            // vertical box sum: running sum over the last BLOCK rows
-            V0 += h0 - ring[k][0]; V1 += h1 - ring[k][1]; V2 += h2 - ring[k][2];
-            ring[k][0] = h0; ring[k][1] = h1; ring[k][2] = h2;
-            const int y = m - Rr;                         // output row completed by this step
-            if (y >= y0 && out_lane) {
-                const float cxx = (float)__dmul_rn((double)V0, scale2);
-                const float cxy = (float)__dmul_rn((double)V1, scale2);
-                const float cyy = (float)__dmul_rn((double)V2, scale2);
-                const float a = __fmul_rn(cxx, 0.5f), b = cxy, cc = __fmul_rn(cyy, 0.5f);
-                const float t = __fsub_rn(a, cc);
-                const float sq = __fadd_rn(__fmul_rn(t, t), __fmul_rn(b, b));
-                const float e = __fsub_rn(__fadd_rn(a, cc), sqrt_rn_normal(sq));
-                eig[(size_t)y * W + gx] = e;
-                if (pmask[k % CH]) { best = have ? fmaxf(best, e) : e; have = true; }
-            }
-        }
-    }
-    unsigned key = have ? eig_key(best) : 0u;
-    for (int o = 32; o > 0; o >>= 1) key = max(key, (unsigned)__shfl_xor((int)key, o));
-    if (lane == 0) {
-        max_partial[wave_id] = key;
-    }
-}
-
-template <int BLOCK>
-static int launch_eig_march(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, double scale2, float *d_eig,
-                            unsigned int *d_max_key)
-{
-    constexpr int VALID = 64 - BLOCK - 1;
-    const int nstrips = (W + VALID - 1) / VALID;
-    dim3 grid((nstrips + 3) / 4, (H + EIG_RS - 1) / EIG_RS);
-    const size_t nwaves = (size_t)grid.x * 4 * grid.y;
-    unsigned *partial = (unsigned *)km_ws(c, WS_PARTIAL, nwaves * sizeof(unsigned));
-    if (!partial) return KM_E_NOMEM;
-    eig_march_kernel<BLOCK><<<km_xcd_grid(grid.x * grid.y), 256, 0, c->stream>>>(d_src, d_mask, H, W, scale2, d_eig, partial, nstrips, (int)grid.y);
-    KM_LAUNCH_CHECK(c);
-    max_u32_kernel<<<1, 1024, 0, c->stream>>>(partial, (unsigned)nwaves, d_max_key);
-    KM_LAUNCH_CHECK(c);
-    return KM_OK;
-}
-
 int kd_min_eigen(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, float *d_eig,
                  unsigned int *d_max_key)
 {
     if (block < 1 || block > 31) return km_fail(c, KM_E_UNSUPPORTED, "blockSize %d (supported 1..31)", block);
-    static const int eig_mode = km_dev_env("KARIOS_HIP_EIG_KERNEL") ? atoi(km_dev_env("KARIOS_HIP_EIG_KERNEL")) : 2;   // 2: two pixels per lane, 1: one
-    if (eig_mode == 2) {
-        const int rc2 = k2_min_eigen(c, d_src, d_mask, H, W, block, d_eig, d_max_key);
-        if (rc2 != KM_E_UNSUPPORTED) return rc2;
-    }
+    const int rc2 = k2_min_eigen(c, d_src, d_mask, H, W, block, d_eig, d_max_key);
+    if (rc2 != KM_E_UNSUPPORTED) return rc2;
     const double scale = 1.0 / (4.0 * (double)block * 255.0);
-    if (W >= 2 * block + 4 && H >= 2 * block + 4) {   // mirror columns / rows stay inside one strip
-        switch (block) {
-        case 3: return launch_eig_march<3>(c, d_src, d_mask, H, W, scale * scale, d_eig, d_max_key);
-        case 5: return launch_eig_march<5>(c, d_src, d_mask, H, W, scale * scale, d_eig, d_max_key);
-        case 7: return launch_eig_march<7>(c, d_src, d_mask, H, W, scale * scale, d_eig, d_max_key);
-        case 9: return launch_eig_march<9>(c, d_src, d_mask, H, W, scale * scale, d_eig, d_max_key);
-        case 11: return launch_eig_march<11>(c, d_src, d_mask, H, W, scale * scale, d_eig, d_max_key);
-        case 15: return launch_eig_march<15>(c, d_src, d_mask, H, W, scale * scale, d_eig, d_max_key);
-        default: break;
-        }
-    }
     // generic LDS-tiled kernel: any block size 1..31, any image size
     const int L = block / 2, Rr = block - 1 - L;
     const int PW = EIG_TW + L + Rr, PH = EIG_TH + L + Rr, LW = (PW + 2 + 3) & ~3, LH = PH + 2;
@@ -2054,15 +1810,10 @@ int kd_candidates(km_ctx *c, const float *d_eig, const uint8_t *d_mask, int H, i
 // cv::pyrDown u8: separable [1 4 6 4 1], (sum + 128) >> 8, REFLECT_101, dst = ((W+1)/2, (H+1)/2).
 // Each thread owns 4 adjacent output columns and marches down PYR_RS output rows with a 5-deep register ring
 // of horizontal sums (two new source rows per output row, loaded one step ahead as 4 aligned dwords each).
-// Both images of a pair are processed by one launch (blockIdx.z).
+// Both images of a pair - of every unit of a batch - are processed by one launch (blockIdx.z).
 #ifndef PYR_RS
 #define PYR_RS 8    // output rows per thread: short items = more waves in different phases (0.14 ms at 32 rows, 0.098 at 8, 0.18 at 64; 10980^2 pair)
 #endif
-
-struct pyr_pair {
-    const uint8_t *src[2];
-    uint8_t *dst[2];
-};
 
 // horizontal [1 4 6 4 1] sums of 4 outputs from 16 source bytes starting at source column 8q-4: output j covers the
 // bytes 2j+2 .. 2j+6 - four of them through one v_dot4_u32_u8 with the coefficients (1,4,6,4), the fifth added on top
@@ -2173,12 +1924,8 @@ __device__ __forceinline__ void pyrdown_item(const uint8_t *__restrict__ src, ui
     pyrdown_quad<false>(src, dst, H, W, dw, q, y, y + 1);
 }
 
-__global__ __launch_bounds__(256) void pyrdown_kernel(pyr_pair pp, int H, int W, int dh, int dw, int nquads)
-{
-    pyrdown_item(pp.src[blockIdx.z], pp.dst[blockIdx.z], H, W, dh, dw, nquads);
-}
-
-// batched units: blockIdx.z = 2 * unit + image; the grid covers the largest unit, the others leave their surplus workgroups at once
+// blockIdx.z = 2 * unit + image (kd_pyrdown_u8: one image); the grid covers the largest unit, the others leave their surplus workgroups
+// at once
 struct pyr_units_args {
     const uint8_t *src[2 * KM_UNITS_MAX];
     uint8_t *dst[2 * KM_UNITS_MAX];
@@ -2197,6 +1944,14 @@ static inline int pyr_grid_x(int W)
     return (q_hi + 255) / 256 + 1;
 }
 
+// nimg images: grid.x for the widest level (pyr_grid_x), dh = the largest output height
+static int pyrdown_launch(km_ctx *c, const pyr_units_args &P, int gx, int dh, int nimg)
+{
+    pyrdown_units_kernel<<<dim3(gx, (dh + PYR_RS - 1) / PYR_RS, nimg), 256, 0, c->stream>>>(P);
+    KM_LAUNCH_CHECK(c);
+    return KM_OK;
+}
+
 // level l of both pyramids of every unit from level l - 1 (units whose pyramid ends below l are skipped by the caller: H = 0)
 int kd_pyrdown_units(km_ctx *c, const km_units &U, int level)
 {
@@ -2213,34 +1968,21 @@ int kd_pyrdown_units(km_ctx *c, const km_units &U, int level)
         n++;
     }
     if (n == 0) return KM_OK;
-    const dim3 grid(max_q, (max_dh + PYR_RS - 1) / PYR_RS, 2 * n);
-    pyrdown_units_kernel<<<grid, 256, 0, c->stream>>>(P);
-    KM_LAUNCH_CHECK(c);
-    return KM_OK;
-}
-
-static int launch_pyrdown(km_ctx *c, const pyr_pair &pp, int nimg, int H, int W)
-{
-    const int dh = (H + 1) / 2, dw = (W + 1) / 2;
-    const int nquads = (dw + 3) / 4;
-    dim3 grid(pyr_grid_x(W), (dh + PYR_RS - 1) / PYR_RS, nimg);
-    pyrdown_kernel<<<grid, 256, 0, c->stream>>>(pp, H, W, dh, dw, nquads);
-    KM_LAUNCH_CHECK(c);
-    return KM_OK;
+    return pyrdown_launch(c, P, max_q, max_dh, 2 * n);
 }
 
 int kd_pyrdown_u8(km_ctx *c, const uint8_t *d_src, int H, int W, uint8_t *d_dst)
 {
-    pyr_pair pp;
-    pp.src[0] = pp.src[1] = d_src; pp.dst[0] = pp.dst[1] = d_dst;
-    return launch_pyrdown(c, pp, 1, H, W);
+    pyr_units_args P;
+    P.src[0] = d_src; P.dst[0] = d_dst; P.H[0] = H; P.W[0] = W;
+    return pyrdown_launch(c, P, pyr_grid_x(W), (H + 1) / 2, 1);
 }
 
 int kd_pyrdown_u8_pair(km_ctx *c, const uint8_t *d_src_a, const uint8_t *d_src_b, int H, int W, uint8_t *d_dst_a, uint8_t *d_dst_b)
 {
-    pyr_pair pp;
-    pp.src[0] = d_src_a; pp.src[1] = d_src_b; pp.dst[0] = d_dst_a; pp.dst[1] = d_dst_b;
-    return launch_pyrdown(c, pp, 2, H, W);
+    pyr_units_args P;
+    P.src[0] = d_src_a; P.src[1] = d_src_b; P.dst[0] = d_dst_a; P.dst[1] = d_dst_b; P.H[0] = H; P.W[0] = W;
+    return pyrdown_launch(c, P, pyr_grid_x(W), (H + 1) / 2, 2);
 }
 
 // ------------------------------------------------------------------ K11 integer shift

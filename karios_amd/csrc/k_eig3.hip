@@ -457,40 +457,10 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
 #endif
 }
 
-// items [0, n_border): eig2_item on the two border strips (left: columns 0 .. MARGIN-1, right: W-MARGIN .. W-1), rows2 rows each;
-// items [n_border, nitems): eig3_item, rowblock-major over nstrips strips of rows3 rows
-template <int BLOCK>
-__global__ __launch_bounds__(256, 3) void eig3_kernel(const uint8_t *__restrict__ src, const uint8_t *__restrict__ mask, int H, int W, double scale2,
-                                                   unsigned *__restrict__ max_partial, int n_border, int rows2, int nstrips, int rows3, int nitems,
-                                                   double quality, km_scalars *sc, unsigned long long *__restrict__ keys, size_t cap, unsigned stage_cap2,
-                                                   unsigned stage_cap3, int count_skips)
-{
-    __shared__ int xs_scratch[4][3][128];
-    __shared__ unsigned long long stage[4][EIG3_STAGE + 64];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    unsigned tile;
-    if (!km_xcd_tile((unsigned)(nitems + 3) / 4u, tile)) return;
-    const int wave_id = (int)tile * 4 + wv;
-    if (wave_id >= nitems) { if (lane == 0) max_partial[wave_id] = 0u; return; }
-    if (wave_id < n_border) {
-        const int rowblock = wave_id >> 1;
-        const bool right = wave_id & 1;
-        constexpr int ML2 = eig2_geom<BLOCK, true>::ML;
-        eig2_item<BLOCK, true>(src, mask, H, W, scale2, nullptr, max_partial, rows2, quality, sc, keys, cap, stage_cap2, wave_id, rowblock,
-                               right ? W - EIG3_MARGIN - ML2 : -ML2, right ? W - EIG3_MARGIN : 0, right ? W : EIG3_MARGIN, &xs_scratch[wv][0][0], stage[wv]);
-        return;
-    }
-    const int j = wave_id - n_border;
-    const int rowblock = j / nstrips, strip = j - rowblock * nstrips;
-    const int xs = min(strip * EIG3_STRIDE, W - 512);
-    const int col_lo = EIG3_MARGIN + strip * EIG3_STRIDE, col_hi = min(col_lo + EIG3_STRIDE, W - EIG3_MARGIN);
-    const int ye0 = rowblock * rows3, ye1 = min(H - 1, ye0 + rows3 + 1);
-    eig3_item<BLOCK>(src, mask, H, W, scale2, max_partial, quality, sc, keys, cap, stage_cap3, wave_id, xs, col_lo, col_hi, ye0, ye1, stage[wv], count_skips);
-}
-
-// batched units: one linear item space over the units (unit u owns [item0[u], item0[u + 1]): its border items first, then its strips,
-// exactly the items of the single-unit launch); shards, running-threshold words and per-wave maxima are the unit's own
+// One linear item space over the units (a single tile: one unit); unit u owns [item0[u], item0[u + 1]):
+//   its items [0, n_border): eig2_item on the two border strips (left: columns 0 .. MARGIN-1, right: W-MARGIN .. W-1), rows2 rows each;
+//   its items [n_border, ...): eig3_item, rowblock-major over nstrips strips of rows3 rows.
+// Shards, running-threshold words and per-wave maxima are the unit's own.
 struct e3_units_args {
     const uint8_t *src[KM_UNITS_MAX], *mask[KM_UNITS_MAX];
     unsigned *max_partial[KM_UNITS_MAX];
@@ -499,6 +469,7 @@ struct e3_units_args {
     int H[KM_UNITS_MAX], W[KM_UNITS_MAX], n_border[KM_UNITS_MAX], nstrips[KM_UNITS_MAX];
     int item0[KM_UNITS_MAX + 1];
     int n, rows2, rows3;
+    int count_skips;      // (KM_DEV) "eig3_count"
 };
 template <int BLOCK>
 __global__ __launch_bounds__(256, 3) void eig3_units_kernel(e3_units_args U, double scale2, double quality, size_t cap, unsigned stage_cap2, unsigned stage_cap3)
@@ -532,11 +503,13 @@ __global__ __launch_bounds__(256, 3) void eig3_units_kernel(e3_units_args U, dou
     const int xs = min(strip * EIG3_STRIDE, W - 512);
     const int col_lo = EIG3_MARGIN + strip * EIG3_STRIDE, col_hi = min(col_lo + EIG3_STRIDE, W - EIG3_MARGIN);
     const int ye0 = rowblock * U.rows3, ye1 = min(H - 1, ye0 + U.rows3 + 1);
-    eig3_item<BLOCK>(src, mask, H, W, scale2, max_partial, quality, sc, keys, cap, stage_cap3, wave_id, xs, col_lo, col_hi, ye0, ye1, stage[wv]);
+    eig3_item<BLOCK>(src, mask, H, W, scale2, max_partial, quality, sc, keys, cap, stage_cap3, wave_id, xs, col_lo, col_hi, ye0, ye1, stage[wv],
+                     U.count_skips);
 }
 
+// single: one tile (k3_eig_candidates) - its own row rule, below
 template <int BLOCK>
-int launch_eig3_units(km_ctx *c, km_units &U, double scale2, double quality)
+int launch_eig3_units(km_ctx *c, km_units &U, double scale2, double quality, bool single)
 {
     e3_units_args A;
     A.n = U.n; A.rows2 = 64;
@@ -548,17 +521,20 @@ int launch_eig3_units(km_ctx *c, km_units &U, double scale2, double quality)
         A.n_border[u] = 2 * ((U.H[u] - 2 + A.rows2 - 1) / A.rows2);
         border_total += A.n_border[u];
     }
-    // rows per strip item: what the single-unit launch picks for the LARGEST unit alone (one round of 3 resident waves per SIMD: ~96 rows
-    // for a 10980^2 tile), clamped to [48, 96].  A batch is several rounds anyway, and measured at four 10980^2 units the item height, not
-    // the number of rounds, decides: 0.357 ms per unit at 96 rows, 0.347 at 64, 0.381 at 128, 0.423 at the ~192 rows a rounds x height
-    // cost model prefers (long items drain the last round slowly); 16 units of 5490^2 are flat between 48 and 128 rows.
+    // rows per strip item.  A single tile: 3 waves per SIMD are resident (168 VGPRs); the border items hold a slot each while they run.
+    // Measured at 10980^2: 0.336 ms with 96-row items (2645 + 344 items: one round), 0.341 at 48 (two rounds), 0.373 at 64 (1.4 rounds),
+    // 0.424 at 128 (slots left empty) - km_pick_rows (a warm-up row of an item costs about a third of a full row).  A batch: what that
+    // rule picks for the LARGEST unit alone (one round: ~96 rows for a 10980^2 tile), clamped to [48, 96].  A batch is several rounds
+    // anyway, and measured at four 10980^2 units the item height, not the number of rounds, decides: 0.357 ms per unit at 96 rows, 0.347
+    // at 64, 0.381 at 128, 0.423 at the ~192 rows a rounds x height cost model prefers (long items drain the last round slowly); 16 units
+    // of 5490^2 are flat between 48 and 128 rows.
     (void)border_total;
-    int rows3 = 48;
+    int rows3 = 0;
     for (int u = 0; u < U.n; u++) {
         const int r = km_pick_rows(U.H[u] - 2, A.nstrips[u], 5, 1024L * 3 - A.n_border[u], 32, 192);
         rows3 = r > rows3 ? r : rows3;
     }
-    rows3 = rows3 > 96 ? 96 : rows3;
+    if (!single) rows3 = std::min(std::max(rows3, 48), 96);
     if (const char *e = km_dev_env("KARIOS_HIP_EIG3_ROWS")) { const int v = atoi(e); if (v >= 8 && v <= 8192) rows3 = v; }   // tuning override
     A.rows3 = rows3;
     A.item0[0] = 0;
@@ -570,8 +546,10 @@ int launch_eig3_units(km_ctx *c, km_units &U, double scale2, double quality)
         A.max_partial[u] = partial + A.item0[u];
         U.eig_partial[u] = A.max_partial[u]; U.eig_npartial[u] = (unsigned)(A.item0[u + 1] - A.item0[u]);
     }
+    // "stage_cap" (test knob): usable slots of the per-wave key stage
     const unsigned cap2 = c->opt_stage_cap > 0 && c->opt_stage_cap < EIG2_STAGE ? (unsigned)c->opt_stage_cap : (unsigned)EIG2_STAGE;
     const unsigned cap3 = c->opt_stage_cap > 0 && c->opt_stage_cap < EIG3_STAGE ? (unsigned)c->opt_stage_cap : (unsigned)EIG3_STAGE;
+    A.count_skips = c->opt_eig3_count ? 1 : 0;
     eig3_units_kernel<BLOCK><<<km_xcd_grid((unsigned)(total + 3) / 4u), 256, 0, c->stream>>>(A, scale2, quality, U.capk, cap2, cap3);
     KM_LAUNCH_CHECK(c);
     return KM_OK;
@@ -592,37 +570,6 @@ __global__ __launch_bounds__(1024) void eig3_max_kernel(const unsigned *__restri
     }
 }
 
-template <int BLOCK>
-int launch_eig3(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, double scale2, double quality, km_scalars *sc,
-                unsigned long long *d_keys, size_t cap)
-{
-    const int nstrips = (W - 2 * EIG3_MARGIN + EIG3_STRIDE - 1) / EIG3_STRIDE;
-    const int rows2 = 64;
-    const int n_border = 2 * ((H - 2 + rows2 - 1) / rows2);
-    // 3 waves per SIMD are resident (168 VGPRs); the border items hold a slot each while they run.  Measured at 10980^2: 0.336 ms with
-    // 96-row items (2645 + 344 items: one round), 0.341 at 48 (two rounds), 0.373 at 64 (1.4 rounds), 0.424 at 128 (slots left empty)
-    int rows3 = km_pick_rows(H - 2, nstrips, 5, 1024L * 3 - n_border, 32, 192);   // (a warm-up row of an item costs about a third of a full row)
-    if (const char *e = km_dev_env("KARIOS_HIP_EIG3_ROWS")) { const int v = atoi(e); if (v >= 8 && v <= 8192) rows3 = v; }   // tuning override
-    const int nrowblocks = (H - 2 + rows3 - 1) / rows3;
-    const int nitems = n_border + nstrips * nrowblocks;
-    const unsigned ntiles = (unsigned)(nitems + 3) / 4u;
-    unsigned *partial = (unsigned *)km_ws(c, WS_PARTIAL, (size_t)ntiles * 4 * sizeof(unsigned));
-    if (!partial) return KM_E_NOMEM;
-    // "stage_cap" (test knob): usable slots of the per-wave key stage
-    const unsigned cap2 = c->opt_stage_cap > 0 && c->opt_stage_cap < EIG2_STAGE ? (unsigned)c->opt_stage_cap : (unsigned)EIG2_STAGE;
-    const unsigned cap3 = c->opt_stage_cap > 0 && c->opt_stage_cap < EIG3_STAGE ? (unsigned)c->opt_stage_cap : (unsigned)EIG3_STAGE;
-    eig3_kernel<BLOCK><<<km_xcd_grid(ntiles), 256, 0, c->stream>>>(d_src, d_mask, H, W, scale2, partial, n_border, rows2, nstrips, rows3, nitems, quality, sc,
-                                                                   d_keys, cap, cap2, cap3, c->opt_eig3_count ? 1 : 0);
-    KM_LAUNCH_CHECK(c);
-    if (c->eig_defer_max) {          // speculative corner path: kf_rank's first launch takes the maximum of the partials itself
-        c->eig_partial = partial; c->eig_npartial = ntiles * 4;
-        return KM_OK;
-    }
-    eig3_max_kernel<<<1, 1024, 0, c->stream>>>(partial, ntiles * 4, &sc->max_eig_key);
-    KM_LAUNCH_CHECK(c);
-    return KM_OK;
-}
-
 }  // namespace
 
 // Batched units (api_units.hip): the fused pass of every unit in ONE launch; the per-wave maxima stay in U.eig_partial[u] for the
@@ -634,7 +581,7 @@ int k3_eig_candidates_units(km_ctx *c, km_units &U, int block, double quality)
         if (U.W[u] < 512 || U.H[u] < 2 * block + 8) return KM_E_UNSUPPORTED;
     const double scale = 1.0 / (4.0 * (double)block * 255.0), s2 = scale * scale;
     switch (block) {
-#define KM_EIG3_CASE(B) case B: return launch_eig3_units<B>(c, U, s2, quality);
+#define KM_EIG3_CASE(B) case B: return launch_eig3_units<B>(c, U, s2, quality, false);
         KM_EIG3_CASE(1) KM_EIG3_CASE(3) KM_EIG3_CASE(5) KM_EIG3_CASE(7) KM_EIG3_CASE(9) KM_EIG3_CASE(11) KM_EIG3_CASE(13) KM_EIG3_CASE(15)
 #undef KM_EIG3_CASE
     default: return KM_E_UNSUPPORTED;
@@ -649,10 +596,22 @@ int k3_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, in
     if (block < 1 || block > 15 || (block & 1) == 0) return KM_E_UNSUPPORTED;
     if (W < 512 || H < 2 * block + 8) return KM_E_UNSUPPORTED;
     const double scale = 1.0 / (4.0 * (double)block * 255.0), s2 = scale * scale;
+    km_units U;
+    U.n = 1; U.H[0] = H; U.W[0] = W; U.capk = cap;
+    U.lap_ref[0] = const_cast<uint8_t *>(d_src); U.mask[0] = const_cast<uint8_t *>(d_mask); U.sc[0] = sc; U.keys[0] = d_keys;
+    int rc;
     switch (block) {
-#define KM_EIG3_CASE(B) case B: return launch_eig3<B>(c, d_src, d_mask, H, W, s2, quality, sc, d_keys, cap);
+#define KM_EIG3_CASE(B) case B: rc = launch_eig3_units<B>(c, U, s2, quality, true); break;
         KM_EIG3_CASE(1) KM_EIG3_CASE(3) KM_EIG3_CASE(5) KM_EIG3_CASE(7) KM_EIG3_CASE(9) KM_EIG3_CASE(11) KM_EIG3_CASE(13) KM_EIG3_CASE(15)
 #undef KM_EIG3_CASE
     default: return KM_E_UNSUPPORTED;
     }
+    if (rc) return rc;
+    if (c->eig_defer_max) {          // speculative corner path: kf_rank's first launch takes the maximum of the partials itself
+        c->eig_partial = U.eig_partial[0]; c->eig_npartial = U.eig_npartial[0];
+        return KM_OK;
+    }
+    eig3_max_kernel<<<1, 1024, 0, c->stream>>>(U.eig_partial[0], U.eig_npartial[0], &sc->max_eig_key);
+    KM_LAUNCH_CHECK(c);
+    return KM_OK;
 }

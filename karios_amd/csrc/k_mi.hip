@@ -295,18 +295,7 @@ __device__ __forceinline__ void mi_int_item(const T *__restrict__ ref, const T *
     }
 }
 
-// c ln c for c = 0 .. 57^2 (float64, host libm), in a workspace slot of the context
-template <typename T>
-__global__ __launch_bounds__(256) void mi_int_kernel(const T *__restrict__ ref, const T *__restrict__ mon, int Href, int Wref, int Hmon, int Wmon,
-                                                     ptrdiff_t sref, ptrdiff_t smon, const float *__restrict__ x0, const float *__restrict__ y0,
-                                                     const float *__restrict__ dx, const float *__restrict__ dy, int n, const int *__restrict__ d_n,
-                                                     const float *__restrict__ score, float score_thr, double *__restrict__ out_studholme,
-                                                     double *__restrict__ out_nmi, km_window win, const double *__restrict__ clogc)
-{
-    __shared__ unsigned s_hist[4][MI_BINS * MI_BINS];
-    mi_int_item<T>(ref, mon, Href, Wref, Hmon, Wmon, sref, smon, x0, y0, dx, dy, n, d_n, score, score_thr, out_studholme, out_nmi, win, clogc, s_hist);
-}
-// batched units: blockIdx.y = unit
+// blockIdx.y = unit (kmi_batch: one unit)
 template <typename T>
 __global__ __launch_bounds__(256) void mi_int_units_kernel(km_score_units A, int n, float score_thr, const double *__restrict__ clogc)
 {
@@ -316,6 +305,7 @@ __global__ __launch_bounds__(256) void mi_int_units_kernel(km_score_units A, int
                    U.out, U.out2, U.win, clogc, s_hist);
 }
 
+// c ln c for c = 0 .. 57^2 (float64, host libm), in a workspace slot of the context
 static const double *mi_table(km_ctx *c)
 {
     // (a table that outlives the call: always the context's lane-0 slot - the lanes of pipelined batched submissions share it)
@@ -357,19 +347,10 @@ int kmi_batch(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int Hr
 {
     if (n <= 0) return KM_OK;
     if (dtype != KM_F32) {
-        const double *tab = mi_table(c);
-        if (!tab) return KM_E_NOMEM;
-        const int nbx = (int)km_xcd_grid((unsigned)((n + 3) / 4));
-#define KM_MII(T) mi_int_kernel<T><<<nbx, 256, 0, c->stream>>>((const T *)d_ref, (const T *)d_mon, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, d_n, d_score, score_thr, d_studholme, d_nmi, c->window, tab)
-        switch (dtype) {
-        case KM_U8: KM_MII(uint8_t); break;
-        case KM_U16: KM_MII(uint16_t); break;
-        case KM_I16: KM_MII(int16_t); break;
-        default: return km_fail(c, KM_E_ARG, "mi: bad dtype %d", dtype);
-        }
-#undef KM_MII
-        KM_LAUNCH_CHECK(c);
-        return KM_OK;
+        km_score_units A;
+        A.u[0] = {d_ref, d_mon, d_x0, d_y0, d_dx, d_dy, d_score, d_n, d_studholme, d_nmi, sref, smon, Href, Wref, Hmon, Wmon, c->window};
+        const int rc = kmi_units(c, A, 1, dtype, n, score_thr);
+        return rc == KM_E_UNSUPPORTED ? km_fail(c, KM_E_ARG, "mi: bad dtype %d", dtype) : rc;
     }
     const int nb = (n + 3) / 4;
 #define KM_MI(T) mi_kernel<T><<<nb, 256, 0, c->stream>>>((const T *)d_ref, (const T *)d_mon, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, d_n, d_score, score_thr, d_studholme, d_nmi, c->window)

@@ -162,15 +162,7 @@ __device__ __forceinline__ void zncc_int_item(const T *__restrict__ ref, const T
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void zncc_int_kernel(const T *__restrict__ ref, const T *__restrict__ mon, int Href, int Wref, int Hmon, int Wmon,
-                                                       ptrdiff_t sref, ptrdiff_t smon, const float *__restrict__ x0, const float *__restrict__ y0,
-                                                       const float *__restrict__ dx, const float *__restrict__ dy, int n, const int *__restrict__ d_n,
-                                                       const float *__restrict__ score, float score_thr, double *__restrict__ out, km_window win)
-{
-    zncc_int_item<T>(ref, mon, Href, Wref, Hmon, Wmon, sref, smon, x0, y0, dx, dy, n, d_n, score, score_thr, out, win);
-}
-// batched units: blockIdx.y = unit
+// blockIdx.y = unit (kz_zncc_filtered: one unit)
 template <typename T>
 __global__ __launch_bounds__(256) void zncc_int_units_kernel(km_score_units A, int n, float score_thr)
 {
@@ -205,19 +197,13 @@ int kz_zncc_filtered(km_ctx *c, const void *d_ref, const void *d_mon, int dtype,
                      const float *d_score, float score_thr, double *d_out)
 {
     if (n <= 0) return KM_OK;
-    const int nb = (int)km_xcd_grid((unsigned)((n + 3) / 4));
     if (dtype != KM_F32) {
-#define KM_ZI(T) zncc_int_kernel<T><<<nb, 256, 0, c->stream>>>((const T *)d_ref, (const T *)d_mon, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, d_n, d_score, score_thr, d_out, c->window)
-        switch (dtype) {
-        case KM_U8: KM_ZI(uint8_t); break;
-        case KM_U16: KM_ZI(uint16_t); break;
-        case KM_I16: KM_ZI(int16_t); break;
-        default: return km_fail(c, KM_E_ARG, "zncc: bad dtype %d", dtype);
-        }
-#undef KM_ZI
-        KM_LAUNCH_CHECK(c);
-        return KM_OK;
+        km_score_units A;
+        A.u[0] = {d_ref, d_mon, d_x0, d_y0, d_dx, d_dy, d_score, d_n, d_out, nullptr, sref, smon, Href, Wref, Hmon, Wmon, c->window};
+        const int rc = kz_zncc_units(c, A, 1, dtype, n, score_thr);
+        return rc == KM_E_UNSUPPORTED ? km_fail(c, KM_E_ARG, "zncc: bad dtype %d", dtype) : rc;
     }
+    const int nb = (int)km_xcd_grid((unsigned)((n + 3) / 4));
 #define KM_Z(T) zncc_kernel<T><<<nb, 256, 0, c->stream>>>((const T *)d_ref, (const T *)d_mon, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, d_n, d_score, score_thr, d_out, c->window)
     KM_Z(float);           // (integer pixels: exact integer moments above)
 #undef KM_Z

@@ -12,7 +12,7 @@ for r in rows:
         wins.append(cur); cur = []
     cur.append(r); end = e if end is None else max(end, e)
 wins.append(cur)
-wins = [w for w in wins if sum('lap_march_units_kernel' in r['Kernel_Name'] for r in w) >= 4]
+wins = [w for w in wins if sum('valid_sum_units_kernel' in r['Kernel_Name'] for r in w) >= 4]   # (once per batched submission)
 w = wins[-1]
 t0 = int(w[0]["Start_Timestamp"])
 names = {"mm": "minmax_partial_units", "L": "lap_march_units", "K": "lk2_units", "E": "eig3_units", "P": "pyrdown_units", "Z": "zncc_int_units"}

@@ -13,10 +13,10 @@ for r in rows:
         wins.append(cur); cur = []
     cur.append(r); end = e if end is None else max(end, e)
 wins.append(cur)
-wins = [w for w in wins if sum('lap_march_units_kernel' in r['Kernel_Name'] for r in w) >= 3]
+wins = [w for w in wins if sum('valid_sum_units_kernel' in r['Kernel_Name'] for r in w) >= 3]   # (once per batched submission)
 w = wins[-int(sys.argv[2]) if len(sys.argv) > 2 else -1]
 t0 = int(w[0]["Start_Timestamp"]); t1 = max(int(r["End_Timestamp"]) for r in w)
-nl = sum('lap_march_units_kernel' in r['Kernel_Name'] for r in w)
+nl = sum('valid_sum_units_kernel' in r['Kernel_Name'] for r in w)
 print(f"window: {len(w)} kernels, {nl} submissions, {(t1 - t0) / 1e3:.1f} us from the first kernel's start to the last one's end")
 busy_end = t0
 big = ('lap_march_units', 'eig3_units', 'lk2_units', 'partial_units', 'pyrdown_units', 'ncc_int_units', 'f_sweep')

@@ -17,26 +17,26 @@ import sys
 STAGES = {   # stage key -> kernel-name fragments
     "minmax": ("minmax_partial", "minmax_final"),            # (incl. the *_units_kernel forms of a batched submission)
     "stretch_laplacian_mask": ("lap_march", "lap_kernel", "sum_u32", "valid_sum_units"),
-    "min_eigen_candidates_fused": ("eig3_kernel", "eig3_units_kernel", "eig2_kernel", "eig3_max"),
+    "min_eigen_candidates_fused": ("eig3_units_kernel", "eig2_kernel", "eig3_max"),
     "rank_select": ("f_hist_cut", "f_scatter_cells", "f_sweep", "f_acc_", "tk_hist", "f_cut", "f_cells"),
-    "pyramid": ("pyrdown_kernel", "pyrdown_units_kernel"),
+    "pyramid": ("pyrdown_units_kernel",),
     "lk_fwd_bwd": ("lk2_kernel", "lk2_units_kernel", "lk_kernel"),
     "fb_frame": ("fb_compact", "fb_place", "fb_gather"),
-    "zncc": ("zncc_kernel", "zncc_int_kernel", "zncc_int_units_kernel"),
+    "zncc": ("zncc_kernel", "zncc_int_units_kernel"),
     "phase_correlation_f32": ("fft_rows", "fft61_", "transpose_kernel", "cross_power_f32", "argmax_f32", "fft_"),
     "shift_image": ("shift_kernel", "shift_rows_kernel"),
-    "mi_kernel": ("mi_kernel", "mi_int_kernel", "mi_int_units_kernel"),
+    "mi_kernel": ("mi_kernel", "mi_int_units_kernel"),
     "dn_keep": ("dn_keep_kernel",),
     "phase_correlation_f64": ("f64_prime_kernel", "f64_smooth_kernel", "f64_cross_kernel", "f64_best_reduce", "f64_pack", "f64_absmax", "f64_first_index"),
     "phase_f64_prime_level": ("f64_prime_kernel",),
     "phase_f64_smooth_level": ("f64_smooth_kernel",),
     "phase_f64_cross_power": ("f64_cross_kernel",),
 }
-ONCE_PER_PAIR = {"config2": "lk2_kernel", "config2_batched": "lk2_units_kernel", "config3": "f61_top2_reduce", "scoring": "mi_int_kernel", "dn": "dn_keep_kernel", "f64": "f64_best_reduce"}
+ONCE_PER_PAIR = {"config2": "lk2_kernel", "config2_batched": "lk2_units_kernel", "config3": "f61_top2_reduce", "scoring": "mi_int_units_kernel", "dn": "dn_keep_kernel", "f64": "f64_best_reduce"}
 
 
 def short_name(kernel: str) -> str:
-    """'void (anonymous namespace)::eig3_kernel<15>(unsigned char const*, ...)' -> 'eig3_kernel<15>': the full kernel name with its
+    """'void (anonymous namespace)::eig3_units_kernel<15>(...)' -> 'eig3_units_kernel<15>': the full kernel name with its
     template arguments, without return type, anonymous namespace and parameter list."""
     n = kernel.strip()
     if n.startswith("void "):

@@ -5,7 +5,7 @@ import csv,sys,glob
 f=glob.glob(sys.argv[1]+'/**/*kernel_trace.csv',recursive=True)[0]
 rows=[r for r in csv.DictReader(open(f))]
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
-idx=[i for i,r in enumerate(rows) if 'lap_march_units_kernel' in r['Kernel_Name']]
+idx=[i for i,r in enumerate(rows) if 'valid_sum_units_kernel' in r['Kernel_Name']]   # (once per batched submission; single tiles run the K2 kernel too)
 k=len(idx)//2+(int(sys.argv[2]) if len(sys.argv)>2 else 0)
 a,b=idx[k],idx[k+1]
 t0=int(rows[a]['Start_Timestamp']); prev=t0
