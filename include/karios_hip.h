@@ -482,6 +482,50 @@ int km_refine_ecc_candidates_dev(km_ctx *ctx, const uint8_t *d_mon, int hm, int 
                                  int wr, ptrdiff_t ref_stride, int n, const double *inits, int max_iter, double eps, double *final_out,
                                  float *residual_out, double *cc_out, int *iterations_out, int64_t *valid_out, int *status_out);
 
+/* ---- Preprocessing of the global align step and the quality check's percentiles (api_prep.hip, k_prep.hip) -------------------------
+ * _to_uint8 / _preprocess of karios/matcher/global_align.py:87-108 and the np.nanpercentile calls of karios/api/core.py:491-506.
+ * The arithmetic is restated in tests/prep_restatement.py (the definition the kernels are tested against, bit for bit).
+ *
+ * Exact order statistics of an H x W raster (KM_U8, KM_U16, KM_I16 or KM_F32; anything else KM_E_ARG).  Every pixel is taken as a
+ * float32 (exact for the integer types).  exclude 0: NaN is left out (np.nanpercentile); 1: every non-finite value is left out
+ * (_to_uint8).  *n = number of values kept.  For each of the n_q quantiles q[j] in [0, 1], with vi = (double)(n - 1) * q[j] (the
+ * virtual index of numpy's 'linear' method): v0[j] = the value of rank floor(vi) among the kept values in ascending order,
+ * v1[j] = the value of rank min(floor(vi) + 1, n - 1), vi_out[j] = vi.  The values are exact (a radix select on an
+ * order-preserving key of the float32 bit pattern, three passes over the raster, integer counters: bitwise repeatable); -0.0 sorts
+ * below +0.0.  n = 0 is not an error: *n = 0 and v0 / v1 / vi_out are left alone.  The interpolation between v0 and v1 is the
+ * caller's (numpy does it in the source dtype: karios_amd/ops.py).  q, n, v0, v1, vi_out: host memory in both forms. */
+int km_order_statistics(km_ctx *ctx, const void *img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q,
+                        int64_t *n, double *v0, double *v1, double *vi_out);
+int km_order_statistics_dev(km_ctx *ctx, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q,
+                            const double *q, int64_t *n, double *v0, double *v1, double *vi_out);
+/* The stretch of _to_uint8 between two percentiles lo < hi, in float64 with every operation rounded on its own (what numpy >= 2
+ * evaluates: the percentiles are float64 scalars): v = (double)(float)pixel, t = ((v - lo) / (hi - lo)) * 255.0, clipped to
+ * [0, 255] and truncated toward zero.  NaN -> 0 (project choice: the C cast is undefined, x86 numpy gives 0), +inf -> 255,
+ * -inf -> 0.  Not (hi > lo): all zeros.  Same four dtypes.  The host form writes a contiguous H x W uint8 image. */
+int km_stretch_percentile_u8(km_ctx *ctx, const void *img, int dtype, int H, int W, ptrdiff_t stride, double lo, double hi,
+                             uint8_t *out);
+int km_stretch_percentile_u8_dev(km_ctx *ctx, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, double lo, double hi,
+                                 uint8_t *d_out, ptrdiff_t out_stride);
+/* cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply(img) of a uint8 image, OpenCV 4.8's CLAHE_Impl::apply restated:
+ *   - W % tiles_x == 0 and H % tiles_y == 0: the tiles divide the image.  Otherwise the image is extended on the right by
+ *     tiles_x - W % tiles_x and at the bottom by tiles_y - H % tiles_y with BORDER_REFLECT_101 (a dimension that IS divisible is then
+ *     extended by a whole tiles_x / tiles_y); tile size = extended size / grid;
+ *   - clip = max((int)(clip_limit * tile_area / 256), 1) (double arithmetic) when clip_limit > 0, else no clipping;
+ *     lut_scale = 255.0f / tile_area (float32);
+ *   - per tile: 256-bin histogram; bins above clip are cut to it, the excess summed; excess / 256 goes to every bin, the residual
+ *     one each to bins 0, step, 2 step, ... (step = max(256 / residual, 1)); LUT[i] = saturate_cast<uchar>(cumsum_i * lut_scale)
+ *     (int -> float32, one float32 multiply, round half to even);
+ *   - over the original H x W: txf = x * (1.0f / tile_w) - 0.5f, tx1 = floor(txf), tx2 = tx1 + 1, xa = txf - tx1, xa1 = 1.0f - xa,
+ *     tx1 = max(tx1, 0), tx2 = min(tx2, tiles_x - 1), the same in y;
+ *     res = (L[ty1][tx1][v] * xa1 + L[ty1][tx2][v] * xa) * ya1 + (L[ty2][tx1][v] * xa1 + L[ty2][tx2][v] * xa) * ya, every operation a
+ *     float32 rounding of its own in this order (no fused multiply-add), rounded half to even and saturated.
+ * KM_E_ARG for what the reflection cannot define: an extension larger than size - 1 in a dimension, a grid with more than 64 KB
+ * of LUTs (tiles_x * tiles_y > 256), fewer than one pixel per tile.  The host form writes a contiguous H x W image; in-place
+ * (d_out == d_img) is not supported. */
+int km_clahe(km_ctx *ctx, const uint8_t *img, int H, int W, ptrdiff_t stride, double clip_limit, int tiles_x, int tiles_y, uint8_t *out);
+int km_clahe_dev(km_ctx *ctx, const uint8_t *d_img, int H, int W, ptrdiff_t stride, double clip_limit, int tiles_x, int tiles_y,
+                 uint8_t *d_out, ptrdiff_t out_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ class KmUnit(C.Structure):
 
 
 UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
+E_ARG = -1                     # KM_E_ARG
 E_UNSUPPORTED = -4             # KM_E_UNSUPPORTED
 E_NO_CONVERGENCE = -7          # KM_E_NO_CONVERGENCE
 ECC_CONVERGED, ECC_SKIPPED, ECC_NO_CONVERGENCE = 0, 1, 2   # KM_ECC_*
@@ -144,6 +145,12 @@ SIGNATURES = {
     "km_find_transform_ecc_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _sz, _vp, _sz, _vp, _i, _d, _i, _pd, _pi]),
     "km_refine_ecc_candidates": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "km_refine_ecc_candidates_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "km_order_statistics": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _i, _pd, C.POINTER(C.c_int64), _pd, _pd, _pd]),
+    "km_order_statistics_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _i, _pd, C.POINTER(C.c_int64), _pd, _pd, _pd]),
+    "km_stretch_percentile_u8": (_i, [_vp, _vp, _i, _i, _i, _sz, _d, _d, _vp]),
+    "km_stretch_percentile_u8_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _d, _d, _vp, _sz]),
+    "km_clahe": (_i, [_vp, _vp, _i, _i, _sz, _d, _i, _i, _vp]),
+    "km_clahe_dev": (_i, [_vp, _vp, _i, _i, _sz, _d, _i, _i, _vp, _sz]),
 }
 
 _lib = None

@@ -129,6 +129,22 @@ __attribute__((weak)) int km_refine_ecc_candidates_dev(km_ctx *c, const uint8_t 
                                                        const double *, int, double, double *, float *, double *, int *, int64_t *, int *)
 { KM_ALIGN_ABSENT("refine_ecc_candidates"); }
 #undef KM_ALIGN_ABSENT
+// ... and of the align step's preprocessing (api_prep.hip), the same way
+#define KM_PREP_ABSENT(name) return km_fail(c, KM_E_UNSUPPORTED, name ": built without api_prep.hip")
+__attribute__((weak)) int km_order_statistics(km_ctx *c, const void *, int, int, int, ptrdiff_t, int, int, const double *, int64_t *, double *, double *,
+                                              double *)
+{ KM_PREP_ABSENT("order_statistics"); }
+__attribute__((weak)) int km_order_statistics_dev(km_ctx *c, const void *, int, int, int, ptrdiff_t, int, int, const double *, int64_t *, double *,
+                                                  double *, double *)
+{ KM_PREP_ABSENT("order_statistics"); }
+__attribute__((weak)) int km_stretch_percentile_u8(km_ctx *c, const void *, int, int, int, ptrdiff_t, double, double, uint8_t *)
+{ KM_PREP_ABSENT("stretch_percentile_u8"); }
+__attribute__((weak)) int km_stretch_percentile_u8_dev(km_ctx *c, const void *, int, int, int, ptrdiff_t, double, double, uint8_t *, ptrdiff_t)
+{ KM_PREP_ABSENT("stretch_percentile_u8"); }
+__attribute__((weak)) int km_clahe(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, double, int, int, uint8_t *) { KM_PREP_ABSENT("clahe"); }
+__attribute__((weak)) int km_clahe_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, double, int, int, uint8_t *, ptrdiff_t)
+{ KM_PREP_ABSENT("clahe"); }
+#undef KM_PREP_ABSENT
 
 const char *km_last_error(km_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 
@@ -272,6 +288,7 @@ int km_set_option(km_ctx *c, const char *name, int value)
     if (strcmp(name, "aux_early") == 0) { c->opt_aux_early = value != 0; return KM_OK; }
     if (strcmp(name, "aux_priority") == 0) { c->opt_aux_priority = value != 0; return KM_OK; }   // (before the first tile: the stream is created once)
     if (strcmp(name, "eig3_count") == 0) { c->opt_eig3_count = value != 0; return KM_OK; }
+    if (strcmp(name, "prep_hist_plain") == 0) { c->opt_prep_plain = value != 0; return KM_OK; }
 #endif
     return km_fail(c, KM_E_ARG, "km_set_option: unknown option '%s'", name);
 }

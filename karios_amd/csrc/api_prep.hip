@@ -1,0 +1,152 @@
+// The dense front half of the global align step (karios/matcher/global_align.py:87-108, _to_uint8 and _preprocess) and the
+// percentiles of the quality check (karios/api/core.py:491-506): exact order statistics of a raster, the percentile stretch to uint8
+// and CLAHE.  The kernels live in k_prep.hip.  The interpolation between the two order statistics of a percentile is numpy's and stays
+// with the caller (karios_amd/ops.py): it is arithmetic of the SOURCE dtype there, wrap-around of int16 included.
+#include "api_internal.hpp"
+#include "k_prep.hpp"
+
+#include <stddef.h>
+#include <string.h>
+
+namespace {
+
+bool prep_dtype(int dtype) { return dtype == KM_U8 || dtype == KM_U16 || dtype == KM_I16 || dtype == KM_F32; }
+
+int stats_args(km_ctx *c, const void *img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q, const int64_t *n_out,
+               const double *v0, const double *v1, const double *vi)
+{
+    int rc;
+    if ((rc = check_image(c, img, H, W, stride, "order_statistics"))) return rc;
+    if (!prep_dtype(dtype)) return km_fail(c, KM_E_ARG, "order_statistics: dtype %d (uint8, uint16, int16 and float32 only)", dtype);
+    if (exclude != 0 && exclude != 1) return km_fail(c, KM_E_ARG, "order_statistics: exclude %d (0: NaN, 1: every non-finite value)", exclude);
+    if (n_q < 0 || !n_out || (n_q && (!q || !v0 || !v1 || !vi))) return km_fail(c, KM_E_ARG, "order_statistics: bad arguments");
+    for (int j = 0; j < n_q; j++)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return km_fail(c, KM_E_ARG, "order_statistics: quantile %d = %g outside [0, 1]", j, q[j]);
+    if ((unsigned long long)H * (unsigned long long)W >= (1ull << 42))   // (a workgroup's 32-bit LDS counters hold its share of the raster)
+        return km_fail(c, KM_E_ARG, "order_statistics: %d x %d raster", H, W);
+    return KM_OK;
+}
+
+// The quantiles go through the select KP_MAX_Q at a time: three passes per group, no host synchronisation inside a group, one copy of
+// its results at the end.
+int stats_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q, int64_t *n_out,
+              double *v0, double *v1, double *vi)
+{
+    kp_state *st = (kp_state *)km_ws(c, WS_PR_STATE, sizeof(kp_state));
+    if (!st) return KM_E_NOMEM;
+    struct { long long n; double vi[KP_MAX_Q], v0[KP_MAX_Q], v1[KP_MAX_Q]; } res;
+    static_assert(sizeof(res) == sizeof(kp_state) - offsetof(kp_state, n), "results are the tail of kp_state");
+    bool plain = false;
+#ifdef KM_DEV
+    plain = c->opt_prep_plain;
+#endif
+    int j0 = 0;
+    do {
+        const int m = n_q - j0 < KP_MAX_Q ? n_q - j0 : KP_MAX_Q;
+        int rc;
+        if ((rc = kp_order_statistics(c, d_img, dtype, H, W, stride, exclude, m, q + j0, st, plain))) return rc;
+        KM_D2H(c, &res, &st->n, sizeof(res));
+        KM_FLUSH(c);
+        *n_out = (int64_t)res.n;
+        if (res.n > 0)
+            for (int j = 0; j < m; j++) { vi[j0 + j] = res.vi[j]; v0[j0 + j] = res.v0[j]; v1[j0 + j] = res.v1[j]; }
+        j0 += m;
+    } while (j0 < n_q);
+    return KM_OK;
+}
+
+int stretch_args(km_ctx *c, const void *img, int dtype, int H, int W, ptrdiff_t stride, const void *out, ptrdiff_t ostride)
+{
+    int rc;
+    if ((rc = check_image(c, img, H, W, stride, "stretch_percentile_u8")) || (rc = check_image(c, out, H, W, ostride, "stretch_percentile_u8 output")))
+        return rc;
+    if (!prep_dtype(dtype)) return km_fail(c, KM_E_ARG, "stretch_percentile_u8: dtype %d (uint8, uint16, int16 and float32 only)", dtype);
+    return KM_OK;
+}
+
+int clahe_args(km_ctx *c, const void *img, int H, int W, ptrdiff_t stride, double clip_limit, int tiles_x, int tiles_y, const void *out,
+               ptrdiff_t ostride, kp_clahe_geom *g)
+{
+    int rc;
+    if ((rc = check_image(c, img, H, W, stride, "clahe")) || (rc = check_image(c, out, H, W, ostride, "clahe output"))) return rc;
+    if (clip_limit != clip_limit) return km_fail(c, KM_E_ARG, "clahe: clip limit is NaN");
+    return kp_clahe_geometry(c, H, W, clip_limit, tiles_x, tiles_y, g);
+}
+
+int clahe_dev(km_ctx *c, const uint8_t *d_img, int H, int W, ptrdiff_t stride, const kp_clahe_geom &g, uint8_t *d_out, ptrdiff_t ostride)
+{
+    const size_t tiles = (size_t)g.tiles_x * g.tiles_y;
+    unsigned *d_hist = (unsigned *)km_ws(c, WS_PR_CLAHE, tiles * 256 * (sizeof(unsigned) + 1));
+    if (!d_hist) return KM_E_NOMEM;
+    return kp_clahe(c, d_img, H, W, stride, g, d_hist, (uint8_t *)(d_hist + tiles * 256), d_out, ostride);
+}
+
+}  // namespace
+
+extern "C" {
+
+int km_order_statistics_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q,
+                            int64_t *n_out, double *v0, double *v1, double *vi)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = stats_args(c, d_img, dtype, H, W, stride, exclude, n_q, q, n_out, v0, v1, vi))) return rc;
+    return stats_dev(c, d_img, dtype, H, W, stride, exclude, n_q, q, n_out, v0, v1, vi);
+}
+
+int km_order_statistics(km_ctx *c, const void *img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q,
+                        int64_t *n_out, double *v0, double *v1, double *vi)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = stats_args(c, img, dtype, H, W, stride, exclude, n_q, q, n_out, v0, v1, vi))) return rc;
+    void *d_img;
+    if ((rc = upload_image(c, WS_RAW_A, img, km_dtype_size(dtype), H, W, stride, &d_img))) return rc;
+    return stats_dev(c, d_img, dtype, H, W, W, exclude, n_q, q, n_out, v0, v1, vi);
+}
+
+int km_stretch_percentile_u8_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, double lo, double hi, uint8_t *d_out,
+                                 ptrdiff_t out_stride)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = stretch_args(c, d_img, dtype, H, W, stride, d_out, out_stride))) return rc;
+    return kp_stretch(c, d_img, dtype, H, W, stride, lo, hi, d_out, out_stride);
+}
+
+int km_stretch_percentile_u8(km_ctx *c, const void *img, int dtype, int H, int W, ptrdiff_t stride, double lo, double hi, uint8_t *out)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = stretch_args(c, img, dtype, H, W, stride, out, W))) return rc;
+    void *d_img;
+    uint8_t *d_out = (uint8_t *)km_ws(c, WS_PR_OUT, (size_t)H * W);
+    if (!d_out) return KM_E_NOMEM;
+    if ((rc = upload_image(c, WS_RAW_A, img, km_dtype_size(dtype), H, W, stride, &d_img))) return rc;
+    if ((rc = kp_stretch(c, d_img, dtype, H, W, W, lo, hi, d_out, W))) return rc;
+    KM_D2H(c, out, d_out, (size_t)H * W);
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+int km_clahe_dev(km_ctx *c, const uint8_t *d_img, int H, int W, ptrdiff_t stride, double clip_limit, int tiles_x, int tiles_y, uint8_t *d_out,
+                 ptrdiff_t out_stride)
+{
+    int rc;
+    kp_clahe_geom g;
+    if ((rc = begin_call(c)) || (rc = clahe_args(c, d_img, H, W, stride, clip_limit, tiles_x, tiles_y, d_out, out_stride, &g))) return rc;
+    return clahe_dev(c, d_img, H, W, stride, g, d_out, out_stride);
+}
+
+int km_clahe(km_ctx *c, const uint8_t *img, int H, int W, ptrdiff_t stride, double clip_limit, int tiles_x, int tiles_y, uint8_t *out)
+{
+    int rc;
+    kp_clahe_geom g;
+    if ((rc = begin_call(c)) || (rc = clahe_args(c, img, H, W, stride, clip_limit, tiles_x, tiles_y, out, W, &g))) return rc;
+    void *d_img;
+    uint8_t *d_out = (uint8_t *)km_ws(c, WS_PR_OUT, (size_t)H * W);
+    if (!d_out) return KM_E_NOMEM;
+    if ((rc = upload_image(c, WS_RAW_A, img, 1, H, W, stride, &d_img))) return rc;
+    if ((rc = clahe_dev(c, (const uint8_t *)d_img, H, W, W, g, d_out, W))) return rc;
+    KM_D2H(c, out, d_out, (size_t)H * W);
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+}  // extern "C"

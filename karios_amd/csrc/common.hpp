@@ -109,6 +109,9 @@ enum km_slot {
     WS_AL_PLANE,    //   {image, gx, gy, pre-mask} float4 plane of the input
     WS_AL_PART,     //   fp64 partials of an ECC iteration + the reduced sums
     WS_AL_SCAL,     //   maximum of the Sobel magnitude, non-zero count
+    WS_PR_STATE,    // api_prep.hip: histograms, tracked prefixes and results of the radix select (kp_state)
+    WS_PR_CLAHE,    //   CLAHE's per-tile histograms and LUTs
+    WS_PR_OUT,      //   uint8 destination of the host-API stretch / CLAHE forms
     WS_COUNT
 };
 
@@ -290,6 +293,7 @@ struct km_ctx {
     unsigned valid_job_n = 0;
     unsigned long long *valid_job_out = nullptr;
     bool opt_eig3_count = false;   // (KM_DEV) "eig3_count": the fused 8-px eigenvalue pass counts the (wave, row, pixel slot) triples a bound could skip
+    bool opt_prep_plain = false;   // (KM_DEV) "prep_hist_plain": the radix select adds one LDS atomic per pixel instead of one per run of equal bins (A/B of DESIGN 12)
     bool opt_defer_valid = true;   // "defer_valid" 0: the sum stays behind the Laplacian pass on the main stream
     int f64_h = 0, f64_w = 0;      // shape whose tables sit in WS_F64_TW* / WS_F64_NEG* (k_fft64.hip)
     int opt_f64_prime_t = 0;       // "f64_prime_t": cap on the transforms per tile of the prime level kernel (0: as many as fit, <= 64)

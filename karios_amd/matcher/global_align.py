@@ -1,8 +1,9 @@
 """Global align step -- mirror of `karios.matcher.global_align` (reference global_align.py) on the GPU.
 
-The caller keeps `_preprocess` (percentile stretch + CLAHE), SIFT, BFMatcher and `cv2.findHomography` on cv2; this module takes
-over from the RANSAC matrix on: the ECC refinement of every candidate (`refine_global_alignment`, the candidate loop of
-`detect_global_alignment`) and the renders of `apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).
+`_to_uint8` and `_preprocess` (percentile stretch + CLAHE, the dense front half) run on the GPU; SIFT, BFMatcher and
+`cv2.findHomography` are sparse and stay with the caller on cv2; this module takes over again from the RANSAC matrix on: the ECC
+refinement of every candidate (`refine_global_alignment`, the candidate loop of `detect_global_alignment`) and the renders of
+`apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).
 Every GPU call goes through `karios_amd.ops`.  The reference's arithmetic is kept as it is, casts included; INTEGRATION.md
 section 6 notes the direction in which it composes the ECC residual.
 """
@@ -37,6 +38,19 @@ class GlobalAlignment:
     def score(self) -> float:
         """RANSAC inlier ratio in [0, 1]."""
         return self.n_inliers / self.n_matches if self.n_matches else 0.0
+
+
+def _to_uint8(arr: np.ndarray) -> np.ndarray:
+    """Stretch between the 2nd and 98th percentile of the finite values (global_align.py:87-101): uint8 input passes through
+    untouched, nothing finite gives zeros; other dtypes than uint16 / int16 / float32 go through astype(float32) on the host first.
+    One host synchronisation between the order statistics and the stretch, for numpy's interpolation."""
+    return ops.to_uint8_percentile(arr, (2.0, 98.0))
+
+
+def _preprocess(arr: np.ndarray) -> np.ndarray:
+    """uint8 stretch + CLAHE(clipLimit=2.0, tileGridSize=(8, 8)) to equalize radiometry across the two images
+    (global_align.py:104-108); the raster is uploaded once."""
+    return ops.preprocess(arr, (2.0, 98.0), 2.0, (8, 8))
 
 
 def _prior_from_georefs(monitored, reference) -> Optional[np.ndarray]:

@@ -4,7 +4,9 @@
                               ZNCC + both mutual-information scores of the rows with score >= confidence threshold,
                               CSV written tile by tile (`sep=";"`, header once, no index), frames concatenated;
   * `filter_by_dn_values`  - `KariosAPI._filter_by_dn_values` (core.py:650-737): drop the key points under which the
-                              reference or monitored image holds one of the excluded DN values / its no-data value.
+                              reference or monitored image holds one of the excluded DN values / its no-data value;
+  * `_check_quality`       - `KariosAPI._check_quality` (core.py:491-506): the dynamic range between the 2nd and 98th percentile
+                              of both rasters, a warning when it is 10 or less.
 
 The pixel work (ZNCC, MI / NMI, DN gather) runs on the device through `ResidentPair`; the column arithmetic and the
 CSV formatting are the reference's own numpy / pandas expressions.
@@ -15,12 +17,17 @@ import ctypes as C
 from pathlib import Path
 from typing import Iterable
 
+import logging
+
 import numpy as np
 import pandas as pd
 
+from . import ops
 from ._lib import KariosHipError
 from .frames import radial_angle_columns
 from .resident import ResidentPair
+
+logger = logging.getLogger(__name__)
 
 CSV_COLUMNS = ["x0", "y0", "dx", "dy", "score", "radial error", "angle", "zncc_score", "mutual_info_score", "mi_score"]
 
@@ -74,3 +81,24 @@ def filter_by_dn_values(points: pd.DataFrame, pair: ResidentPair, no_values=None
             raise IndexError(msg)                # numpy's fancy indexing raises for an out-of-bounds key point
         raise KariosHipError(f"km_dn_keep_dev: {msg}")
     return points[keep.astype(bool)].copy()
+
+
+def _dynamic_range(image) -> np.ndarray:
+    """np.nanpercentile(image.array, [2, 98]) (core.py:500, 504): on the GPU for 2-D uint8 / uint16 / int16 / float32 rasters, numpy
+    for anything else (float64 and 32-bit integer rasters: a float32 key would not order them exactly)."""
+    arr = image.array if hasattr(image, "array") else np.asarray(image)
+    if arr.ndim == 2 and arr.dtype in ops.PREP_DTYPES:
+        return ops.nanpercentile(arr, [2, 98])
+    return np.nanpercentile(arr, [2, 98])
+
+
+def _check_quality(monitored_image, reference_image) -> tuple:
+    """`KariosAPI._check_quality` (core.py:491-506): warn about a low dynamic range (98th - 2nd percentile <= 10) of either image.
+    -> the two percentile pairs (monitored, reference), which the reference discards."""
+    min_max_mon = _dynamic_range(monitored_image)
+    if min_max_mon[1] - min_max_mon[0] <= 10:
+        logger.warning("Low dynamic range detected for monitored, you could get poor results")
+    min_max_ref = _dynamic_range(reference_image)
+    if min_max_ref[1] - min_max_ref[0] <= 10:
+        logger.warning("Low dynamic range detected for reference, you could get poor results")
+    return min_max_mon, min_max_ref
