@@ -526,6 +526,34 @@ int km_clahe(km_ctx *ctx, const uint8_t *img, int H, int W, ptrdiff_t stride, do
 int km_clahe_dev(km_ctx *ctx, const uint8_t *d_img, int H, int W, ptrdiff_t stride, double clip_limit, int tiles_x, int tiles_y,
                  uint8_t *d_out, ptrdiff_t out_stride);
 
+/* ---- Descriptor matching of the global align step (api_match.hip, k_match.hip) --------------------------------------------------------
+ * The arithmetic is restated in tests/match_restatement.py (the definition the kernels are tested against, bit for bit).
+ * Descriptors are rows of `dim` = 128 integers 0 .. 255 (what OpenCV's SIFT stores); anything else than 128 is KM_E_UNSUPPORTED.
+ * The squared distance d2 of two rows is an exact integer (int8 MFMA contraction), the distance the float32 nearest to sqrt(d2).
+ *
+ * cv2.BFMatcher(NORM_L2).knnMatch(query, train, k) of karios/matcher/global_align.py:178-179, 193 for k = 1 or 2 (anything else
+ * KM_E_ARG): the train rows of every query row ranked ascending by (float32 distance, train index) - among equal float32 distances
+ * the lower index comes first, even where its d2 is the larger one.  idx: int32 [n_q, k], dist: float32 [n_q, k]; columns beyond
+ * n_t hold -1 / +inf.  Strides in elements.  n_q == 0: nothing to do.  n_t == 0: status 0, nothing is launched; the host form fills
+ * -1 / +inf, the device form leaves its outputs alone. */
+int km_knn_match_u8(km_ctx *ctx, const uint8_t *query, int n_q, ptrdiff_t stride_q, const uint8_t *train, int n_t, ptrdiff_t stride_t,
+                    int dim, int k, int *idx, float *dist);
+int km_knn_match_u8_dev(km_ctx *ctx, const uint8_t *d_query, int n_q, ptrdiff_t stride_q, const uint8_t *d_train, int n_t,
+                        ptrdiff_t stride_t, int dim, int k, int *d_idx, float *d_dist);
+/* karios/matcher/global_align.py:178-202 in one call: the two nearest ref rows of every mon row, Lowe's test
+ * (double)dist1 < ratio * (double)dist2 (one float64 product; false without a second neighbour), the nearest mon row of every ref
+ * row, and the mutual check.  Rows that pass, in ascending mon index: query_idx (mon row), train_idx (ref row), distance; room for
+ * `cap` rows each (n_mon always suffices).  counts[3] = {raw = n_mon, rows passing Lowe, mutual rows}, host memory in both forms.
+ * dtype KM_U8, or KM_F32 with every element an integer 0 .. 255 as cv2 hands descriptors out: any other value (NaN and infinities
+ * included) is KM_E_ARG, the message naming the first such (row, column) - nothing is rounded.  More mutual rows than cap: KM_E_ARG
+ * after counts was written.  n_mon == 0 or n_ref == 0: status 0, no matches, nothing launched.  No host synchronisation between the
+ * stages; the device form's only copy is the counters. */
+int km_match_lowe_mutual(km_ctx *ctx, const void *mon, int n_mon, ptrdiff_t stride_mon, const void *ref, int n_ref, ptrdiff_t stride_ref,
+                         int dtype, int dim, double ratio, int cap, int *query_idx, int *train_idx, float *distance, int *counts);
+int km_match_lowe_mutual_dev(km_ctx *ctx, const void *d_mon, int n_mon, ptrdiff_t stride_mon, const void *d_ref, int n_ref,
+                             ptrdiff_t stride_ref, int dtype, int dim, double ratio, int cap, int *d_query_idx, int *d_train_idx,
+                             float *d_distance, int *counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,10 @@ SIGNATURES = {
     "km_stretch_percentile_u8_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _d, _d, _vp, _sz]),
     "km_clahe": (_i, [_vp, _vp, _i, _i, _sz, _d, _i, _i, _vp]),
     "km_clahe_dev": (_i, [_vp, _vp, _i, _i, _sz, _d, _i, _i, _vp, _sz]),
+    "km_knn_match_u8": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _vp, _vp]),
+    "km_knn_match_u8_dev": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _vp, _vp]),
+    "km_match_lowe_mutual": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _d, _i, _vp, _vp, _vp, _pi]),
+    "km_match_lowe_mutual_dev": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _d, _i, _vp, _vp, _vp, _pi]),
 }
 
 _lib = None

@@ -145,6 +145,19 @@ __attribute__((weak)) int km_clahe(km_ctx *c, const uint8_t *, int, int, ptrdiff
 __attribute__((weak)) int km_clahe_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, double, int, int, uint8_t *, ptrdiff_t)
 { KM_PREP_ABSENT("clahe"); }
 #undef KM_PREP_ABSENT
+// ... and of the align step's descriptor matching (api_match.hip)
+#define KM_MATCH_ABSENT(name) return km_fail(c, KM_E_UNSUPPORTED, name ": built without api_match.hip")
+__attribute__((weak)) int km_knn_match_u8(km_ctx *c, const uint8_t *, int, ptrdiff_t, const uint8_t *, int, ptrdiff_t, int, int, int *, float *)
+{ KM_MATCH_ABSENT("knn_match_u8"); }
+__attribute__((weak)) int km_knn_match_u8_dev(km_ctx *c, const uint8_t *, int, ptrdiff_t, const uint8_t *, int, ptrdiff_t, int, int, int *, float *)
+{ KM_MATCH_ABSENT("knn_match_u8"); }
+__attribute__((weak)) int km_match_lowe_mutual(km_ctx *c, const void *, int, ptrdiff_t, const void *, int, ptrdiff_t, int, int, double, int, int *, int *,
+                                               float *, int *)
+{ KM_MATCH_ABSENT("match_lowe_mutual"); }
+__attribute__((weak)) int km_match_lowe_mutual_dev(km_ctx *c, const void *, int, ptrdiff_t, const void *, int, ptrdiff_t, int, int, double, int, int *,
+                                                   int *, float *, int *)
+{ KM_MATCH_ABSENT("match_lowe_mutual"); }
+#undef KM_MATCH_ABSENT
 
 const char *km_last_error(km_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 

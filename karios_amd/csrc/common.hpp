@@ -112,6 +112,15 @@ enum km_slot {
     WS_PR_STATE,    // api_prep.hip: histograms, tracked prefixes and results of the radix select (kp_state)
     WS_PR_CLAHE,    //   CLAHE's per-tile histograms and LUTs
     WS_PR_OUT,      //   uint8 destination of the host-API stretch / CLAHE forms
+    WS_MT_PQ,       // api_match.hip: packed int8 rows + norms of the query / mon descriptors (k_match.hpp kmt_packed)
+    WS_MT_PT,       //   ... of the train / ref descriptors
+    WS_MT_PART,     //   partial k-bests per (row, chunk of the other set) as 64-bit keys
+    WS_MT_FWD,      //   knn(mon, ref, 2): indices, then distances
+    WS_MT_BWD,      //   knn(ref, mon, 1)
+    WS_MT_FLAG,     //   mutual flags and their exclusive scan
+    WS_MT_SCAN,     //   tile sums of that scan
+    WS_MT_STATE,    //   counters of the call (kmt_state)
+    WS_MT_OUT,      //   results of the host-API forms
     WS_COUNT
 };
 

@@ -1,7 +1,8 @@
 """Global align step -- mirror of `karios.matcher.global_align` (reference global_align.py) on the GPU.
 
-`_to_uint8` and `_preprocess` (percentile stretch + CLAHE, the dense front half) run on the GPU; SIFT, BFMatcher and
-`cv2.findHomography` are sparse and stay with the caller on cv2; this module takes over again from the RANSAC matrix on: the ECC
+`_to_uint8` and `_preprocess` (percentile stretch + CLAHE, the dense front half) run on the GPU; SIFT stays with the caller on cv2;
+the descriptor matching behind it (both BFMatcher.knnMatch calls, Lowe's test, the mutual check: `match_descriptors`) runs on the GPU;
+`cv2.findHomography` stays on cv2; this module takes over again from the RANSAC matrix on: the ECC
 refinement of every candidate (`refine_global_alignment`, the candidate loop of `detect_global_alignment`) and the renders of
 `apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).
 Every GPU call goes through `karios_amd.ops`.  The reference's arithmetic is kept as it is, casts included; INTEGRATION.md
@@ -22,6 +23,8 @@ logger = logging.getLogger(__name__)
 ECC_MAX_ITERS = 200
 ECC_EPS = 1e-6
 ECC_MIN_VALID = 1000   # _refine_with_ecc: "need >1000" (it skips below 1000)
+LOWE_RATIO = 0.75      # global_align.py:51
+MIN_MATCHES = 4        # global_align.py:53: cv2.findHomography needs at least 4 point pairs
 
 
 @dataclass
@@ -51,6 +54,39 @@ def _preprocess(arr: np.ndarray) -> np.ndarray:
     """uint8 stretch + CLAHE(clipLimit=2.0, tileGridSize=(8, 8)) to equalize radiometry across the two images
     (global_align.py:104-108); the raster is uploaded once."""
     return ops.preprocess(arr, (2.0, 98.0), 2.0, (8, 8))
+
+
+def _points(kp) -> np.ndarray:
+    """Key points as a float32 [n, 2] array: an array of coordinates, or a sequence of objects with `.pt` (cv2.KeyPoint)."""
+    if isinstance(kp, np.ndarray):
+        pts = kp
+    else:
+        pts = np.array([k.pt for k in kp], dtype=np.float32).reshape(-1, 2)
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"key points: expected an [n, 2] array or objects with .pt, got shape {pts.shape}")
+    return pts.astype(np.float32)
+
+
+def match_descriptors(kp_mon, desc_mon, kp_ref, desc_ref):
+    """The matching of detect_global_alignment between SIFT and RANSAC (global_align.py:168-210) on the GPU: the checks on the
+    descriptors, knnMatch(mon, ref, 2) + Lowe's ratio test + knnMatch(ref, mon, 1) + mutual check in one call, the log line, and the
+    point arrays -> (src_pts, dst_pts), float32 [n_good, 2] in the reference's order, ready for cv2.findHomography.
+    kp_*: [n, 2] arrays of (x, y) or sequences of objects with `.pt`; desc_*: uint8 or float32 [n, 128]."""
+    if desc_mon is None or desc_ref is None:
+        raise RuntimeError("SIFT found no descriptors in one or both images")
+    if len(kp_mon) < MIN_MATCHES or len(kp_ref) < MIN_MATCHES:
+        raise RuntimeError(
+            f"Too few SIFT keypoints: mon={len(kp_mon)} ref={len(kp_ref)} "
+            f"(need ≥{MIN_MATCHES})"
+        )
+    logger.info("Keypoints detected: mon=%d  ref=%d", len(kp_mon), len(kp_ref))
+    query_idx, train_idx, _dist, (raw, lowe, mutual) = ops.match_lowe_mutual(desc_mon, desc_ref, LOWE_RATIO)
+    logger.info("Matches: raw=%d  Lowe<%.2f=%d  mutual=%d", raw, LOWE_RATIO, lowe, mutual)
+    if mutual < MIN_MATCHES:
+        raise RuntimeError(
+            f"Too few good matches after Lowe + cross-check: {mutual} (need ≥{MIN_MATCHES})"
+        )
+    return _points(kp_mon)[query_idx], _points(kp_ref)[train_idx]
 
 
 def _prior_from_georefs(monitored, reference) -> Optional[np.ndarray]:

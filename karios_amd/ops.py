@@ -548,3 +548,65 @@ def clahe(img, clip_limit: float = 2.0, tile_grid=(8, 8), ctx: Context | None = 
 def preprocess(arr, q=(2.0, 98.0), clip_limit: float = 2.0, tile_grid=(8, 8), ctx: Context | None = None):
     """_preprocess (global_align.py:104-108): _to_uint8, then CLAHE; the raster is uploaded once and stays on the device in between."""
     return _preprocess_resident(arr, q, (clip_limit, tile_grid), ctx)
+
+
+# ---- descriptor matching of the align step (csrc/api_match.hip) -------------------------------------------------------------------
+DESCRIPTOR_DIM = 128
+
+
+def _as_descriptors(arr, what):
+    """uint8 or float32 [n, 128] with contiguous rows, as sift.detectAndCompute returns them; ValueError for anything else."""
+    a = np.asarray(arr)
+    if a.ndim != 2 or a.shape[1] != DESCRIPTOR_DIM:
+        raise ValueError(f"{what}: expected descriptors of shape [n, {DESCRIPTOR_DIM}], got {a.shape}")
+    if a.dtype != np.uint8 and a.dtype != np.float32:
+        raise ValueError(f"{what}: expected uint8 or float32 descriptors, got {a.dtype}")
+    if a.strides[1] != a.itemsize or a.strides[0] % a.itemsize or (a.shape[0] > 1 and a.strides[0] < DESCRIPTOR_DIM * a.itemsize):
+        raise ValueError(f"{what}: rows must be contiguous")
+    return a
+
+
+def _u8_descriptors(a, what):
+    """float32 descriptors as uint8; ValueError (naming the element) when one is not an integer in 0 .. 255."""
+    if a.dtype == np.uint8:
+        return a
+    with np.errstate(invalid="ignore"):
+        bad = ~((a >= 0) & (a <= 255) & (a == np.trunc(a)))
+    if bad.any():
+        r, col = np.argwhere(bad)[0]
+        raise ValueError(f"{what}: element (row {r}, column {col}) = {a[r, col]!r} is not an integer in 0 .. 255")
+    return a.astype(np.uint8)
+
+
+def knn_match(query, train, k: int = 2, ctx: Context | None = None):
+    """cv2.BFMatcher(NORM_L2).knnMatch(query, train, k) (global_align.py:178-179, 193) for k = 1 or 2 -> (idx int32 [n, k],
+    dist float32 [n, k]): the train rows ranked by (float32 distance, train index); columns beyond len(train) hold -1 / +inf."""
+    q, t = _as_descriptors(query, "knn_match query"), _as_descriptors(train, "knn_match train")
+    if k not in (1, 2):
+        raise ValueError(f"knn_match: k = {k} (1 or 2)")
+    q, t = _u8_descriptors(q, "knn_match query"), _u8_descriptors(t, "knn_match train")
+    idx = np.full((q.shape[0], k), -1, np.int32)
+    dist = np.full((q.shape[0], k), np.inf, np.float32)
+    if q.shape[0] and t.shape[0]:
+        c = _ctx(ctx)
+        c.check(c.lib.km_knn_match_u8(c.handle, ptr(q), q.shape[0], row_stride(q), ptr(t), t.shape[0], row_stride(t), DESCRIPTOR_DIM, int(k),
+                                      ptr(idx), ptr(dist)), "km_knn_match_u8")
+    return idx, dist
+
+
+def match_lowe_mutual(desc_mon, desc_ref, ratio: float = 0.75, ctx: Context | None = None):
+    """knnMatch(mon, ref, 2), Lowe's ratio test, knnMatch(ref, mon, 1) and the mutual check (global_align.py:178-202) in one call
+    -> (query_idx int32, train_idx int32, distance float32, (raw, lowe, mutual)): the mutual rows in ascending mon index.  float32
+    descriptors must hold integers 0 .. 255 (KariosHipError with code E_ARG otherwise)."""
+    m, r = _as_descriptors(desc_mon, "match_lowe_mutual mon"), _as_descriptors(desc_ref, "match_lowe_mutual ref")
+    if m.dtype != r.dtype:
+        raise ValueError(f"match_lowe_mutual: descriptor dtypes differ ({m.dtype}, {r.dtype})")
+    n = m.shape[0]
+    qi, ti, dist = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+    counts = (C.c_int * 3)(n, 0, 0)
+    if n and r.shape[0]:
+        c = _ctx(ctx)
+        c.check(c.lib.km_match_lowe_mutual(c.handle, ptr(m), n, row_stride(m), ptr(r), r.shape[0], row_stride(r), dtype_code(m), DESCRIPTOR_DIM,
+                                           float(ratio), n, ptr(qi), ptr(ti), ptr(dist), counts), "km_match_lowe_mutual")
+    k = counts[2]
+    return qi[:k], ti[:k], dist[:k], (counts[0], counts[1], counts[2])

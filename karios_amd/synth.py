@@ -113,6 +113,31 @@ def make_cross_sensor_pair(H: int, W: int, sx: float = 0.4, sy: float = -0.3, se
     return mon, ref, mask
 
 
+def _sift_like(n: int, rng) -> np.ndarray:
+    """Rows shaped like OpenCV's SIFT descriptors: non-negative, unit norm, clipped at 0.2, renormalised, * 512, rounded, saturated."""
+    g = rng.gamma(0.6, 1.0, (n, 128))
+    g /= np.linalg.norm(g, axis=1, keepdims=True)
+    g = np.minimum(g, 0.2)
+    g /= np.linalg.norm(g, axis=1, keepdims=True)
+    return np.clip(np.rint(g * 512), 0, 255).astype(np.uint8)
+
+
+def descriptor_scene(n_mon: int, n_ref: int, n_common: int, n_rival: int, sigma: float, seed: int):
+    """Two sets of SIFT-like uint8 descriptors [n, 128] for the matching of the align step (global_align.py:178-202): `n_common`
+    planted pairs (ref row = mon row + N(0, sigma) noise, re-saturated), `n_rival` extra mon rows that sit closer (sigma / 3) to a
+    planted ref row than its partner does - the partner passes Lowe's test and fails the mutual check -, the rest unrelated; both
+    sets shuffled.  -> (mon, ref)"""
+    if not (0 <= n_rival <= n_common and n_common + n_rival <= n_mon and n_common <= n_ref):
+        raise ValueError("descriptor_scene: need n_rival <= n_common, n_common + n_rival <= n_mon, n_common <= n_ref")
+    rng = np.random.default_rng(seed)
+    base = _sift_like(n_common, rng)
+    noisy = np.clip(np.rint(base + rng.normal(0, sigma, base.shape)), 0, 255).astype(np.uint8)
+    rival = np.clip(np.rint(noisy[:n_rival] + rng.normal(0, sigma / 3, (n_rival, 128))), 0, 255).astype(np.uint8)
+    mon = np.concatenate([base, rival, _sift_like(n_mon - n_common - n_rival, rng)])
+    ref = np.concatenate([noisy, _sift_like(n_ref - n_common, rng)])
+    return mon[rng.permutation(n_mon)], ref[rng.permutation(n_ref)]
+
+
 def _base_torch(H: int, W: int, seed: int, device):
     """Device version of `make_base`: float32 texture field of shape (H + 2 PAD, W + 2 PAD)."""
     import torch
