@@ -135,6 +135,9 @@ int km_set_profiling(km_ctx *ctx, int enable);
  *   "f64_plain"    1: the double-precision transform packs the images in a pass of its own and finds the arg-max in two passes behind
  *                  the last level - the form that serves sides with a Bluestein dimension - on every shape (default 0: both ends ride in
  *                  the level kernels where the shape allows)
+ *   "ransac_first_batch" iterations of the first batch of km_find_homography_ransac* (batches end at B0, 2 B0, 4 B0, ... iterations);
+ *                  0 (default): chosen from the number of pairs and the chip (csrc/api_ransac.hip).  Only the number of iterations
+ *                  evaluated beyond the sequential loop's end depends on it
  *  test knobs that shrink internal capacities so that the corner detector's retry paths run on every call (0 = default)
  *   "key_cap"      candidate keys per shard of the first attempt          -> key-buffer overflow + regrow
  *   "stage_cap"    usable slots of the fused kernel's per-wave key stage  -> stage overflow + two-kernel repeat
@@ -553,6 +556,29 @@ int km_match_lowe_mutual(km_ctx *ctx, const void *mon, int n_mon, ptrdiff_t stri
 int km_match_lowe_mutual_dev(km_ctx *ctx, const void *d_mon, int n_mon, ptrdiff_t stride_mon, const void *d_ref, int n_ref,
                              ptrdiff_t stride_ref, int dtype, int dim, double ratio, int cap, int *d_query_idx, int *d_train_idx,
                              float *d_distance, int *counts);
+
+/* ---- RANSAC homography of the global align step (api_ransac.hip, k_ransac.hip, ransac_math.hpp) ----------------------------------------
+ * cv2.findHomography(src_pts, dst_pts, cv2.RANSAC, threshold, maxIters=max_iters, confidence=confidence) of
+ * karios/matcher/global_align.py:223-230, as OpenCV 4.8 defines it: restated in tests/ransac_restatement.py (the definition the
+ * library is held to, bit for bit; parity with cv2 itself is unpinned).  src / dst: n points (x, y) as float32 with a row stride in
+ * elements (>= 2).  H: 9 float64 (row-major 3 x 3), mask: n bytes (1 = inlier), *found: 1 when a model was found.  Not found is no
+ * error: status 0, *found = 0, H and mask zero.  n == 4: the direct solve with a mask of ones; n > 4: the RANSAC loop (random stream
+ * RNG(-1), 4-point models, inliers err <= (float)(threshold^2); threshold <= 0 means 3), then the solve on all inliers and at most
+ * 10 Levenberg-Marquardt iterations, both sequential float64 on the host.  The models and inlier counts of a batch of iterations
+ * are evaluated on the device at once and the loop's bookkeeping replayed over them in iteration order: the outcome is the
+ * sequential loop's (see csrc/api_ransac.hip for the batch schedule and the option "ransac_first_batch").
+ * KM_E_ARG: n < 4, confidence outside (0, 1), max_iters above 2^24, a coordinate that is NaN or infinite (the message names the
+ * first).  stats (8 words, may be NULL): [0] iterations the sequential loop ran, [1] iterations evaluated, [2] index of the winning
+ * iteration (-1: none), [3] its inlier count, [4] Levenberg-Marquardt iterations, [5] size of the first batch, [6] batches, [7] 0.
+ * iter_counts / iter_valid (each max(max_iters, 1) ints, may be NULL; for tests): inlier count and "the 4-point solve gave a
+ * model" flag of every evaluated iteration.  Host form: everything in host memory.  Device form: src, dst and mask on the device;
+ * H, found, stats and iter_* on the host; the pairs travel back once (16 bytes each) for the sequential parts. */
+int km_find_homography_ransac(km_ctx *ctx, const float *src, ptrdiff_t stride_src, const float *dst, ptrdiff_t stride_dst, int n,
+                              double threshold, int max_iters, double confidence, double H[9], uint8_t *mask, int *found, int64_t *stats,
+                              int *iter_counts, int *iter_valid);
+int km_find_homography_ransac_dev(km_ctx *ctx, const float *d_src, ptrdiff_t stride_src, const float *d_dst, ptrdiff_t stride_dst, int n,
+                                  double threshold, int max_iters, double confidence, double H[9], uint8_t *d_mask, int *found,
+                                  int64_t *stats, int *iter_counts, int *iter_valid);
 
 #ifdef __cplusplus
 }

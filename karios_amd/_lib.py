@@ -155,6 +155,8 @@ SIGNATURES = {
     "km_knn_match_u8_dev": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _vp, _vp]),
     "km_match_lowe_mutual": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _d, _i, _vp, _vp, _vp, _pi]),
     "km_match_lowe_mutual_dev": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _d, _i, _vp, _vp, _vp, _pi]),
+    "km_find_homography_ransac": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _d, _i, _d, _pd, _vp, _pi, C.POINTER(C.c_int64), _vp, _vp]),
+    "km_find_homography_ransac_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _d, _i, _d, _pd, _vp, _pi, C.POINTER(C.c_int64), _vp, _vp]),
 }
 
 _lib = None

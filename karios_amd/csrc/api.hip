@@ -158,6 +158,15 @@ __attribute__((weak)) int km_match_lowe_mutual_dev(km_ctx *c, const void *, int,
                                                    int *, float *, int *)
 { KM_MATCH_ABSENT("match_lowe_mutual"); }
 #undef KM_MATCH_ABSENT
+// ... and of its RANSAC homography (api_ransac.hip)
+#define KM_RANSAC_ABSENT return km_fail(c, KM_E_UNSUPPORTED, "find_homography_ransac: built without api_ransac.hip")
+__attribute__((weak)) int km_find_homography_ransac(km_ctx *c, const float *, ptrdiff_t, const float *, ptrdiff_t, int, double, int, double, double *,
+                                                    uint8_t *, int *, int64_t *, int *, int *)
+{ KM_RANSAC_ABSENT; }
+__attribute__((weak)) int km_find_homography_ransac_dev(km_ctx *c, const float *, ptrdiff_t, const float *, ptrdiff_t, int, double, int, double,
+                                                        double *, uint8_t *, int *, int64_t *, int *, int *)
+{ KM_RANSAC_ABSENT; }
+#undef KM_RANSAC_ABSENT
 
 const char *km_last_error(km_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 
@@ -282,6 +291,7 @@ int km_set_option(km_ctx *c, const char *name, int value)
     if (strcmp(name, "select_first") == 0) { c->opt_select_first = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "stash_cap") == 0) { c->opt_stash_cap = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "spec_flag") == 0) { c->opt_spec_flag = value < 0 ? 0 : value; return KM_OK; }
+    if (strcmp(name, "ransac_first_batch") == 0) { c->opt_ransac_first_batch = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "defer") == 0) { c->opt_no_defer = value == 0; return KM_OK; }
     if (strcmp(name, "phase_fp64") == 0) { c->opt_phase_fp64 = value != 0; return KM_OK; }
     if (strcmp(name, "fft61") == 0) { c->opt_fft61 = value != 0; return KM_OK; }

@@ -121,6 +121,12 @@ enum km_slot {
     WS_MT_SCAN,     //   tile sums of that scan
     WS_MT_STATE,    //   counters of the call (kmt_state)
     WS_MT_OUT,      //   results of the host-API forms
+    WS_RS_PAIRS,    // api_ransac.hip: the point pairs as (x, y, mx, my) float4
+    WS_RS_IDX,      //   the four pair indices of every iteration's subset
+    WS_RS_H64,      //   the float64 model of every iteration
+    WS_RS_HF,       //   ... and its float32 cast, the scoring table (KRS_HSTRIDE floats per iteration)
+    WS_RS_COUNT,    //   inlier count and valid flag per iteration, then the winner's total
+    WS_RS_MASK,     //   inlier mask of the host-API form
     WS_COUNT
 };
 
@@ -280,6 +286,7 @@ struct km_ctx {
     bool opt_lk2 = true;           // "lk2" 1 (default): LK on four resident patches per key point (two-level pyramids); 0: the first form
     bool opt_mm_early = true;      // "mm_early" 0: min / max of a submitted unit on the main stream behind the previous unit's tail (round-2 order)
     bool opt_frame_mi = false;     // "frame_mi" 1: frames scored by the tile entry points (ZNCC of the rows with score >= threshold) also carry the two mutual-information scores of those rows (core.py:894-907): two more float64 columns behind zncc
+    int opt_ransac_first_batch = 0;   // "ransac_first_batch": iterations of the first batch of km_find_homography_ransac* (0: chosen from n and the chip)
     bool opt_no_defer = false; // "defer" 0: the deferred pyramid jobs run after the read-back waits instead of under them
     // stage-timer events: set 0 serves the synchronous calls, sets 1..KM_FRAME_SLOTS the frames in flight of
     // km_klt_tile_frame_submit (a frame's spans are read after ITS completion, while the next one is already recording)

@@ -2,9 +2,9 @@
 
 `_to_uint8` and `_preprocess` (percentile stretch + CLAHE, the dense front half) run on the GPU; SIFT stays with the caller on cv2;
 the descriptor matching behind it (both BFMatcher.knnMatch calls, Lowe's test, the mutual check: `match_descriptors`) runs on the GPU;
-`cv2.findHomography` stays on cv2; this module takes over again from the RANSAC matrix on: the ECC
-refinement of every candidate (`refine_global_alignment`, the candidate loop of `detect_global_alignment`) and the renders of
-`apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).
+so do `cv2.findHomography` with RANSAC (`estimate_homography`), the ECC refinement of every candidate (`refine_global_alignment`) and
+the renders of `apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).  `detect_global_alignment` chains
+them as the reference does; SIFT is the one part it takes from outside (its `sift` argument, cv2's by default).
 Every GPU call goes through `karios_amd.ops`.  The reference's arithmetic is kept as it is, casts included; INTEGRATION.md
 section 6 notes the direction in which it composes the ECC residual.
 """
@@ -25,6 +25,12 @@ ECC_EPS = 1e-6
 ECC_MIN_VALID = 1000   # _refine_with_ecc: "need >1000" (it skips below 1000)
 LOWE_RATIO = 0.75      # global_align.py:51
 MIN_MATCHES = 4        # global_align.py:53: cv2.findHomography needs at least 4 point pairs
+RANSAC_THRESHOLD_PX = 3.0   # global_align.py:52
+RANSAC_MAX_ITERS = 10000    # global_align.py:228
+RANSAC_CONFIDENCE = 0.999   # global_align.py:229
+SIFT_NFEATURES = 0          # global_align.py:48-50: cv2.SIFT_create(nfeatures=, contrastThreshold=, edgeThreshold=); 0 = unlimited
+SIFT_CONTRAST_THRESHOLD = 0.02
+SIFT_EDGE_THRESHOLD = 10
 
 
 @dataclass
@@ -87,6 +93,54 @@ def match_descriptors(kp_mon, desc_mon, kp_ref, desc_ref):
             f"Too few good matches after Lowe + cross-check: {mutual} (need ≥{MIN_MATCHES})"
         )
     return _points(kp_mon)[query_idx], _points(kp_ref)[train_idx]
+
+
+def estimate_homography(src_pts, dst_pts):
+    """cv2.findHomography(src_pts, dst_pts, cv2.RANSAC, RANSAC_THRESHOLD_PX, maxIters=10000, confidence=0.999) and what the reference
+    does with its result (global_align.py:223-231) on the GPU -> (3x3 float64 matrix, n_inliers)."""
+    matrix, inlier_mask = ops.find_homography(src_pts, dst_pts, RANSAC_THRESHOLD_PX, RANSAC_MAX_ITERS, RANSAC_CONFIDENCE)
+    if matrix is None:
+        raise RuntimeError("RANSAC failed to estimate a homography")
+    n_inliers = int(inlier_mask.sum())
+    logger.info("RANSAC initial fit: %s  inliers=%d/%d (%.1f%%)", _decompose(matrix), n_inliers, len(src_pts),
+                100.0 * n_inliers / len(src_pts))
+    return matrix, n_inliers
+
+
+def _default_sift():
+    try:
+        import cv2
+    except ImportError as exc:
+        raise ImportError(
+            "detect_global_alignment: SIFT is the one part of the align step karios_amd does not provide; "
+            "install OpenCV (cv2) or pass sift=<object with detectAndCompute(image, None)>") from exc
+    return cv2.SIFT_create(nfeatures=SIFT_NFEATURES, contrastThreshold=SIFT_CONTRAST_THRESHOLD, edgeThreshold=SIFT_EDGE_THRESHOLD)
+
+
+def detect_global_alignment(mon_arr, ref_arr, prior=None, sift=None) -> GlobalAlignment:
+    """detect_global_alignment of the reference (global_align.py:143-270): preprocess both images, SIFT (`sift.detectAndCompute`,
+    cv2's SIFT when `sift` is None), descriptor matching, the prior's log line, RANSAC, ECC refinement of the candidates."""
+    if sift is None:
+        sift = _default_sift()
+    mon_u8 = _preprocess(mon_arr)
+    ref_u8 = _preprocess(ref_arr)
+    mh, mw = mon_u8.shape
+    rh, rw = ref_u8.shape
+    logger.info("SIFT feature matching: mon=%dx%d  ref=%dx%d  contrast=%.3f  Lowe=%.2f  RANSAC=%.1fpx",
+                mw, mh, rw, rh, SIFT_CONTRAST_THRESHOLD, LOWE_RATIO, RANSAC_THRESHOLD_PX)
+    kp_mon, desc_mon = sift.detectAndCompute(mon_u8, None)
+    kp_ref, desc_ref = sift.detectAndCompute(ref_u8, None)
+    src_pts, dst_pts = match_descriptors(kp_mon, desc_mon, kp_ref, desc_ref)
+    n_matches = len(src_pts)
+    if prior is not None:
+        # global_align.py:212-221, informational: the matches against the prior's upper-left 2 x 3 (translation + scale)
+        prior = np.asarray(prior)
+        predicted = (prior[:2, :2] @ src_pts.T).T + prior[:2, 2]
+        errors = np.linalg.norm(dst_pts - predicted, axis=1)
+        logger.info("Match error vs geotransform prior: median=%.1fpx  min=%.1fpx  max=%.1fpx",
+                    float(np.median(errors)), float(errors.min()), float(errors.max()))
+    matrix, n_inliers = estimate_homography(src_pts, dst_pts)
+    return refine_global_alignment(mon_u8, ref_u8, matrix, n_inliers, n_matches, prior=prior)
 
 
 def _prior_from_georefs(monitored, reference) -> Optional[np.ndarray]:

@@ -610,3 +610,68 @@ def match_lowe_mutual(desc_mon, desc_ref, ratio: float = 0.75, ctx: Context | No
                                            float(ratio), n, ptr(qi), ptr(ti), ptr(dist), counts), "km_match_lowe_mutual")
     k = counts[2]
     return qi[:k], ti[:k], dist[:k], (counts[0], counts[1], counts[2])
+
+
+# ---- RANSAC homography of the align step (csrc/api_ransac.hip) --------------------------------------------------------------------
+RANSAC_STATS = ("ran", "evaluated", "best_iter", "best_count", "lm_iters", "first_batch", "batches")
+
+
+def _as_points(arr, what):
+    """float32 [n, 2] whose rows hold x, y next to each other (a row stride is fine); cv2's [n, 1, 2] is accepted."""
+    a = np.asarray(arr)
+    if a.ndim == 3 and a.shape[1] == 1:
+        a = a[:, 0, :]
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"{what}: expected points of shape [n, 2], got {a.shape}")
+    if a.dtype != np.float32:
+        a = a.astype(np.float32)
+    if a.strides[1] != 4 or a.strides[0] % 4 or (a.shape[0] > 1 and a.strides[0] < 8):
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def find_homography(src_pts, dst_pts, ransac_reproj_threshold: float = 3.0, max_iters: int = 10000, confidence: float = 0.999,
+                    ctx: Context | None = None, return_stats: bool = False, return_iterations: bool = False):
+    """cv2.findHomography(src_pts, dst_pts, cv2.RANSAC, ransac_reproj_threshold, maxIters=max_iters, confidence=confidence)
+    (global_align.py:223-230) -> (matrix float64 [3, 3] or None, mask uint8 [n, 1]), cv2's return shape.  Points: float32 [n, 2]
+    numpy arrays, or torch tensors on the context's device (the device form; the mask still comes back as a numpy array).
+    return_stats adds a dict of RANSAC_STATS; return_iterations adds (inlier counts, valid flags) of every evaluated iteration."""
+    c = _ctx(ctx)
+    on_device = hasattr(src_pts, "data_ptr")
+    if on_device:
+        import torch
+        s, d = src_pts, dst_pts
+        if s.dtype != torch.float32 or d.dtype != torch.float32 or s.dim() != 2 or d.dim() != 2 or s.shape[1] != 2 or d.shape[1] != 2:
+            raise ValueError("find_homography: device points must be float32 tensors of shape [n, 2]")
+        if s.stride(1) != 1 or d.stride(1) != 1:
+            raise ValueError("find_homography: x and y of a device point must be adjacent")
+        n, ss, sd = s.shape[0], (s.stride(0) if s.shape[0] > 1 else 2), (d.stride(0) if d.shape[0] > 1 else 2)
+        d_mask = torch.zeros(max(n, 1), dtype=torch.uint8, device=s.device)
+        args = (C.c_void_p(s.data_ptr()), ss, C.c_void_p(d.data_ptr()), sd)
+        mask_arg, fn, what = C.c_void_p(d_mask.data_ptr()), c.lib.km_find_homography_ransac_dev, "km_find_homography_ransac_dev"
+        torch.cuda.synchronize(s.device)
+    else:
+        s, d = _as_points(src_pts, "find_homography src_pts"), _as_points(dst_pts, "find_homography dst_pts")
+        n, ss, sd = s.shape[0], (s.strides[0] // 4 if s.shape[0] > 1 else 2), (d.strides[0] // 4 if d.shape[0] > 1 else 2)
+        args = (ptr(s), ss, ptr(d), sd)
+        mask = np.zeros((n, 1), np.uint8)
+        mask_arg, fn, what = ptr(mask), c.lib.km_find_homography_ransac, "km_find_homography_ransac"
+    if d.shape[0] != n:
+        raise ValueError(f"find_homography: {n} source points, {d.shape[0]} destination points")
+    H = np.zeros(9, np.float64)
+    found = C.c_int(0)
+    stats = (C.c_int64 * 8)()
+    room = max(int(max_iters), 1)
+    it_counts = np.zeros(room if return_iterations else 0, np.int32)
+    it_valid = np.zeros(room if return_iterations else 0, np.int32)
+    c.check(fn(c.handle, *args, n, float(ransac_reproj_threshold), int(max_iters), float(confidence), H.ctypes.data_as(C.POINTER(C.c_double)),
+               mask_arg, C.byref(found), stats, ptr(it_counts) if return_iterations else None, ptr(it_valid) if return_iterations else None), what)
+    if on_device:
+        mask = d_mask[:n].cpu().numpy().reshape(n, 1)
+    out = (H.reshape(3, 3) if found.value else None, mask)
+    if return_stats:
+        out += (dict(zip(RANSAC_STATS, (int(v) for v in stats))),)
+    if return_iterations:
+        k = int(stats[1])
+        out += ((it_counts[:k], it_valid[:k]),)
+    return out

@@ -138,6 +138,27 @@ def descriptor_scene(n_mon: int, n_ref: int, n_common: int, n_rival: int, sigma:
     return mon[rng.permutation(n_mon)], ref[rng.permutation(n_ref)]
 
 
+def homography_scene(n: int, inlier_share: float, sigma: float, seed: int, size: int = 10980):
+    """Point pairs for the RANSAC homography of the align step (global_align.py:223-230): `n` uniform float32 points in a
+    size x size image, a mild homography (a small rotation, scales near one, a shift of some tens of pixels, perspective terms
+    around 1e-6 / px), N(0, sigma) noise on the images of the round(n * inlier_share) inliers, uniform points for the outliers, one
+    permutation over all pairs.  -> (src float32 [n, 2], dst float32 [n, 2], planted bool [n], H float64 [3, 3])"""
+    rng = np.random.default_rng(seed)
+    n_in = int(round(n * inlier_share))
+    src = rng.uniform(0, size, (n, 2))
+    a = np.deg2rad(rng.uniform(-1.5, 1.5))
+    sx, sy = rng.uniform(0.98, 1.02, 2)
+    H = np.array([[sx * np.cos(a), -sy * np.sin(a), rng.uniform(-40, 40)],
+                  [sx * np.sin(a), sy * np.cos(a), rng.uniform(-40, 40)],
+                  [rng.uniform(-1e-6, 1e-6), rng.uniform(-1e-6, 1e-6), 1.0]])
+    p = np.concatenate([src, np.ones((n, 1))], 1) @ H.T
+    dst = p[:, :2] / p[:, 2:] + rng.normal(0, sigma, (n, 2)) if sigma > 0 else p[:, :2] / p[:, 2:]
+    dst[n_in:] = rng.uniform(0, size, (n - n_in, 2))
+    planted = np.arange(n) < n_in
+    order = rng.permutation(n)
+    return src[order].astype(np.float32), dst[order].astype(np.float32), planted[order], H
+
+
 def _base_torch(H: int, W: int, seed: int, device):
     """Device version of `make_base`: float32 texture field of shape (H + 2 PAD, W + 2 PAD)."""
     import torch
