@@ -45,7 +45,8 @@ enum {
     KM_E_UNSUPPORTED = -4,
     KM_E_NO_DEVICE = -5,
     KM_E_INTERNAL = -6,
-    KM_E_NO_CONVERGENCE = -7   /* km_find_transform_ecc*: NaN correlation or lambda_d <= 0 (cv2.error StsNoConv) */
+    KM_E_NO_CONVERGENCE = -7,  /* km_find_transform_ecc*: NaN correlation or lambda_d <= 0 (cv2.error StsNoConv) */
+    KM_E_CAPACITY = -8         /* km_sift_detect_and_compute*: more key points than the outputs have room for (the first `cap` are written) */
 };
 
 /* KLTConfiguration fields (core/configuration.py:36-50) + the fixed LK criteria of
@@ -579,6 +580,35 @@ int km_find_homography_ransac(km_ctx *ctx, const float *src, ptrdiff_t stride_sr
 int km_find_homography_ransac_dev(km_ctx *ctx, const float *d_src, ptrdiff_t stride_src, const float *d_dst, ptrdiff_t stride_dst, int n,
                                   double threshold, int max_iters, double confidence, double H[9], uint8_t *d_mask, int *found,
                                   int64_t *stats, int *iter_counts, int *iter_valid);
+
+/* ---- SIFT of the global align step (api_sift.hip, k_sift.hip, sift_math.hpp) -----------------------------------------------------------
+ * cv2.SIFT_create(nfeatures=0, nOctaveLayers=n_octave_layers, contrastThreshold=, edgeThreshold=, sigma=).detectAndCompute(img, None)
+ * of karios/matcher/global_align.py:48-50, 160-166, as OpenCV 4.8 defines it with the float pyramid: restated in
+ * tests/sift_restatement.py (the definition the library is held to, bit for bit; parity with cv2 itself is unpinned).  img: H x W
+ * uint8 with a row stride in elements, at most 32767 a side.  nfeatures: 0 only (KM_E_UNSUPPORTED otherwise); n_octave_layers 1 .. 8;
+ * a sigma whose widest Gaussian kernel exceeds 65 taps is KM_E_UNSUPPORTED.
+ * Outputs, each with room for `cap` key points: x, y, size, angle, response (float32) and octave (int32, cv2's packed field) as a
+ * struct of arrays, descriptors as [cap, 128] rows of desc_dtype (KM_U8 or KM_F32, the same integers 0 .. 255) with a row stride in
+ * elements (>= 128; the host form takes dense rows only).  *count is the true number of key points, always.  More key points than
+ * cap: the first cap entries of the final order are written and the call returns KM_E_CAPACITY - call again with cap >= *count.
+ * The order is cv2's: x, y ascending, size descending, angle ascending, response and octave descending; duplicates in (x, y, size,
+ * angle) are dropped.
+ * stats (160 words, may be NULL): [0] octaves, [1] key points before and [2] after the duplicates went, [3] peak workspace bytes of
+ * the call, then per octave o: [4 + 3 o] extrema candidates, [5 + 3 o] candidates that passed the refinement, [6 + 3 o] key points
+ * (one per orientation peak).  Times in microseconds: [52] the base image, [53] the final order on the host, [54] the gather,
+ * [55] the whole call (host clock), and per octave o device time of [56 + 5 o] blur + DoG + decimation, [57 + 5 o] extrema scan,
+ * [58 + 5 o] refinement, [59 + 5 o] orientations, [60 + 5 o] descriptors; [136] / [137] how often the candidate /
+ * key-point list of an octave was too small and its stage ran again with room.  Host form: everything in host memory.  Device form: img and the outputs on the device; count and
+ * stats on the host; the call returns with the outputs complete.  The key-point records travel to the host once (24 bytes each)
+ * for the final order. */
+int km_sift_detect_and_compute(km_ctx *ctx, const uint8_t *img, int H, int W, ptrdiff_t stride, int nfeatures, int n_octave_layers,
+                               double contrast_threshold, double edge_threshold, double sigma, int cap, float *x, float *y, float *size,
+                               float *angle, float *response, int *octave, void *desc, int desc_dtype, ptrdiff_t desc_stride, int *count,
+                               int64_t *stats);
+int km_sift_detect_and_compute_dev(km_ctx *ctx, const uint8_t *d_img, int H, int W, ptrdiff_t stride, int nfeatures, int n_octave_layers,
+                                   double contrast_threshold, double edge_threshold, double sigma, int cap, float *d_x, float *d_y,
+                                   float *d_size, float *d_angle, float *d_response, int *d_octave, void *d_desc, int desc_dtype,
+                                   ptrdiff_t desc_stride, int *count, int64_t *stats);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
 E_ARG = -1                     # KM_E_ARG
 E_UNSUPPORTED = -4             # KM_E_UNSUPPORTED
 E_NO_CONVERGENCE = -7          # KM_E_NO_CONVERGENCE
+E_CAPACITY = -8                # KM_E_CAPACITY
 ECC_CONVERGED, ECC_SKIPPED, ECC_NO_CONVERGENCE = 0, 1, 2   # KM_ECC_*
 
 _vp, _i, _d, _sz, _pd = C.c_void_p, C.c_int, C.c_double, C.c_ssize_t, C.POINTER(C.c_double)
@@ -157,6 +158,10 @@ SIGNATURES = {
     "km_match_lowe_mutual_dev": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, _d, _i, _vp, _vp, _vp, _pi]),
     "km_find_homography_ransac": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _d, _i, _d, _pd, _vp, _pi, C.POINTER(C.c_int64), _vp, _vp]),
     "km_find_homography_ransac_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _d, _i, _d, _pd, _vp, _pi, C.POINTER(C.c_int64), _vp, _vp]),
+    "km_sift_detect_and_compute": (_i, [_vp, _vp, _i, _i, _sz, _i, _i, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _pi,
+                                        C.POINTER(C.c_int64)]),
+    "km_sift_detect_and_compute_dev": (_i, [_vp, _vp, _i, _i, _sz, _i, _i, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _pi,
+                                            C.POINTER(C.c_int64)]),
 }
 
 _lib = None

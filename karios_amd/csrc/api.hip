@@ -167,6 +167,15 @@ __attribute__((weak)) int km_find_homography_ransac_dev(km_ctx *c, const float *
                                                         double *, uint8_t *, int *, int64_t *, int *, int *)
 { KM_RANSAC_ABSENT; }
 #undef KM_RANSAC_ABSENT
+// ... and of its SIFT (api_sift.hip)
+#define KM_SIFT_ABSENT return km_fail(c, KM_E_UNSUPPORTED, "sift_detect_and_compute: built without api_sift.hip")
+__attribute__((weak)) int km_sift_detect_and_compute(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, int, int, double, double, double, int, float *, float *,
+                                                     float *, float *, float *, int *, void *, int, ptrdiff_t, int *, int64_t *)
+{ KM_SIFT_ABSENT; }
+__attribute__((weak)) int km_sift_detect_and_compute_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, int, int, double, double, double, int, float *,
+                                                         float *, float *, float *, float *, int *, void *, int, ptrdiff_t, int *, int64_t *)
+{ KM_SIFT_ABSENT; }
+#undef KM_SIFT_ABSENT
 
 const char *km_last_error(km_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 

@@ -127,6 +127,16 @@ enum km_slot {
     WS_RS_HF,       //   ... and its float32 cast, the scoring table (KRS_HSTRIDE floats per iteration)
     WS_RS_COUNT,    //   inlier count and valid flag per iteration, then the winner's total
     WS_RS_MASK,     //   inlier mask of the host-API form
+    WS_SF_GAUSS,    // api_sift.hip: the Gaussian levels of the current octave (n + 3 planes of the doubled image)
+    WS_SF_DOG,      //   its DoG levels (n + 2 planes)
+    WS_SF_TMP,      //   row pass of the blur
+    WS_SF_STATE,    //   counters: candidates, refined, key points per octave
+    WS_SF_CAND,     //   extrema of the current octave (ksf_cand)
+    WS_SF_REFINED,  //   ... those that passed the refinement (sf::Refined)
+    WS_SF_KP,       //   key-point records of all octaves so far, before the final order (sf::Key)
+    WS_SF_DESC,     //   ... and their descriptors
+    WS_SF_PERM,     //   the final order
+    WS_SF_OUT,      //   results of the host-API form
     WS_COUNT
 };
 

@@ -1,10 +1,10 @@
 """Global align step -- mirror of `karios.matcher.global_align` (reference global_align.py) on the GPU.
 
-`_to_uint8` and `_preprocess` (percentile stretch + CLAHE, the dense front half) run on the GPU; SIFT stays with the caller on cv2;
-the descriptor matching behind it (both BFMatcher.knnMatch calls, Lowe's test, the mutual check: `match_descriptors`) runs on the GPU;
+`_to_uint8` and `_preprocess` (percentile stretch + CLAHE, the dense front half) run on the GPU; so does SIFT
+(`karios_amd.matcher.Sift`, passed as `sift=`); the descriptor matching behind it (both BFMatcher.knnMatch calls, Lowe's test, the mutual check: `match_descriptors`) runs on the GPU;
 so do `cv2.findHomography` with RANSAC (`estimate_homography`), the ECC refinement of every candidate (`refine_global_alignment`) and
 the renders of `apply_global_alignment` without its GeoTIFF writes (`render_global_alignment`).  `detect_global_alignment` chains
-them as the reference does; SIFT is the one part it takes from outside (its `sift` argument, cv2's by default).
+them as the reference does: with `sift=Sift()` the whole step runs on the GPU, with `sift=None` SIFT is cv2's, as before.
 Every GPU call goes through `karios_amd.ops`.  The reference's arithmetic is kept as it is, casts included; INTEGRATION.md
 section 6 notes the direction in which it composes the ECC residual.
 """
@@ -63,9 +63,12 @@ def _preprocess(arr: np.ndarray) -> np.ndarray:
 
 
 def _points(kp) -> np.ndarray:
-    """Key points as a float32 [n, 2] array: an array of coordinates, or a sequence of objects with `.pt` (cv2.KeyPoint)."""
+    """Key points as a float32 [n, 2] array: an array of coordinates (or an object that converts to one: `Sift`'s KeyPoints), or a
+    sequence of objects with `.pt` (cv2.KeyPoint)."""
     if isinstance(kp, np.ndarray):
         pts = kp
+    elif hasattr(kp, "__array__"):
+        pts = np.asarray(kp)
     else:
         pts = np.array([k.pt for k in kp], dtype=np.float32).reshape(-1, 2)
     if pts.ndim != 2 or pts.shape[1] != 2:
@@ -119,7 +122,7 @@ def _default_sift():
 
 def detect_global_alignment(mon_arr, ref_arr, prior=None, sift=None) -> GlobalAlignment:
     """detect_global_alignment of the reference (global_align.py:143-270): preprocess both images, SIFT (`sift.detectAndCompute`,
-    cv2's SIFT when `sift` is None), descriptor matching, the prior's log line, RANSAC, ECC refinement of the candidates."""
+    cv2's SIFT when `sift` is None, the GPU's with `sift=karios_amd.matcher.Sift()`), descriptor matching, the prior's log line, RANSAC, ECC refinement of the candidates."""
     if sift is None:
         sift = _default_sift()
     mon_u8 = _preprocess(mon_arr)

@@ -159,6 +159,27 @@ def homography_scene(n: int, inlier_share: float, sigma: float, seed: int, size:
     return src[order].astype(np.float32), dst[order].astype(np.float32), planted[order], H
 
 
+def sift_scene(size: int, seed: int) -> np.ndarray:
+    """uint8 [size, size] scene for SIFT: Gaussian blobs of many scales and axis-aligned bright / dark rectangles (corners) on a
+    gentle ramp, a little noise on top.  tests/test_sift_host.py checks that it carries >= 500 key points at 512 x 512."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:size, 0:size].astype(np.float32)
+    img = 110.0 + 20.0 * (xx / size) - 15.0 * (yy / size)
+    for _ in range(max(size * size // 1800, 4)):
+        w, h = rng.integers(5, 28, 2)
+        x0, y0 = rng.integers(-8, size - 4, 2)
+        img[max(y0, 0):y0 + h, max(x0, 0):x0 + w] += rng.choice([-1.0, 1.0]) * rng.uniform(25, 60)
+    for _ in range(max(size * size // 350, 8)):
+        s = rng.uniform(1.2, 5.0)
+        cx, cy = rng.uniform(0, size, 2)
+        amp = rng.choice([-1.0, 1.0]) * rng.uniform(30, 80)
+        r = int(4 * s) + 1
+        x0, x1, y0, y1 = max(int(cx) - r, 0), min(int(cx) + r + 1, size), max(int(cy) - r, 0), min(int(cy) + r + 1, size)
+        img[y0:y1, x0:x1] += amp * np.exp(-((xx[y0:y1, x0:x1] - cx) ** 2 + (yy[y0:y1, x0:x1] - cy) ** 2) / (2 * s * s))
+    img += rng.normal(0.0, 1.5, img.shape)
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
 def _base_torch(H: int, W: int, seed: int, device):
     """Device version of `make_base`: float32 texture field of shape (H + 2 PAD, W + 2 PAD)."""
     import torch
