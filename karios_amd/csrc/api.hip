@@ -106,77 +106,6 @@ extern "C" {
 
 int km_version(void) { return 101; }
 
-// Weak defaults of the global-align entry points.  The library's api_align.hip defines them (its strong definitions replace these
-// at link time); a build of the host half without the align kernels (the sanitizer build of tests/hoststub) answers KM_E_UNSUPPORTED.
-#define KM_ALIGN_ABSENT(name) return km_fail(c, KM_E_UNSUPPORTED, name ": built without api_align.hip")
-__attribute__((weak)) int km_warp_perspective(km_ctx *c, const void *, int, int, int, ptrdiff_t, void *, int, int, int, int, double, const double *)
-{ KM_ALIGN_ABSENT("warp_perspective"); }
-__attribute__((weak)) int km_warp_perspective_dev(km_ctx *c, const void *, int, int, int, ptrdiff_t, void *, int, int, ptrdiff_t, int, int, double,
-                                                  const double *)
-{ KM_ALIGN_ABSENT("warp_perspective"); }
-__attribute__((weak)) int km_sobel_magnitude(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, float *) { KM_ALIGN_ABSENT("sobel_magnitude"); }
-__attribute__((weak)) int km_sobel_magnitude_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, float *) { KM_ALIGN_ABSENT("sobel_magnitude"); }
-__attribute__((weak)) int km_find_transform_ecc(km_ctx *c, const void *, const void *, int, int, int, ptrdiff_t, int, int, ptrdiff_t, const uint8_t *,
-                                                ptrdiff_t, float *, int, double, int, double *, int *)
-{ KM_ALIGN_ABSENT("find_transform_ecc"); }
-__attribute__((weak)) int km_find_transform_ecc_dev(km_ctx *c, const void *, const void *, int, int, int, ptrdiff_t, int, int, ptrdiff_t,
-                                                    const uint8_t *, ptrdiff_t, float *, int, double, int, double *, int *)
-{ KM_ALIGN_ABSENT("find_transform_ecc"); }
-__attribute__((weak)) int km_refine_ecc_candidates(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, const uint8_t *, int, int, ptrdiff_t, int,
-                                                   const double *, int, double, double *, float *, double *, int *, int64_t *, int *)
-{ KM_ALIGN_ABSENT("refine_ecc_candidates"); }
-__attribute__((weak)) int km_refine_ecc_candidates_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, const uint8_t *, int, int, ptrdiff_t, int,
-                                                       const double *, int, double, double *, float *, double *, int *, int64_t *, int *)
-{ KM_ALIGN_ABSENT("refine_ecc_candidates"); }
-#undef KM_ALIGN_ABSENT
-// ... and of the align step's preprocessing (api_prep.hip), the same way
-#define KM_PREP_ABSENT(name) return km_fail(c, KM_E_UNSUPPORTED, name ": built without api_prep.hip")
-__attribute__((weak)) int km_order_statistics(km_ctx *c, const void *, int, int, int, ptrdiff_t, int, int, const double *, int64_t *, double *, double *,
-                                              double *)
-{ KM_PREP_ABSENT("order_statistics"); }
-__attribute__((weak)) int km_order_statistics_dev(km_ctx *c, const void *, int, int, int, ptrdiff_t, int, int, const double *, int64_t *, double *,
-                                                  double *, double *)
-{ KM_PREP_ABSENT("order_statistics"); }
-__attribute__((weak)) int km_stretch_percentile_u8(km_ctx *c, const void *, int, int, int, ptrdiff_t, double, double, uint8_t *)
-{ KM_PREP_ABSENT("stretch_percentile_u8"); }
-__attribute__((weak)) int km_stretch_percentile_u8_dev(km_ctx *c, const void *, int, int, int, ptrdiff_t, double, double, uint8_t *, ptrdiff_t)
-{ KM_PREP_ABSENT("stretch_percentile_u8"); }
-__attribute__((weak)) int km_clahe(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, double, int, int, uint8_t *) { KM_PREP_ABSENT("clahe"); }
-__attribute__((weak)) int km_clahe_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, double, int, int, uint8_t *, ptrdiff_t)
-{ KM_PREP_ABSENT("clahe"); }
-#undef KM_PREP_ABSENT
-// ... and of the align step's descriptor matching (api_match.hip)
-#define KM_MATCH_ABSENT(name) return km_fail(c, KM_E_UNSUPPORTED, name ": built without api_match.hip")
-__attribute__((weak)) int km_knn_match_u8(km_ctx *c, const uint8_t *, int, ptrdiff_t, const uint8_t *, int, ptrdiff_t, int, int, int *, float *)
-{ KM_MATCH_ABSENT("knn_match_u8"); }
-__attribute__((weak)) int km_knn_match_u8_dev(km_ctx *c, const uint8_t *, int, ptrdiff_t, const uint8_t *, int, ptrdiff_t, int, int, int *, float *)
-{ KM_MATCH_ABSENT("knn_match_u8"); }
-__attribute__((weak)) int km_match_lowe_mutual(km_ctx *c, const void *, int, ptrdiff_t, const void *, int, ptrdiff_t, int, int, double, int, int *, int *,
-                                               float *, int *)
-{ KM_MATCH_ABSENT("match_lowe_mutual"); }
-__attribute__((weak)) int km_match_lowe_mutual_dev(km_ctx *c, const void *, int, ptrdiff_t, const void *, int, ptrdiff_t, int, int, double, int, int *,
-                                                   int *, float *, int *)
-{ KM_MATCH_ABSENT("match_lowe_mutual"); }
-#undef KM_MATCH_ABSENT
-// ... and of its RANSAC homography (api_ransac.hip)
-#define KM_RANSAC_ABSENT return km_fail(c, KM_E_UNSUPPORTED, "find_homography_ransac: built without api_ransac.hip")
-__attribute__((weak)) int km_find_homography_ransac(km_ctx *c, const float *, ptrdiff_t, const float *, ptrdiff_t, int, double, int, double, double *,
-                                                    uint8_t *, int *, int64_t *, int *, int *)
-{ KM_RANSAC_ABSENT; }
-__attribute__((weak)) int km_find_homography_ransac_dev(km_ctx *c, const float *, ptrdiff_t, const float *, ptrdiff_t, int, double, int, double,
-                                                        double *, uint8_t *, int *, int64_t *, int *, int *)
-{ KM_RANSAC_ABSENT; }
-#undef KM_RANSAC_ABSENT
-// ... and of its SIFT (api_sift.hip)
-#define KM_SIFT_ABSENT return km_fail(c, KM_E_UNSUPPORTED, "sift_detect_and_compute: built without api_sift.hip")
-__attribute__((weak)) int km_sift_detect_and_compute(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, int, int, double, double, double, int, float *, float *,
-                                                     float *, float *, float *, int *, void *, int, ptrdiff_t, int *, int64_t *)
-{ KM_SIFT_ABSENT; }
-__attribute__((weak)) int km_sift_detect_and_compute_dev(km_ctx *c, const uint8_t *, int, int, ptrdiff_t, int, int, double, double, double, int, float *,
-                                                         float *, float *, float *, float *, int *, void *, int, ptrdiff_t, int *, int64_t *)
-{ KM_SIFT_ABSENT; }
-#undef KM_SIFT_ABSENT
-
 const char *km_last_error(km_ctx *ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
 
 int km_ctx_create(int device, km_ctx **out)

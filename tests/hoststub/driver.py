@@ -1,10 +1,10 @@
 """Driver of the host-only sanitizer build (run by tests/test_host_asan.py in a subprocess with libasan preloaded).
 
-Loads tests/hoststub/_build/libkarios_host_asan.so - api.hip + staging.hip compiled with g++ -fsanitize=address,undefined against
-the stand-in HIP layer - through the SAME ctypes signatures the product uses (karios_amd._lib.SIGNATURES) and walks the host-side
+Loads tests/hoststub/_build/libkarios_host_asan.so - every api*.hip + staging.hip compiled with g++ -fsanitize=address,undefined
+against the stand-in HIP layer - through the SAME ctypes signatures the product uses (karios_amd._lib.SIGNATURES) and walks the host-side
 bookkeeping: argument validation of every family of entry points, workspace slots (regrow, allocation failure), the page-locked
 staging ring and landing arena (sizes around the chunk boundaries, strided sources), upload tickets, the three-slot frame ring.
-Prints 'HOST-ASAN OK' at the end; any sanitizer report aborts the process.
+The entry points of the align step have a driver of their own, driver_align.py.  Prints 'HOST-ASAN OK' at the end; any sanitizer report aborts the process.
 """
 import ctypes as C
 import os

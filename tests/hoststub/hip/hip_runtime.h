@@ -1,10 +1,11 @@
 // HOST-ONLY STAND-IN for <hip/hip_runtime.h> - TEST INFRASTRUCTURE (tests/test_host_asan.py), never part of the product.
 //
 // SURVEY section 5 asks for sanitizer coverage of the host code; GPU AddressSanitizer is not available on this pool.  The host
-// half of libkarios_hip.so (api.hip: argument validation, workspace slots, upload tickets, the frame ring; staging.hip: the
-// page-locked staging ring and landing arena) is compiled a second time with g++ -fsanitize=address,undefined against THIS
-// header: "device" memory is host memory, streams execute at once, events are always complete, kernels (stub_kernels.cpp) do
-// nothing but fill their outputs deterministically.  What is exercised is the bookkeeping and every memcpy of the staging paths.
+// half of libkarios_hip.so (every api*.hip: argument validation, workspace slots, upload tickets, the frame ring, the host algebra
+// and list protocols of the align step; staging.hip: the page-locked staging ring and landing arena) is compiled a second time with
+// g++ -fsanitize=address,undefined against THIS header: "device" memory is host memory, streams execute at once, events are always
+// complete, kernels (stub_kernels.cpp, stub_kernels_align.cpp) fill their outputs deterministically - those of RANSAC and SIFT with
+// the arithmetic of ransac_math.hpp / sift_math.hpp.  What is exercised is the host code and every memcpy of the staging paths.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -32,6 +33,7 @@ enum hipMemoryType { hipMemoryTypeHost = 1, hipMemoryTypeDevice = 2, hipMemoryTy
 enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount = 16 };
 struct hipPointerAttribute_t { hipMemoryType type; int device; void *devicePointer, *hostPointer; };
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
+struct alignas(16) float4 { float x, y, z, w; };      // (k_align.hpp: the {image, gx, gy, pre-mask} plane of the ECC input)
 
 // registry of the page-locked ranges (hipHostMalloc): hipPointerGetAttributes tells them from pageable memory
 struct stub_state {

@@ -1,5 +1,6 @@
 // TEST INFRASTRUCTURE (tests/test_host_asan.py): the stand-in HIP layer of hip/hip_runtime.h and do-little replacements of every
-// kernel launcher api.hip / staging.hip call (csrc/common.hpp).  "Device" memory is malloc'ed host memory, so AddressSanitizer
+// kernel launcher of csrc/common.hpp that api*.hip / staging.hip call (the launchers of the align step's k_*.hpp headers have
+// their stand-ins in stub_kernels_align.cpp).  "Device" memory is malloc'ed host memory, so AddressSanitizer
 // sees every access: the stand-ins READ their inputs completely and WRITE their outputs completely, at the sizes the launchers
 // are entitled to - an undersized workspace slot, a short upload or a read-back beyond a buffer is a sanitizer report.
 #include "../../karios_amd/csrc/common.hpp"

@@ -10,16 +10,15 @@
 import logging
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import ransac_restatement as R
+import sanitizer_harness as san
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "karios_amd", "csrc")
 
 
 # ---- 1. anchors ---------------------------------------------------------------------------------------------------------------------------
@@ -183,19 +182,11 @@ int rs_refine(const float *M, const float *m, int count, double *H) { return rs:
 
 
 def test_shared_header_matches_the_restatement_under_sanitizers(tmp_path):
-    asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
-    if not os.path.isabs(asan) or not os.path.exists(asan):
-        pytest.skip("gcc has no libasan.so")
+    env = san.san_env()
     src, so = tmp_path / "ransac_shim.cpp", tmp_path / "libransac_shim.so"
     src.write_text(SHIM)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-shared", "-fPIC", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(so)])
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
-               OMP_NUM_THREADS="2")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ransac_host_driver.py"), str(so)], env=env, capture_output=True, text=True,
-                         timeout=1500)
-    assert out.returncode == 0 and "RANSAC-HOST OK" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
-    assert "Sanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-6000:]
+    san.build(src, so)
+    san.run([sys.executable, os.path.join(ROOT, "tests", "ransac_host_driver.py"), str(so)], "RANSAC-HOST OK", 1500, env)
 
 
 # ---- 3. host glue -----------------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ import pytest
 import align_restatement as A
 import match_restatement as M
 import ransac_restatement as R
+import sanitizer_harness as san
 import sift_restatement as S
 
 from karios_amd import _lib, ops, synth
@@ -27,7 +28,6 @@ from karios_amd.matcher import Sift, global_align
 from karios_amd.ops import sift_detect_and_compute
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "karios_amd", "csrc")
 
 
 # ---- 1. the shared header ---------------------------------------------------------------------------------------------------------------
@@ -61,19 +61,11 @@ void sf_describe(const float *img, ptrdiff_t stride, int rows, int cols, float p
 
 
 def test_shared_header_matches_the_restatement_under_sanitizers(tmp_path):
-    asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
-    if not os.path.isabs(asan) or not os.path.exists(asan):
-        pytest.skip("gcc has no libasan.so")
+    env = san.san_env()
     src, so = tmp_path / "sift_shim.cpp", tmp_path / "libsift_shim.so"
     src.write_text(SHIM)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-shared", "-fPIC", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(so)])
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
-               OMP_NUM_THREADS="2")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "sift_host_driver.py"), str(so)], env=env, capture_output=True, text=True,
-                         timeout=1500)
-    assert out.returncode == 0 and "SIFT-HOST OK" in out.stdout, out.stdout[-3000:] + out.stderr[-6000:]
-    assert "Sanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr[-6000:]
+    san.build(src, so)
+    out = san.run([sys.executable, os.path.join(ROOT, "tests", "sift_host_driver.py"), str(so)], "SIFT-HOST OK", 1500, env)
     cand, kps = re.search(r"candidates (\d+) key points (\d+)", out.stdout).groups()
     assert int(cand) >= 200 and int(kps) >= 200
 
@@ -106,8 +98,7 @@ def test_final_order_of_the_library_is_the_stated_total_order(tmp_path):
     with ties at every depth; the records that are not positive and finite take the header's other path."""
     src, exe = tmp_path / "order_main.cpp", tmp_path / "order_main"
     src.write_text(ORDER_MAIN)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                           "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)])
+    san.build(src, exe, shared=False)
     rng = np.random.default_rng(4)
 
     def records(n, lowest):
