@@ -526,9 +526,7 @@ int begin_call(km_ctx *c, int reset)
     { const int rcj = join_uploads(c); if (rcj) return rcj; }
     km_upload_check_drop(c);   // (checks armed by a call that failed half-way: their sources may be gone)
     c->land_jobs.clear(); c->land_used = 0;   // (... and results it queued for a caller buffer that may be gone too: km_d2h_queue without its flush)
-    c->spec_used = false; c->spec_flags = 0;
     c->retired_mark = c->retired.size();        // (km_d2h_flush inside this call frees only what was retired before it)
-    c->valid_job_pending = false;      // (a call that failed between the Laplacian pass and the fork)
     // early min / max (klt_tile_dev_impl): only a tile call that DIRECTLY follows a tile call may start its K1 beside the previous
     // unit's LK - any call in between may have produced the rasters on the main stream (km_shift_image_dev ...)
     c->lk_start_prev = c->lk_start_valid; c->lk_start_valid = false;
@@ -549,6 +547,33 @@ int begin_call(km_ctx *c, int reset)
     else if (reset == RESET_ZNCC)
         c->evs_used[c->ev_cur][ST_ZNCC] = false;
     return KM_OK;
+}
+
+int km_event(km_ctx *c, hipEvent_t *e) { if (!*e) KM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming)); return KM_OK; }
+int km_record(km_ctx *c, hipEvent_t ev, hipStream_t s) { KM_HIP(c, hipEventRecord(ev, s)); return KM_OK; }
+int km_wait(km_ctx *c, hipStream_t s, hipEvent_t ev) { KM_HIP(c, hipStreamWaitEvent(s, ev, 0)); return KM_OK; }
+
+// The second stream: the pyramids, the valid-pixel sum and the early min / max of a tile, the same and the setup of a batched submission.
+// "aux_priority" (development build) gives it the lowest priority: when a kernel of the main stream and one of this stream become ready
+// together (both wait for the Laplacians), the main stream's takes the compute units first and this stream's fill what it leaves
+int km_aux_stream(km_ctx *c)
+{
+    if (!c->aux_stream) {
+        int prio_lo = 0, prio_hi = 0;
+        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+        KM_HIP(c, hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, c->opt_aux_priority ? prio_lo : 0));
+    }
+    const int rc = km_event(c, &c->ev_fork);
+    return rc ? rc : km_event(c, &c->ev_join);
+}
+
+// The block-copy stream, made to wait for what c->stream holds so far (its tail event): a submitted frame's blocks leave there
+int km_block_stream(km_ctx *c)
+{
+    int rc;
+    if (!c->d2h_stream) KM_HIP(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
+    if ((rc = km_event(c, &c->ev_tail)) || (rc = km_record(c, c->ev_tail, c->stream))) return rc;
+    return km_wait(c, c->d2h_stream, c->ev_tail);
 }
 
 // Host -> device copy of caller memory on the library stream through the page-locked ring: `src` has been read completely on

@@ -142,7 +142,7 @@ int gftt_dev(km_ctx *c, const uint8_t *d_img, const uint8_t *d_mask, int H, int 
     return KM_OK;
 }
 
-int read_stats(km_ctx *c, km_scalars *sc)
+int read_stats(km_ctx *c, km_scalars *sc, km_call_modes *m)
 {
     km_scalars h;
     KM_D2H(c, &h, sc, sizeof h);
@@ -151,20 +151,27 @@ int read_stats(km_ctx *c, km_scalars *sc)
     c->stats.n_select_batches = h.n_batches;
     c->stats.max_eig = h.max_eig;
     c->stats.min_ref = h.mm[0]; c->stats.max_ref = h.mm[1]; c->stats.min_mon = h.mm[2]; c->stats.max_mon = h.mm[3];
-    if (c->spec_used) {   // the speculative corner path read nothing back on the way: its diagnostics arrive here
+    if (m && m->spec_used) {   // the speculative corner path read nothing back on the way: its diagnostics arrive here
         c->stats.valid_pixels = (int64_t)h.valid;
         c->stats.n_candidates = (int64_t)h.cut[3];
-        c->spec_flags = h.flags;
+        m->spec_flags = h.flags;
     }
     c->stats.tie_rows = (int32_t)h.tie_rows;
     if (h.n_cand == 0xffffffffu) return km_fail(c, KM_E_INTERNAL, "corner grid cell overflow");
     return KM_OK;
 }
 
-// klt_tracker numeric core on dense device u8 images (klt.py:103-142)
-int klt_track_dev(km_ctx *c, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap, const uint8_t *d_mask, int H, int W,
-                         const km_klt_params *prm, const float *d_p0_in, int n_p0, float *d_p0, float *d_p1, float *d_p0r, int cap,
-                         km_scalars *sc)
+int mark_lk_start(km_ctx *c)
+{
+    int rc;
+    if ((rc = km_event(c, &c->ev_lk_start)) || (rc = km_record(c, c->ev_lk_start, c->stream))) return rc;
+    c->lk_start_valid = true;
+    return KM_OK;
+}
+
+// klt_tracker numeric core on dense device u8 images (klt.py:103-142).  vjob: the valid-pixel sum the Laplacian pass left to this call (empty: none)
+static int klt_track_dev(km_ctx *c, km_call_modes &m, km_valid_job vjob, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap, const uint8_t *d_mask, int H,
+                         int W, const km_klt_params *prm, const float *d_p0_in, int n_p0, float *d_p0, float *d_p1, float *d_p0r, int cap, km_scalars *sc)
 {
     int rc;
     if (d_p0_in) {
@@ -175,10 +182,9 @@ int klt_track_dev(km_ctx *c, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap,
     }
     km_pyr A, B;
     // Speculative corner path (k_select2.hip): no host synchronisation, fixed capacities, flags instead of retries.  The
-    // caller reads sc->flags with the tile's result and repeats a flagged tile with c->spec_allowed = false.
-    bool spec = !d_p0_in && c->spec_allowed && c->opt_speculative && c->fused_eig && prm->max_corners > 0 && prm->min_distance >= 1 &&
-                !c->opt_key_cap && !c->opt_stage_cap && !c->opt_topk_factor && !c->opt_select_first;
-    if (!spec && (rc = kd_run_valid_sum(c))) return rc;  // (... and the valid-pixel sum)
+    // caller reads sc->flags with the tile's result and repeats a flagged tile with spec_allowed = false.
+    bool spec = !d_p0_in && m.spec_allowed && spec_path_covers(c, prm);
+    if (!spec && (rc = kd_run_valid_sum(c, &vjob))) return rc;  // (... and the valid-pixel sum)
     if (spec) {
         const size_t capk = (size_t)H * W / 8 + 4096 * KM_NSHARD;
         unsigned long long *keys = (unsigned long long *)km_ws(c, WS_KEYS0, capk * sizeof(unsigned long long));
@@ -189,37 +195,25 @@ int klt_track_dev(km_ctx *c, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap,
         // forked behind it (round 2) the pyramids stretched the chain's one-workgroup kernels from 8 to 36 us.
         bool forked = false;
         auto fork_pyramids = [&]() -> int {
-            if (!c->aux_stream) {
-                // lowest priority: when a kernel of the main stream and a pyramid kernel become ready together (both wait for the
-                // Laplacians), the main stream's takes the compute units first and the pyramids fill what it leaves
-                int prio_lo = 0, prio_hi = 0;
-                (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-                KM_HIP(c, hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, c->opt_aux_priority ? prio_lo : 0));
-                KM_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                KM_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-            }
-            KM_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-            KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-            hipStream_t main_stream = c->stream;
-            c->stream = c->aux_stream;
-            int r = kd_run_valid_sum(c);                     // (the Laplacian pass's deferred valid-pixel sum: off the main stream)
-            if (r == KM_OK) {
+            int r;
+            if ((r = km_aux_stream(c)) || (r = km_record(c, c->ev_fork, c->stream)) || (r = km_wait(c, c->aux_stream, c->ev_fork))) return r;
+            km_on_stream on(c, c->aux_stream);
+            if ((r = kd_run_valid_sum(c, &vjob))) return r;   // (the Laplacian pass's deferred valid-pixel sum: off the main stream)
+            {
                 km_stage_timer t(c, ST_PYRAMID);
-                r = build_pyramid_pair(c, d_ref_lap, d_mon_lap, H, W, prm->win_size, prm->max_level, &A, &B);
+                if ((r = build_pyramid_pair(c, d_ref_lap, d_mon_lap, H, W, prm->win_size, prm->max_level, &A, &B))) return r;
             }
-            if (r == KM_OK && hipEventRecord(c->ev_join, c->aux_stream) != hipSuccess) r = km_fail(c, KM_E_HIP, "hipEventRecord(join)");
-            c->stream = main_stream;
-            forked = r == KM_OK;
-            return r;
+            if ((r = km_record(c, c->ev_join, c->aux_stream))) return r;
+            forked = true;
+            return KM_OK;
         };
+        km_eig_partials partials;   // per-wave maxima of the fused pass: the ranking's first launch reduces them itself
         {
             // (the stage's start event sits in front of the fork: recorded between the fork and the kernel it would let the pyramid
             // kernels take the compute units first, and the bracketed kernel would measure 0.48 instead of 0.33 ms)
             km_stage_timer t(c, ST_EIGEN);
             if (c->opt_aux_pyramid && c->opt_aux_early && (rc = fork_pyramids())) return rc;
-            c->eig_defer_max = true; c->eig_partial = nullptr; c->eig_npartial = 0;   // the ranking's first launch reduces the per-wave maxima itself
-            rc = k2_eig_candidates(c, d_ref_lap, d_mask, H, W, prm->block_size, prm->quality_level, sc, keys, capk, false);
-            c->eig_defer_max = false;
+            rc = k2_eig_candidates(c, d_ref_lap, d_mask, H, W, prm->block_size, prm->quality_level, sc, keys, capk, false, &partials);
         }
         if (rc == KM_E_UNSUPPORTED) {
             spec = false;
@@ -229,7 +223,7 @@ int klt_track_dev(km_ctx *c, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap,
             if (c->opt_aux_pyramid && !forked && (rc = fork_pyramids())) return rc;
             {
                 km_stage_timer t(c, ST_SORT);
-                rc = kf_rank(c, keys, capk, H, W, prm->max_corners, prm->quality_level, prm->min_distance, sc);
+                rc = kf_rank(c, keys, capk, H, W, prm->max_corners, prm->quality_level, prm->min_distance, sc, partials);
             }
             if (rc == KM_OK) {
                 km_stage_timer t(c, ST_SELECT);
@@ -242,14 +236,14 @@ int klt_track_dev(km_ctx *c, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap,
             } else if (rc) return rc;
         }
         if (spec) {
-            c->spec_used = true;
+            m.spec_used = true;
             if (!forked) {
                 km_stage_timer t(c, ST_PYRAMID);
                 if ((rc = build_pyramid_pair(c, d_ref_lap, d_mon_lap, H, W, prm->win_size, prm->max_level, &A, &B))) return rc;
             }
         }
     }
-    if ((rc = kd_run_valid_sum(c))) return rc;           // (a path that never forked the second stream)
+    if ((rc = kd_run_valid_sum(c, &vjob))) return rc;    // (a path that never forked the second stream)
     if (spec) {
         // corners, their count and the pyramids are enqueued
     } else if (d_p0_in) {
@@ -281,9 +275,7 @@ int klt_track_dev(km_ctx *c, const uint8_t *d_ref_lap, const uint8_t *d_mon_lap,
         if (spec && !c->lk_start_valid) {
             // (the next unit's early min / max starts here: beside LK - in front of the selection sweeps, the ranking or behind LK it
             // measured slower, CHANGELOG.md round 4)
-            if (!c->ev_lk_start) KM_HIP(c, hipEventCreateWithFlags(&c->ev_lk_start, hipEventDisableTiming));
-            KM_HIP(c, hipEventRecord(c->ev_lk_start, c->stream));
-            c->lk_start_valid = true;
+            if ((rc = mark_lk_start(c))) return rc;
         }
         if ((rc = kl_track(c, A, B, d_p0, &sc->n_corners, n_max, prm->win_size, prm->max_count, prm->epsilon, true, d_p1, d_p0r)))
             return rc;
@@ -302,9 +294,9 @@ int check_params(km_ctx *c, const km_klt_params *p)
     return KM_OK;
 }
 
-int klt_tile_dev_impl(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
+static int klt_tile_dev_impl(km_ctx *c, km_call_modes &m, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
                              const uint8_t *d_mask, ptrdiff_t smask, const double *nodata_ref, const double *nodata_mon, const km_klt_params *prm,
-                             float *d_p0, float *d_p1, float *d_p0r, int cap, km_scalars *sc, bool *no_valid)
+                             float *d_p0, float *d_p1, float *d_p0r, int cap, km_scalars *sc)
 {
     int rc;
     const size_t n = (size_t)H * W;
@@ -321,7 +313,8 @@ int klt_tile_dev_impl(km_ctx *c, const void *d_ref, const void *d_mon, int dtype
         d_mask = dense;
     }
     const double *mm = sc->mm;
-    if (dtype != KM_U8 && c->mm_early_allowed && c->opt_mm_early && c->lk_start_prev && c->aux_stream) {
+    km_valid_job vjob;
+    if (dtype != KM_U8 && m.mm_early_allowed && c->opt_mm_early && c->lk_start_prev && c->aux_stream) {
         // Early min / max: K1 of THIS unit does not queue behind the tail of the previous one (LK, FB test, ZNCC - instruction-bound
         // kernels of short-lived waves that leave HBM idle) but starts on the second stream the moment the previous unit's LK launch
         // starts, and streams the two rasters beside it.  The previous tile call of this context recorded ev_lk_start; if the GPU is
@@ -329,18 +322,16 @@ int klt_tile_dev_impl(km_ctx *c, const void *d_ref, const void *d_mon, int dtype
         // zeroed on the main stream at the start of every call, WS_PARTIAL belongs to the kernels of the unit still running).
         double *mm_early = (double *)km_ws(c, WS_MM_EARLY, 4 * sizeof(double));
         if (!mm_early) return KM_E_NOMEM;
-        if (!c->ev_mm) KM_HIP(c, hipEventCreateWithFlags(&c->ev_mm, hipEventDisableTiming));
-        KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_lk_start, 0));
-        hipStream_t main_stream = c->stream;
-        c->stream = c->aux_stream;
+        if ((rc = km_event(c, &c->ev_mm)) || (rc = km_wait(c, c->aux_stream, c->ev_lk_start))) return rc;
         {
-            km_stage_timer t(c, ST_MINMAX);
-            rc = kd_minmax_pair_ws(c, d_ref, d_mon, dtype, H, W, sref, smon, mm_early, WS_MM_PARTIAL);
+            km_on_stream on(c, c->aux_stream);
+            {
+                km_stage_timer t(c, ST_MINMAX);
+                if ((rc = kd_minmax_pair_ws(c, d_ref, d_mon, dtype, H, W, sref, smon, mm_early, WS_MM_PARTIAL))) return rc;
+            }
+            if ((rc = km_record(c, c->ev_mm, c->aux_stream))) return rc;
         }
-        if (rc == KM_OK && hipEventRecord(c->ev_mm, c->aux_stream) != hipSuccess) rc = km_fail(c, KM_E_HIP, "hipEventRecord(min/max)");
-        c->stream = main_stream;
-        if (rc) return rc;
-        KM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_mm, 0));
+        if ((rc = km_wait(c, c->stream, c->ev_mm))) return rc;
         mm = mm_early;
         c->stats.path_flags |= KM_PATH_MM_EARLY;
     } else if (dtype != KM_U8) {
@@ -350,29 +341,22 @@ int klt_tile_dev_impl(km_ctx *c, const void *d_ref, const void *d_mon, int dtype
     {
         km_stage_timer t(c, ST_LAPLACIAN);
         if (d_mask) { if ((rc = kd_count_nonzero(c, d_mask, n, &sc->valid))) return rc; }
-        // on the sync-free path with the pyramids on a second stream the valid-pixel sum goes there too (klt_track_dev: same condition)
-        c->defer_valid_sum = c->opt_defer_valid && c->spec_allowed && c->opt_speculative && c->fused_eig && c->opt_aux_pyramid && prm->max_corners > 0 &&
-                             prm->min_distance >= 1 && !c->opt_key_cap && !c->opt_stage_cap && !c->opt_topk_factor && !c->opt_select_first;
-        rc = kd_stretch_laplacian_pair(c, d_ref, d_mon, dtype, H, W, sref, smon, mm, prm->ksize_ref, prm->ksize_mon,
-                                       prm->invert_mon, nodata_ref, nodata_mon, lap_ref, lap_mon, mask_auto, &sc->valid);
-        c->defer_valid_sum = false;
-        if (rc) return rc;
+        // on the sync-free path with the pyramids on a second stream the valid-pixel sum goes there too (klt_track_dev launches it)
+        const bool defer = c->opt_defer_valid && c->opt_aux_pyramid && m.spec_allowed && spec_path_covers(c, prm);
+        if ((rc = kd_stretch_laplacian_pair(c, d_ref, d_mon, dtype, H, W, sref, smon, mm, prm->ksize_ref, prm->ksize_mon, prm->invert_mon, nodata_ref,
+                                            nodata_mon, lap_ref, lap_mon, mask_auto, &sc->valid, defer ? &vjob : nullptr)))
+            return rc;
     }
     // "No valid pixels" (klt.py:276-279) needs no early exit: an all-zero mask gives max-eig 0, no candidate, no corner.
     // The count itself reaches the host with the candidate count (gftt_dev), i.e. without an extra synchronisation.
-    *no_valid = false;
-    const int rc2 = klt_track_dev(c, lap_ref, lap_mon, d_mask ? d_mask : mask_auto, H, W, prm, nullptr, 0, d_p0, d_p1, d_p0r, cap, sc);
-    *no_valid = c->stats.valid_pixels == 0;
-    return rc2;
+    return klt_track_dev(c, m, vjob, lap_ref, lap_mon, d_mask ? d_mask : mask_auto, H, W, prm, nullptr, 0, d_p0, d_p1, d_p0r, cap, sc);
 }
 
-extern "C" {
-
-extern "C++" int fetch_tracks(km_ctx *c, km_scalars *sc, const float *d_p0, const float *d_p1, const float *d_p0r, float *p0, float *p1,
+static int fetch_tracks(km_ctx *c, km_call_modes &m, km_scalars *sc, const float *d_p0, const float *d_p1, const float *d_p0r, float *p0, float *p1,
                         float *p0r, int cap, int *out_n)
 {
     int rc;
-    if ((rc = read_stats(c, sc))) return rc;
+    if ((rc = read_stats(c, sc, &m))) return rc;
     int n = c->stats.n_init;
     if (n > cap) return km_fail(c, KM_E_ARG, "%d corners exceed capacity %d", n, cap);
     if (n > 0) {
@@ -385,6 +369,57 @@ extern "C++" int fetch_tracks(km_ctx *c, km_scalars *sc, const float *d_p0, cons
     *out_n = n;
     return KM_OK;
 }
+
+// The previous submitted frame's block may still be on its way to the host (on the d2h stream): WS_FRAME may be rewritten once it
+// has left - a device-side wait that never stalls in practice (the copy takes 13 us, the next frame is written ~1 ms later).
+int frame_block_free(km_ctx *c)
+{
+    const int rc = c->frame_copy ? km_wait(c, c->stream, c->frame_copy) : KM_OK;
+    if (rc == KM_OK) c->frame_copy = nullptr;
+    return rc;
+}
+
+int frame_sink_check(km_ctx *c, size_t pitch, int n, size_t ob)
+{
+    if (!pitch) pitch = ob;
+    if (!c->frame_sink || (pitch >= ob && c->frame_sink_cap >= pitch * (size_t)(n - 1) + ob)) return KM_OK;
+    return km_fail(c, KM_E_ARG, "frame sink of %zu bytes (pitch %zu) is smaller than %d frame block(s) of %zu bytes", c->frame_sink_cap, pitch, n, ob);
+}
+
+// the slot of a submitted frame: `bytes` of page-locked memory (one eighth of head-room when it grows) and its completion event
+int frame_slot_reserve(km_ctx *c, km_frame_slot *slot, size_t bytes)
+{
+    if (slot->cap < bytes) {
+        if (slot->host) KM_HIP(c, hipHostFree(slot->host));
+        slot->host = nullptr; slot->cap = 0;
+        KM_HIP(c, hipHostMalloc(&slot->host, bytes + bytes / 8, hipHostMallocDefault));
+        slot->cap = bytes + bytes / 8;
+    }
+    return km_event(c, &slot->done);
+}
+
+// n frame blocks of ob bytes (device pitch ob_al) leave d_out on stream s: into the frame sink, if there is one (km_set_frame_sink: the
+// device-side copy; km_stream_wait_frame lets a stream of the caller - the one an RCCL collective is issued on - wait for exactly this
+// copy), and into the slot's page-locked buffer.  One block travels as a plain copy, several as one strided copy each way
+int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, size_t ob, size_t ob_al, int n, void *sink, size_t sink_pitch, hipStream_t s)
+{
+    int rc;
+    slot->sunk_valid = false;
+    if (sink) {
+        if (n == 1) KM_HIP(c, hipMemcpyAsync(sink, d_out, ob, hipMemcpyDeviceToDevice, s));
+        else KM_HIP(c, hipMemcpy2DAsync(sink, sink_pitch ? sink_pitch : ob, d_out, ob_al, ob, (size_t)n, hipMemcpyDeviceToDevice, s));
+        if ((rc = km_event(c, &slot->sunk)) || (rc = km_record(c, slot->sunk, s))) return rc;
+        slot->sunk_valid = true;
+    }
+    if (n == 1) KM_HIP(c, hipMemcpyAsync(slot->host, d_out, ob, hipMemcpyDeviceToHost, s));
+    else KM_HIP(c, hipMemcpy2DAsync(slot->host, ob, d_out, ob_al, ob, (size_t)n, hipMemcpyDeviceToHost, s));
+    if ((rc = km_record(c, slot->done, s))) return rc;
+    c->frame_copy = slot->done;
+    slot->bytes = ob * n;
+    return KM_OK;
+}
+
+extern "C" {
 
 int km_klt_track(km_ctx *c, const uint8_t *ref_lap, const uint8_t *mon_lap, const uint8_t *mask, int H, int W, const km_klt_params *prm,
                  const float *p0_in, int n_p0, float *p0, float *p1, float *p0r, int cap, int *out_n)
@@ -410,10 +445,11 @@ int km_klt_track(km_ctx *c, const uint8_t *ref_lap, const uint8_t *mon_lap, cons
         if (n_p0 > 0) { const int rch = h2d_now(c, d_p0, p0_in, (size_t)n_p0 * 2 * sizeof(float)); if (rch) return rch; }
         d_p0_in = d_p0;
     }
-    if ((rc = klt_track_dev(c, (const uint8_t *)d_ref, (const uint8_t *)d_mon, (const uint8_t *)d_mask, H, W, prm, d_p0_in, n_p0, d_p0, d_p1,
-                            d_p0r, cap, sc)))
+    km_call_modes m;
+    if ((rc = klt_track_dev(c, m, km_valid_job(), (const uint8_t *)d_ref, (const uint8_t *)d_mon, (const uint8_t *)d_mask, H, W, prm, d_p0_in, n_p0, d_p0,
+                            d_p1, d_p0r, cap, sc)))
         return rc;
-    return fetch_tracks(c, sc, d_p0, d_p1, d_p0r, p0, p1, p0r, cap, out_n);
+    return fetch_tracks(c, m, sc, d_p0, d_p1, d_p0r, p0, p1, p0r, cap, out_n);
 }
 
 int km_klt_tile(km_ctx *c, const void *ref, const void *mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon, const uint8_t *mask,
@@ -438,16 +474,14 @@ int km_klt_tile(km_ctx *c, const void *ref, const void *mon, int dtype, int H, i
     if (!sc || !d_p0 || !d_p1 || !d_p0r) return KM_E_NOMEM;
     for (int attempt = 0; attempt < 2; attempt++) {
         KM_HIP(c, hipMemsetAsync(sc, 0, sizeof *sc, c->stream));
-        bool no_valid = false;
-        c->spec_allowed = attempt == 0; c->spec_used = false; c->spec_flags = 0;
-        rc = klt_tile_dev_impl(c, d_ref, d_mon, dtype, H, W, W, W, (const uint8_t *)d_mask, W, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc,
-                               &no_valid);
-        c->spec_allowed = false;
-        if (rc) return rc;
-        if ((rc = fetch_tracks(c, sc, d_p0, d_p1, d_p0r, p0, p1, p0r, cap, out_n))) return rc;
+        km_call_modes m;
+        m.spec_allowed = attempt == 0;
+        if ((rc = klt_tile_dev_impl(c, m, d_ref, d_mon, dtype, H, W, W, W, (const uint8_t *)d_mask, W, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc)))
+            return rc;
+        if ((rc = fetch_tracks(c, m, sc, d_p0, d_p1, d_p0r, p0, p1, p0r, cap, out_n))) return rc;
         (void)verify_upload(c, "end of km_klt_tile (ref)", WS_RAW_A, ref, es, H, W, sref, d_ref);
         (void)verify_upload(c, "end of km_klt_tile (mon)", WS_RAW_B, mon, es, H, W, smon, d_mon);
-        if (!(c->spec_used && c->spec_flags)) break;       // flagged speculative run: once more through the exact path
+        if (!(m.spec_used && m.spec_flags)) break;         // flagged speculative run: once more through the exact path
         memset(&c->stats, 0, sizeof c->stats);
         c->stats.path_flags |= KM_PATH_SPEC_RETRY;
     }
@@ -507,22 +541,9 @@ int km_klt_tile_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, 
     km_scalars *sc = scalars(c);
     if (!sc) return KM_E_NOMEM;
     KM_HIP(c, hipMemsetAsync(sc, 0, sizeof *sc, c->stream));
-    bool no_valid = false;
-    if ((rc = klt_tile_dev_impl(c, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc,
-                                &no_valid)))
-        return rc;
+    km_call_modes m;           // (nobody reads this call's flags: the exact corner path)
+    if ((rc = klt_tile_dev_impl(c, m, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc))) return rc;
     KM_HIP(c, hipMemcpyAsync(d_n, &sc->n_corners, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-    return KM_OK;
-}
-
-// The previous submitted frame's block may still be on its way to the host (on the d2h stream): WS_FRAME may be rewritten once it
-// has left - a device-side wait that never stalls in practice (the copy takes 13 us, the next frame is written ~1 ms later).
-extern "C++" int frame_block_free(km_ctx *c)
-{
-    if (c->frame_copy) {
-        KM_HIP(c, hipStreamWaitEvent(c->stream, c->frame_copy, 0));
-        c->frame_copy = nullptr;
-    }
     return KM_OK;
 }
 
@@ -556,92 +577,65 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
     char *d_out = (char *)km_ws(c, WS_FRAME, ob);
     if (!sc || !d_p0 || !d_p1 || !d_p0r || !d_out) return KM_E_NOMEM;
     for (int attempt = 0;; attempt++) {
-    KM_HIP(c, hipMemsetAsync(sc, 0, sizeof *sc, c->stream));
-    bool no_valid = false;
-    // corners without a host synchronisation where the case allows it; header word 2 of the frame block carries the flags of
-    // that speculative path: the synchronous variants repeat a flagged tile right here, a submitted one is repeated by the
-    // caller that waits for it (karios_amd.resident)
-    c->spec_allowed = attempt == 0; c->spec_used = false; c->spec_flags = 0;
-    c->mm_early_allowed = slot != nullptr;     // (the synchronous forms report min / max in their statistics: scalar block)
-    rc = klt_tile_dev_impl(c, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc, &no_valid);
-    c->spec_allowed = false; c->mm_early_allowed = false;
-    if (rc) return rc;
-    const int n_max = prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap;
-    if ((rc = frame_block_free(c))) return rc;
-    {
-        km_stage_timer t(c, ST_FRAME);
-        if ((rc = kf_frame(c, d_p0, d_p1, d_p0r, &sc->n_corners, n_max, cap, 0.1f, x_off, y_off, d_out, c->spec_used ? sc : nullptr, W))) return rc;
-    }
-    if (with_zncc) {
-        km_stage_timer t(c, ST_ZNCC);
-        const float *f = (const float *)(d_out + 16);
-        if ((rc = kz_zncc_filtered(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, f, f + cap, f + 2 * (size_t)cap,
-                                   f + 3 * (size_t)cap, n_max, (const int *)d_out, f + 4 * (size_t)cap, (float)zncc_threshold,
-                                   (double *)(d_out + fb))))
-            return rc;
-    }
-    if (with_mi) {
-        // the other two scores of _handle_klt_results (core.py:894-907) for the same rows, behind ZNCC in the same call: the chips of
-        // a key point (57 x 57, around the 43 x 43 ZNCC window) are still in the XCD's L2
-        km_stage_timer t(c, ST_MI);
-        const float *f = (const float *)(d_out + 16);
-        double *st = (double *)(d_out + fb) + cap;
-        if ((rc = kmi_batch(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, f, f + cap, f + 2 * (size_t)cap, f + 3 * (size_t)cap, n_max,
-                            (const int *)d_out, f + 4 * (size_t)cap, (float)zncc_threshold, st, st + cap)))
-            return rc;
-    }
-    if (c->frame_sink && c->frame_sink_cap < ob)
-        return km_fail(c, KM_E_ARG, "frame sink of %zu bytes is smaller than the %zu-byte frame block", c->frame_sink_cap, ob);
-    if (c->frame_sink && !slot) KM_HIP(c, hipMemcpyAsync(c->frame_sink, d_out, ob, hipMemcpyDeviceToDevice, c->stream));
-    if (slot) {
-        if (slot->cap < ob) {
-            if (slot->host) KM_HIP(c, hipHostFree(slot->host));
-            slot->host = nullptr; slot->cap = 0;
-            KM_HIP(c, hipHostMalloc(&slot->host, ob + ob / 8, hipHostMallocDefault));
-            slot->cap = ob + ob / 8;
+        KM_HIP(c, hipMemsetAsync(sc, 0, sizeof *sc, c->stream));
+        // corners without a host synchronisation where the case allows it; header word 2 of the frame block carries the flags of
+        // that speculative path: the synchronous variants repeat a flagged tile right here, a submitted one is repeated by the
+        // caller that waits for it (karios_amd.resident)
+        km_call_modes m;
+        m.spec_allowed = attempt == 0;
+        m.mm_early_allowed = slot != nullptr;     // (the synchronous forms report min / max in their statistics: scalar block)
+        if ((rc = klt_tile_dev_impl(c, m, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc))) return rc;
+        const int n_max = prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap;
+        if ((rc = frame_block_free(c))) return rc;
+        {
+            km_stage_timer t(c, ST_FRAME);
+            if ((rc = kf_frame(c, d_p0, d_p1, d_p0r, &sc->n_corners, n_max, cap, 0.1f, x_off, y_off, d_out, m.spec_used ? sc : nullptr, W))) return rc;
         }
-        if (!slot->done) KM_HIP(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
-        // the block leaves on a stream of its own: 13 us of DMA that the next submission's first kernels need not wait for
-        // (the next frame is written into WS_FRAME ~1 ms later, behind a wait for this copy: see frame_block_free)
-        if (!c->d2h_stream) {
-            KM_HIP(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-            KM_HIP(c, hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
+        if (with_zncc) {
+            km_stage_timer t(c, ST_ZNCC);
+            const float *f = (const float *)(d_out + 16);
+            if ((rc = kz_zncc_filtered(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, f, f + cap, f + 2 * (size_t)cap,
+                                       f + 3 * (size_t)cap, n_max, (const int *)d_out, f + 4 * (size_t)cap, (float)zncc_threshold,
+                                       (double *)(d_out + fb))))
+                return rc;
         }
-        KM_HIP(c, hipEventRecord(c->ev_tail, c->stream));
-        KM_HIP(c, hipStreamWaitEvent(c->d2h_stream, c->ev_tail, 0));
-        slot->sunk_valid = false;
-        if (c->frame_sink) {
-            // the device-side copy of the block (km_set_frame_sink) leaves there too: on the compute stream it cost the next unit 11 us.
-            // km_stream_wait_frame: a stream of the caller (the one an RCCL collective is issued on) can wait for exactly this copy
-            KM_HIP(c, hipMemcpyAsync(c->frame_sink, d_out, ob, hipMemcpyDeviceToDevice, c->d2h_stream));
-            if (!slot->sunk) KM_HIP(c, hipEventCreateWithFlags(&slot->sunk, hipEventDisableTiming));
-            KM_HIP(c, hipEventRecord(slot->sunk, c->d2h_stream));
-            slot->sunk_valid = true;
+        if (with_mi) {
+            // the other two scores of _handle_klt_results (core.py:894-907) for the same rows, behind ZNCC in the same call: the chips of
+            // a key point (57 x 57, around the 43 x 43 ZNCC window) are still in the XCD's L2
+            km_stage_timer t(c, ST_MI);
+            const float *f = (const float *)(d_out + 16);
+            double *st = (double *)(d_out + fb) + cap;
+            if ((rc = kmi_batch(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, f, f + cap, f + 2 * (size_t)cap, f + 3 * (size_t)cap,
+                                n_max, (const int *)d_out, f + 4 * (size_t)cap, (float)zncc_threshold, st, st + cap)))
+                return rc;
         }
-        KM_HIP(c, hipMemcpyAsync(slot->host, d_out, ob, hipMemcpyDeviceToHost, c->d2h_stream));
-        KM_HIP(c, hipEventRecord(slot->done, c->d2h_stream));
-        c->frame_copy = slot->done;
-        slot->bytes = ob;
+        if ((rc = frame_sink_check(c, 0, 1, ob))) return rc;      // (a single block ignores the sink's pitch)
+        if (slot) {
+            // the block leaves on a stream of its own: 13 us of DMA that the next submission's first kernels need not wait for
+            // (the next frame is written into WS_FRAME ~1 ms later, behind a wait for this copy: see frame_block_free); the
+            // device-side copy into the frame sink leaves there too: on the compute stream it cost the next unit 11 us
+            if ((rc = frame_slot_reserve(c, slot, ob)) || (rc = km_block_stream(c))) return rc;
+            return frame_blocks_out(c, slot, d_out, ob, ob, 1, c->frame_sink, 0, c->d2h_stream);
+        }
+        if (c->frame_sink) KM_HIP(c, hipMemcpyAsync(c->frame_sink, d_out, ob, hipMemcpyDeviceToDevice, c->stream));
+        km_scalars *land = m.spec_used ? (km_scalars *)km_pinned_rb(c, sizeof(km_scalars)) : nullptr;
+        if (land) KM_HIP(c, hipMemcpyAsync(land, sc, sizeof *land, hipMemcpyDeviceToHost, c->stream));   // diagnostics of the sync-free corner path
+        KM_D2H(c, host_out, d_out, ob);
+        KM_FLUSH(c);
+        c->stats.n_init = ((const int *)host_out)[1];
+        if (land) {
+            c->stats.valid_pixels = (int64_t)land->valid;
+            c->stats.n_candidates = (int64_t)land->cut[3];
+            c->stats.tie_rows = (int32_t)land->tie_rows;
+            c->stats.max_eig = land->max_eig;
+            c->stats.min_ref = land->mm[0]; c->stats.max_ref = land->mm[1]; c->stats.min_mon = land->mm[2]; c->stats.max_mon = land->mm[3];
+            if (land->flags) {                                   // did not fit the fixed capacities: the exact path decides
+                memset(&c->stats, 0, sizeof c->stats);
+                c->stats.path_flags |= KM_PATH_SPEC_RETRY;
+                continue;
+            }
+        }
         return KM_OK;
-    }
-    km_scalars *land = c->spec_used ? (km_scalars *)km_pinned_rb(c, sizeof(km_scalars)) : nullptr;
-    if (land) KM_HIP(c, hipMemcpyAsync(land, sc, sizeof *land, hipMemcpyDeviceToHost, c->stream));   // diagnostics of the sync-free corner path
-    KM_D2H(c, host_out, d_out, ob);
-    KM_FLUSH(c);
-    c->stats.n_init = ((const int *)host_out)[1];
-    if (land) {
-        c->stats.valid_pixels = (int64_t)land->valid;
-        c->stats.n_candidates = (int64_t)land->cut[3];
-        c->stats.tie_rows = (int32_t)land->tie_rows;
-        c->stats.max_eig = land->max_eig;
-        c->stats.min_ref = land->mm[0]; c->stats.max_ref = land->mm[1]; c->stats.min_mon = land->mm[2]; c->stats.max_mon = land->mm[3];
-        if (land->flags) {                                   // did not fit the fixed capacities: the exact path decides
-            memset(&c->stats, 0, sizeof c->stats);
-            c->stats.path_flags |= KM_PATH_SPEC_RETRY;
-            continue;
-        }
-    }
-    return KM_OK;
     }
 }
 
@@ -722,9 +716,8 @@ int km_klt_auto_ksize_frame_dev(km_ctx *c, const void *d_ref, const void *d_mon,
     int n_p0[8];
     const int *d_np0[8];                                             // device word holding the corner count of reference kernel k
     bool corners_done = false, tracks_done = false;
-    const bool batchable = prm->max_level == 1 && probe.levels == 1 && nk <= KM_UNITS_MAX && nk * nk <= KM_LK_JOBS_MAX && prm->max_corners > 0 &&
-                           prm->min_distance >= 1 && c->opt_speculative && c->fused_eig && !c->opt_key_cap && !c->opt_stage_cap && !c->opt_topk_factor &&
-                           !c->opt_select_first && c->opt_eig3 && c->opt_lk2 && W >= 512 && H >= 2 * prm->block_size + 8;
+    const bool batchable = prm->max_level == 1 && probe.levels == 1 && nk <= KM_UNITS_MAX && nk * nk <= KM_LK_JOBS_MAX && spec_path_covers(c, prm) &&
+                           c->opt_eig3 && c->opt_lk2 && W >= 512 && H >= 2 * prm->block_size + 8;
     km_units U;
     if (batchable) {
         U.n = nk; U.dtype = KM_U8; U.capk = n / 8 + 4096 * KM_NSHARD;

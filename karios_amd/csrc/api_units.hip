@@ -42,7 +42,16 @@ struct km_units_tail {
     size_t fb = 0, ob = 0, ob_al = 0;
     char *d_out = nullptr;
     void *sink = nullptr;                 // the frame sink as it was set at submission time
-    size_t sink_cap = 0, sink_pitch = 0;
+    size_t sink_pitch = 0;
+};
+
+// Lane, stage-event set and (tail: profile sampling) of one submission or of its tail; every way out restores what it found
+struct units_scope {
+    km_ctx *c;
+    const int lane, ev;
+    const bool skip, in_submit, tail;
+    units_scope(km_ctx *ctx, bool is_tail) : c(ctx), lane(ctx->lane), ev(ctx->ev_cur), skip(ctx->profile_skip), in_submit(ctx->in_units_submit), tail(is_tail) {}
+    ~units_scope() { c->lane = lane; c->ev_cur = ev; c->in_units_submit = in_submit; if (tail) c->profile_skip = skip; }
 };
 
 // K, F and the copy-out of a submission.  piped: K on the main stream behind the lane's chain, F on the chain stream behind K.
@@ -53,30 +62,20 @@ static int units_tail(km_ctx *c, km_units_tail &T)
     const int n = T.n;
     km_frame_slot *slot = &c->fslot[T.slot];
     hipStream_t const main_stream = c->stream;
-    const int lane_before = c->lane, ev_before = c->ev_cur;
-    struct restore_t { km_ctx *c; hipStream_t s; int lane, ev; bool skip; ~restore_t() { c->stream = s; c->lane = lane; c->ev_cur = ev; c->profile_skip = skip; } }
-        restore{c, main_stream, lane_before, ev_before, c->profile_skip};
+    units_scope scope(c, true);
     c->lane = T.lane;
     c->ev_cur = 1 + T.slot;
     c->profile_skip = T.profile_skip;             // (the stage events of THIS submission: sampled with its own tick)
     hipEvent_t *ev = c->ev_lane[T.lane];
-    KM_HIP(c, hipStreamWaitEvent(main_stream, ev[EV_JOIN], 0));
-    if (T.piped) KM_HIP(c, hipStreamWaitEvent(main_stream, ev[EV_C_DONE], 0));
+    if ((rc = km_wait(c, main_stream, ev[EV_JOIN])) || (T.piped && (rc = km_wait(c, main_stream, ev[EV_C_DONE])))) return rc;
     // ---- K7: LK forward + backward of every unit's corners in one launch
     {
         km_stage_timer t(c, ST_LK);
-        if (!T.piped) {          // (unpipelined: the next submission's early min / max starts here)
-            if (!c->ev_lk_start) KM_HIP(c, hipEventCreateWithFlags(&c->ev_lk_start, hipEventDisableTiming));
-            KM_HIP(c, hipEventRecord(c->ev_lk_start, c->stream));
-            c->lk_start_valid = true;
-        }
+        if (!T.piped && (rc = mark_lk_start(c))) return rc;          // (unpipelined: the next submission's early min / max starts here)
         if ((rc = kl_units_launch(c, n, T.n_max, T.prm.win_size))) return rc;
     }
-    if (T.piped) {
-        KM_HIP(c, hipEventRecord(ev[EV_K_DONE], main_stream));
-        KM_HIP(c, hipStreamWaitEvent(c->chain_stream, ev[EV_K_DONE], 0));
-        c->stream = c->chain_stream;
-    }
+    if (T.piped && ((rc = km_record(c, ev[EV_K_DONE], main_stream)) || (rc = km_wait(c, c->chain_stream, ev[EV_K_DONE])))) return rc;
+    km_on_stream on(c, T.piped ? c->chain_stream : main_stream);
     // ---- K8: FB test, score, (x0, y0) order; K9 / K12: scores of the confident rows
     if ((rc = frame_block_free(c))) return rc;
     {
@@ -108,35 +107,27 @@ static int units_tail(km_ctx *c, km_units_tail &T)
     // block-copy stream (the next submission's dense kernels queue behind this tail on the main stream).  Pipelined: in the chain stream's
     // own order - one stream fewer: the runtime maps streams onto FOUR hardware queues, and whenever the copy stream shared one with the
     // main stream its device-side wait for this chain held the next eigenvalue pass up (1 ms per 16-unit step, profiles/timeline_r06_c4.txt)
-    const size_t ob = T.ob, ob_al = T.ob_al;
-    if (!slot->done) KM_HIP(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
-    hipStream_t out_stream = c->stream;
-    if (!T.piped) {
-        if (!c->d2h_stream) {
-            KM_HIP(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-            KM_HIP(c, hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
-        }
-        KM_HIP(c, hipEventRecord(c->ev_tail, c->stream));
-        KM_HIP(c, hipStreamWaitEvent(c->d2h_stream, c->ev_tail, 0));
-        out_stream = c->d2h_stream;
-    }
-    slot->sunk_valid = false;
-    if (T.sink) {
-        const size_t pitch = T.sink_pitch ? T.sink_pitch : ob;
-        KM_HIP(c, hipMemcpy2DAsync(T.sink, pitch, T.d_out, ob_al, ob, (size_t)n, hipMemcpyDeviceToDevice, out_stream));
-        if (!slot->sunk) KM_HIP(c, hipEventCreateWithFlags(&slot->sunk, hipEventDisableTiming));
-        KM_HIP(c, hipEventRecord(slot->sunk, out_stream));
-        slot->sunk_valid = true;
-    }
-    KM_HIP(c, hipMemcpy2DAsync(slot->host, ob, T.d_out, ob_al, ob, (size_t)n, hipMemcpyDeviceToHost, out_stream));
-    KM_HIP(c, hipEventRecord(slot->done, out_stream));
+    if (!T.piped && (rc = km_block_stream(c))) return rc;
+    if ((rc = frame_blocks_out(c, slot, T.d_out, T.ob, T.ob_al, n, T.sink, T.sink_pitch, T.piped ? c->chain_stream : c->d2h_stream))) return rc;
     if (T.piped) {      // the lane's next submission may rewrite its scalars / points / frame buffers once this chain (copies included) is through
-        KM_HIP(c, hipEventRecord(c->ev_lane[T.lane][EV_F_DONE], c->chain_stream));
+        if ((rc = km_record(c, ev[EV_F_DONE], c->chain_stream))) return rc;
         c->lane_f_recorded[T.lane] = true;
+        c->frame_copy = nullptr;                        // (every lane owns its frame buffer and waits for EV_F_DONE)
     }
-    c->frame_copy = T.piped ? nullptr : slot->done;     // (pipelined: every lane owns its frame buffer and waits for EV_F_DONE)
-    slot->bytes = ob * n;
     slot->deferred.store(0, std::memory_order_release);
+    return KM_OK;
+}
+
+// whatever follows on `s` may reuse a lane's workspace: behind the lane's frame stage and copies
+static int wait_lane_done(km_ctx *c, int l, hipStream_t s) { return s && c->lane_f_recorded[l] ? km_wait(c, s, c->ev_lane[l][EV_F_DONE]) : KM_OK; }
+// ... the main and the second stream behind both lanes
+static int join_lanes(km_ctx *c)
+{
+    for (int l = 0; l < 2; l++) {
+        int rc;
+        if ((rc = wait_lane_done(c, l, c->stream)) || (rc = wait_lane_done(c, l, c->aux_stream))) return rc;
+        c->lane_f_recorded[l] = false;
+    }
     return KM_OK;
 }
 
@@ -164,14 +155,7 @@ extern "C++" int km_units_flush(km_ctx *c, bool join)
     std::lock_guard<std::mutex> lk(*c->enqueue_mu);
     if (c->utail->armed) KM_HIP(c, hipSetDevice(c->device));      // (the fallback of km_frame_wait runs on a thread of the caller's)
     const int rc = units_flush_locked(c);
-    if (rc || !join) return rc;
-    for (int l = 0; l < 2; l++)
-        if (c->lane_f_recorded[l]) {
-            KM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_lane[l][EV_F_DONE], 0));
-            if (c->aux_stream) KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_lane[l][EV_F_DONE], 0));
-            c->lane_f_recorded[l] = false;
-        }
-    return KM_OK;
+    return rc || !join ? rc : join_lanes(c);
 }
 
 extern "C" {
@@ -198,9 +182,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     if (cap <= 0 || prm->max_corners <= 0 || cap < prm->max_corners) return km_fail(c, KM_E_ARG, "klt_units_frame_submit: capacity %d / maxCorners %d", cap, prm->max_corners);
     // the batch form IS the synchronisation-free corner path: whatever that path does not cover goes unit by unit (no message).  Every
     // coverage check sits HERE, in front of the first launch: a refused batch has queued nothing
-    if (!(prm->min_distance >= 1) || !c->opt_speculative || !c->fused_eig || c->opt_key_cap || c->opt_stage_cap || c->opt_topk_factor || c->opt_select_first ||
-        prm->max_level != 1 || cap > 32768)
-        return KM_E_UNSUPPORTED;
+    if (!spec_path_covers(c, prm) || prm->max_level != 1 || cap > 32768) return KM_E_UNSUPPORTED;
     if (prm->block_size < 1 || prm->block_size > 15 || (prm->block_size & 1) == 0 || !c->opt_eig3 || !c->opt_lk2 || prm->win_size <= 2 || prm->win_size > 40)
         return KM_E_UNSUPPORTED;
     if (!km_units_ksize_supported(prm->ksize_ref) || !km_units_ksize_supported(prm->ksize_mon)) return KM_E_UNSUPPORTED;
@@ -227,15 +209,8 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     std::lock_guard<std::mutex> enqueue_lock(*c->enqueue_mu);
     km_units_tail &old_tail = *c->utail;
     const bool piped = c->opt_units_pipeline && dtype != KM_U8;
-    if (!piped) {      // (a pipelined submission was the previous one: its tail first, and this one behind both lanes' chains)
-        if ((rc = units_flush_locked(c))) return rc;
-        for (int l = 0; l < 2; l++)
-            if (c->lane_f_recorded[l]) {
-                KM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_lane[l][EV_F_DONE], 0));
-                if (c->aux_stream) KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_lane[l][EV_F_DONE], 0));
-                c->lane_f_recorded[l] = false;
-            }
-    }
+    // (a pipelined submission was the previous one: its tail first, and this one behind both lanes' chains)
+    if (!piped && ((rc = units_flush_locked(c)) || (rc = join_lanes(c)))) return rc;
     const int k = c->fslot_next;
     km_frame_slot *slot = &c->fslot[k];
     if (slot->pending.load(std::memory_order_acquire)) {   // never waited for: its block is about to be overwritten
@@ -245,20 +220,16 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     }
     const int lane = piped ? (old_tail.armed ? 1 - old_tail.lane : 0) : 0;
     hipStream_t const main_stream = c->stream;
-    struct guard_t { km_ctx *c; hipStream_t s; ~guard_t() { c->ev_cur = 0; c->stream = s; c->lane = 0; c->in_units_submit = false; } } guard{c, main_stream};
+    units_scope scope(c, false);
     c->ev_cur = 1 + k;
     c->in_units_submit = true;
     if ((rc = begin_call(c, RESET_KLT))) return rc;
     memset(&c->stats, 0, sizeof c->stats);
     c->evs_used[c->ev_cur][ST_ZNCC] = false; c->evs_used[c->ev_cur][ST_MI] = false;
     c->lane = lane;
-    if (!c->aux_stream) {
-        KM_HIP(c, hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, 0));
-        KM_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        KM_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    }
+    if ((rc = km_aux_stream(c))) return rc;
     for (int i = 0; i < KM_LANE_EVENTS; i++)
-        if (!c->ev_lane[lane][i]) KM_HIP(c, hipEventCreateWithFlags(&c->ev_lane[lane][i], hipEventDisableTiming));
+        if ((rc = km_event(c, &c->ev_lane[lane][i]))) return rc;
     if (piped && !c->chain_stream) KM_HIP(c, hipStreamCreateWithFlags(&c->chain_stream, hipStreamNonBlocking));
     hipEvent_t *ev = c->ev_lane[lane];
 
@@ -304,15 +275,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         A.H[1] = B.H[1] = (U.H[u] + 1) / 2; A.W[1] = B.W[1] = (U.W[u] + 1) / 2;
         A.levels = B.levels = 1;
     }
-    const size_t pitch = c->frame_sink_pitch ? c->frame_sink_pitch : ob;
-    if (c->frame_sink && (pitch < ob || c->frame_sink_cap < pitch * (size_t)(n - 1) + ob))
-        return km_fail(c, KM_E_ARG, "frame sink of %zu bytes (pitch %zu) is smaller than %d frame blocks of %zu bytes", c->frame_sink_cap, pitch, n, ob);
-    if (slot->cap < ob * n) {
-        if (slot->host) KM_HIP(c, hipHostFree(slot->host));
-        slot->host = nullptr; slot->cap = 0;
-        KM_HIP(c, hipHostMalloc(&slot->host, ob * n + ob / 8, hipHostMallocDefault));
-        slot->cap = ob * n + ob / 8;
-    }
+    if ((rc = frame_sink_check(c, c->frame_sink_pitch, n, ob)) || (rc = frame_slot_reserve(c, slot, ob * n))) return rc;
     // The lane's previous submission must have left its frame stage before its scalars, points and frame buffers are reset - the scalar
     // blocks' reset and the LK table's small copy ("setup").  Unpipelined: here, on the main stream.  Pipelined: on the second stream
     // BEHIND the min / max (below): the min / max touches none of those buffers, and with the wait in front of it the Laplacians of this
@@ -322,16 +285,12 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     const int n_max = prm->max_corners < cap ? prm->max_corners : cap;
     const bool setup_on_aux = piped && dtype != KM_U8;
     auto setup = [&]() -> int {
-        int r = hipMemsetAsync(sc, 0, sc_stride * n, c->stream) == hipSuccess ? KM_OK : km_fail(c, KM_E_HIP, "hipMemsetAsync(scalars)");
-        if (r == KM_OK) r = kl_units_prepare(c, U, n_max, prm->win_size, prm->max_count, prm->epsilon);
-        return r;
+        KM_HIP(c, hipMemsetAsync(sc, 0, sc_stride * n, c->stream));
+        return kl_units_prepare(c, U, n_max, prm->win_size, prm->max_count, prm->epsilon);
     };
     if (!setup_on_aux) {
-        if (c->lane_f_recorded[lane]) {
-            KM_HIP(c, hipStreamWaitEvent(c->stream, ev[EV_F_DONE], 0));
-            KM_HIP(c, hipStreamWaitEvent(c->aux_stream, ev[EV_F_DONE], 0));
-            c->lane_f_recorded[lane] = false;
-        }
+        if ((rc = wait_lane_done(c, lane, c->stream)) || (rc = wait_lane_done(c, lane, c->aux_stream))) return rc;
+        c->lane_f_recorded[lane] = false;
         if ((rc = setup())) return rc;
     }
 
@@ -344,24 +303,21 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
             double *slot_mm = (double *)km_ws(c, WS_UNITS_MM, (size_t)4 * KM_UNITS_MAX * sizeof(double));
             if (!slot_mm) return KM_E_NOMEM;
             for (int u = 0; u < n; u++) { out[u] = slot_mm + 4 * u; U.mm[u] = out[u]; }
-            if (!piped) KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_lk_start, 0));
-            c->stream = c->aux_stream;
+            if (!piped && (rc = km_wait(c, c->aux_stream, c->ev_lk_start))) return rc;
             {
-                km_stage_timer t(c, ST_MINMAX);
-                rc = kd_minmax_units(c, U, out, WS_MM_PARTIAL);
-            }
-            if (rc == KM_OK && hipEventRecord(ev[EV_MM], c->aux_stream) != hipSuccess) rc = km_fail(c, KM_E_HIP, "hipEventRecord(min/max)");
-            if (rc == KM_OK && setup_on_aux) {      // the setup, behind the min / max and behind the lane's previous frame stage
-                if (c->lane_f_recorded[lane]) {
-                    if (hipStreamWaitEvent(c->aux_stream, ev[EV_F_DONE], 0) != hipSuccess) rc = km_fail(c, KM_E_HIP, "hipStreamWaitEvent(lane)");
-                    c->lane_f_recorded[lane] = false;
+                km_on_stream on(c, c->aux_stream);
+                {
+                    km_stage_timer t(c, ST_MINMAX);
+                    if ((rc = kd_minmax_units(c, U, out, WS_MM_PARTIAL))) return rc;
                 }
-                if (rc == KM_OK) rc = setup();
-                if (rc == KM_OK && hipEventRecord(ev[EV_SETUP], c->aux_stream) != hipSuccess) rc = km_fail(c, KM_E_HIP, "hipEventRecord(setup)");
+                if ((rc = km_record(c, ev[EV_MM], c->aux_stream))) return rc;
+                if (setup_on_aux) {      // the setup, behind the min / max and behind the lane's previous frame stage
+                    rc = wait_lane_done(c, lane, c->aux_stream);
+                    c->lane_f_recorded[lane] = false;
+                    if (rc || (rc = setup()) || (rc = km_record(c, ev[EV_SETUP], c->aux_stream))) return rc;
+                }
             }
-            c->stream = main_stream;
-            if (rc) return rc;
-            KM_HIP(c, hipStreamWaitEvent(c->stream, ev[EV_MM], 0));
+            if ((rc = km_wait(c, c->stream, ev[EV_MM]))) return rc;
             c->stats.path_flags |= KM_PATH_MM_EARLY;
         } else {
             for (int u = 0; u < n; u++) out[u] = U.sc[u]->mm;
@@ -377,23 +333,19 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     }
     // ---- the valid-pixel sums and the pyramids (they depend on the Laplacians only) on the second stream
     {
-        KM_HIP(c, hipEventRecord(ev[EV_FORK], c->stream));
-        KM_HIP(c, hipStreamWaitEvent(c->aux_stream, ev[EV_FORK], 0));
-        c->stream = c->aux_stream;
-        rc = kd_valid_sum_units(c, vjob);
-        if (rc == KM_OK) {
+        if ((rc = km_record(c, ev[EV_FORK], c->stream)) || (rc = km_wait(c, c->aux_stream, ev[EV_FORK]))) return rc;
+        km_on_stream on(c, c->aux_stream);
+        if ((rc = kd_valid_sum_units(c, vjob))) return rc;
+        {
             km_stage_timer tp(c, ST_PYRAMID);
-            rc = kd_pyrdown_units(c, U, 1);
+            if ((rc = kd_pyrdown_units(c, U, 1))) return rc;
         }
-        if (rc == KM_OK && hipEventRecord(ev[EV_JOIN], c->aux_stream) != hipSuccess) rc = km_fail(c, KM_E_HIP, "hipEventRecord(join)");
-        c->stream = main_stream;
-        if (rc) return rc;
+        if ((rc = km_record(c, ev[EV_JOIN], c->aux_stream))) return rc;
     }
     // ---- pipelined: the PREVIOUS submission's LK goes here, between this one's Laplacians and its eigenvalue pass (its frame stage and
     // scores follow on the chain stream, beside this submission's eigenvalue pass)
     if (piped && (rc = units_flush_locked(c))) { (void)hipStreamWaitEvent(c->stream, ev[EV_JOIN], 0); return rc; }
-    c->lane = lane; c->ev_cur = 1 + k;
-    if (setup_on_aux) KM_HIP(c, hipStreamWaitEvent(c->stream, ev[EV_SETUP], 0));     // (scalars reset, the lane's previous frame stage through)
+    if (setup_on_aux && (rc = km_wait(c, c->stream, ev[EV_SETUP]))) return rc;      // (scalars reset, the lane's previous frame stage through)
     // ---- K3 + K4 fused
     {
         km_stage_timer t(c, ST_EIGEN);
@@ -401,31 +353,25 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     }
     if (rc) { (void)hipStreamWaitEvent(c->stream, ev[EV_JOIN], 0); return rc; }
     // ---- K5: ranking + greedy selection, every unit's chain side by side (pipelined: on the chain stream, beside the next submission's Laplacians)
-    if (piped) {
-        KM_HIP(c, hipEventRecord(ev[EV_E_DONE], main_stream));
-        KM_HIP(c, hipStreamWaitEvent(c->chain_stream, ev[EV_E_DONE], 0));
-        c->stream = c->chain_stream;
-    }
+    if (piped && ((rc = km_record(c, ev[EV_E_DONE], main_stream)) || (rc = km_wait(c, c->chain_stream, ev[EV_E_DONE])))) return rc;
     {
-        km_stage_timer t(c, ST_SELECT);
-        rc = kf_rank_select_units(c, U, prm->max_corners, prm->quality_level, prm->min_distance, cap);
-    }
-    if (piped) {
-        if (rc == KM_OK && hipEventRecord(ev[EV_C_DONE], c->chain_stream) != hipSuccess) rc = km_fail(c, KM_E_HIP, "hipEventRecord(chain)");
-        c->stream = main_stream;
+        km_on_stream on(c, piped ? c->chain_stream : main_stream);
+        {
+            km_stage_timer t(c, ST_SELECT);
+            rc = kf_rank_select_units(c, U, prm->max_corners, prm->quality_level, prm->min_distance, cap);
+        }
+        if (piped && rc == KM_OK) rc = km_record(c, ev[EV_C_DONE], c->chain_stream);
     }
     if (rc) { (void)hipStreamWaitEvent(c->stream, ev[EV_JOIN], 0); return rc; }
-    c->spec_used = true;
     // ---- the tail: LK, frame stage, scores, copy-out - now, or with the next submission
     km_units_tail &T = *c->utail;
     T.lane = lane; T.slot = k; T.U = U; T.prm = *prm; T.n = n; T.n_max = n_max; T.cap = cap; T.dtype = dtype;
     T.with_zncc = with_zncc; T.with_mi = with_mi; T.piped = piped; T.zncc_threshold = zncc_threshold; T.profile_skip = c->profile_skip;
     T.fb = fb; T.ob = ob; T.ob_al = ob_al; T.d_out = d_out;
-    T.sink = c->frame_sink; T.sink_cap = c->frame_sink_cap; T.sink_pitch = c->frame_sink_pitch;
+    T.sink = c->frame_sink; T.sink_pitch = c->frame_sink_pitch;
     slot->sunk_valid = false;
     if (piped) {
         T.armed = true;
-        if (!slot->done) KM_HIP(c, hipEventCreateWithFlags(&slot->done, hipEventDisableTiming));
         slot->deferred.store(1, std::memory_order_release);
     } else if ((rc = units_tail(c, T)))
         return rc;

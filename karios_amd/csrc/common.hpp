@@ -233,7 +233,6 @@ struct km_ctx {
     hipEvent_t ev_tail = nullptr, frame_copy = nullptr;   // frame_copy: completion of the last block copy (WS_FRAME must not be rewritten before)
     hipEvent_t ev_lk_start = nullptr, ev_mm = nullptr;   // early min/max: the next unit's K1 starts on aux_stream when this unit's LK launch starts
     bool lk_start_valid = false, lk_start_prev = false;   //   ... ev_lk_start was recorded by the tile call that directly preceded this one
-    bool mm_early_allowed = false;       //   ... the running entry point reads no min / max statistics back (km_klt_tile_frame_submit)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // chain of small corner-selection kernels on `stream`, joined before LK
     bool copy_pending = false;           // uploads queued since the compute stream last waited for the whole copy stream
     std::vector<hipEvent_t> upload_marks;   // km_upload_mark tickets: events on the copy stream, nullptr = ticket consumed
@@ -282,12 +281,6 @@ struct km_ctx {
     int opt_profile_stage = -1;    // "profile_stage": with profiling on, time only this stage (-1: every stage; each timed span costs two events = two pipeline drains)
     int opt_stash_cap = 0;         // "stash_cap": kept keys a workgroup of the scatter launch stashes in LDS (small values force its second read of the keys)
     int opt_spec_flag = 0;         // "spec_flag": KM_FLAG_* bits raised artificially by the speculative path (tests of the repeat logic)
-    const unsigned *eig_partial = nullptr;   // speculative path: per-wave maxima the fused eigenvalue pass left for the ranking's first launch
-    unsigned eig_npartial = 0;               //   (the one-workgroup reduction launch in between is skipped), consumed by kf_rank
-    bool eig_defer_max = false;
-    bool spec_used = false;        // the running call went through the speculative corner path
-    unsigned spec_flags = 0;       // sc->flags of the speculative run, once read back
-    bool spec_allowed = false;     // set by the entry points that check sc->flags with their result (and cleared for the repeat)
     bool opt_roctx = false;        // "roctx": roctx ranges around the stages
     bool opt_fft_cross_fused = true;   // "fft_cross": the cross-power step fused into the first inverse pass's row load (61 M rows)
     bool opt_fft_herm = true;      // "fft_herm" 1 (default): the inverse transform of the float32 phase correlation works on the Hermitian half plane (rows of length 61 M on both sides)
@@ -313,11 +306,6 @@ struct km_ctx {
     km_klt_stats stats;
     int phase_path = 0;            // last km_phase_shift*: 1 = float32 hand-written FFT, 2 = double precision (k_fft64.hip)
     double phase_margin = 0.0;     // (max - second largest) / max of |cc| seen by the float32 path
-    bool defer_valid_sum = false;  // set around the Laplacian pass of a unit on the sync-free path: the valid-pixel sum becomes a job for the second stream
-    bool valid_job_pending = false;
-    const unsigned *valid_job_partial = nullptr;
-    unsigned valid_job_n = 0;
-    unsigned long long *valid_job_out = nullptr;
     bool opt_eig3_count = false;   // (KM_DEV) "eig3_count": the fused 8-px eigenvalue pass counts the (wave, row, pixel slot) triples a bound could skip
     bool opt_prep_plain = false;   // (KM_DEV) "prep_hist_plain": the radix select adds one LDS atomic per pixel instead of one per run of equal bins (A/B of DESIGN 12)
     bool opt_defer_valid = true;   // "defer_valid" 0: the sum stays behind the Laplacian pass on the main stream
@@ -483,7 +471,13 @@ int kd_auto_mask(km_ctx *c, const void *d_mon, const void *d_ref, int dtype, int
                  ptrdiff_t stride_mon, ptrdiff_t stride_ref, const double *nodata_mon,
                  const double *nodata_ref, uint8_t *d_mask, unsigned long long *d_valid);
 int kd_count_nonzero(km_ctx *c, const uint8_t *d_mask, size_t n, unsigned long long *d_valid);
-int kd_run_valid_sum(km_ctx *c);
+// the sum of the per-item valid-pixel counts of kd_stretch_laplacian_pair, left to the caller (partial == nullptr: nothing pending)
+struct km_valid_job {
+    const unsigned *partial = nullptr;
+    unsigned n = 0;
+    unsigned long long *out = nullptr;
+};
+int kd_run_valid_sum(km_ctx *c, km_valid_job *job);   // launches a pending sum on c->stream and clears the job
 int kd_laplacian_u8(km_ctx *c, const uint8_t *d_src, int H, int W, int ksize, uint8_t *d_dst);
 // fused: raw ref+mon -> uint8 stretch -> Laplacians (+ auto mask when d_mask_out != null)
 int kd_stretch_laplacian_pair(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H,
@@ -491,7 +485,7 @@ int kd_stretch_laplacian_pair(km_ctx *c, const void *d_ref, const void *d_mon, i
                               const double *d_mm /* [4] */, int ksize_ref, int ksize_mon,
                               int invert_mon, const double *nodata_ref, const double *nodata_mon,
                               uint8_t *d_lap_ref, uint8_t *d_lap_mon, uint8_t *d_mask_out,
-                              unsigned long long *d_valid);
+                              unsigned long long *d_valid, km_valid_job *defer = nullptr);   // defer: the sum into d_valid becomes the caller's job (null: summed now)
 int kd_min_eigen(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block,
                  float *d_eig, unsigned int *d_max_key);
 // k_frame.hip: DN-value filter of the key points (core.py:650-737)
@@ -501,11 +495,18 @@ int kf_dn_keep(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H
                const float *d_y0, int n, const double *d_no_values, int n_no, const double *ref_nd, const double *mon_nd, uint8_t *d_keep);
 // k_eig2.hip: minimum-eigenvalue map + masked maximum, 2 pixels per lane (KM_E_UNSUPPORTED when the case is not covered)
 int k2_min_eigen(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, float *d_eig, unsigned *d_max_key);
+// per-wave maxima the fused eigenvalue pass leaves for the ranking's first launch (kf_rank), which then reduces them itself: the
+// one-workgroup reduction launch in between is skipped.  partial == nullptr: sc->max_eig_key already holds the maximum
+struct km_eig_partials {
+    const unsigned *partial = nullptr;
+    unsigned n = 0;
+};
+// partials != nullptr: leave the maximum to the ranking where the 8-px kernel ran (the 2-px kernel always reduces its own: *partials stays empty)
 int k2_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, double quality, km_scalars *sc,
-                      unsigned long long *d_keys, size_t cap, bool rezero);
+                      unsigned long long *d_keys, size_t cap, bool rezero, km_eig_partials *partials = nullptr);
 // k_eig3.hip
 int k3_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, double quality, km_scalars *sc,
-                      unsigned long long *d_keys, size_t cap);
+                      unsigned long long *d_keys, size_t cap, km_eig_partials *partials = nullptr);
 int kd_candidates(km_ctx *c, const float *d_eig, const uint8_t *d_mask, int H, int W,
                   double quality, km_scalars *d_sc, unsigned long long *d_keys, size_t cap, bool rezero);
 int kd_pyrdown_u8(km_ctx *c, const uint8_t *d_src, int H, int W, uint8_t *d_dst);
@@ -525,7 +526,7 @@ int ks_topk_prefilter(km_ctx *c, const unsigned long long *d_keys, size_t cap_ke
 // k_select2.hip: ranking + selection without host synchronisation or library sorts (flags instead of retries)
 size_t kf_kept_capacity(int max_corners);
 int kf_rank(km_ctx *c, const unsigned long long *d_keys, size_t cap_keys, int H, int W, int max_corners, double quality, double min_distance,
-            km_scalars *sc);
+            km_scalars *sc, km_eig_partials partials);
 int kf_select(km_ctx *c, int H, int W, int max_corners, double min_distance, float *d_xy, int cap, km_scalars *sc);
 // k_lk.hip
 struct km_pyr {

@@ -1264,7 +1264,7 @@ static int lapm_launch(km_ctx *c, int R, const lapm_units_args &A, const lap_coe
 template <typename T, bool MASK>
 static int launch_lap_march(km_ctx *c, int R, const T *a, const T *b, int H, int W, ptrdiff_t sa, ptrdiff_t sb, const double *mm,
                             const lap_coef &cf, int invert1, const nodata_t &nd, uint8_t *oa, uint8_t *ob,
-                            uint8_t *mask, unsigned long long *valid_out)
+                            uint8_t *mask, unsigned long long *valid_out, km_valid_job *defer)
 {
     lapm_units_args A;
     A.n = 1;
@@ -1280,10 +1280,10 @@ static int launch_lap_march(km_ctx *c, int R, const T *a, const T *b, int H, int
     }
     if (int rc = lapm_launch<T, MASK>(c, R, A, cf, invert1, nd)) return rc;
     if (MASK) {
-        if (c->defer_valid_sum) {
+        if (defer) {
             // the count of valid pixels is only read at the end of the unit (frame header, statistics): its sum leaves the critical
             // path - klt_track_dev launches it on the second stream in front of the pyramids (kd_run_valid_sum)
-            c->valid_job_partial = A.valid[0]; c->valid_job_n = nitems; c->valid_job_out = valid_out; c->valid_job_pending = true;
+            defer->partial = A.valid[0]; defer->n = nitems; defer->out = valid_out;
         } else {
             sum_u32_kernel<<<1, 1024, 0, c->stream>>>(A.valid[0], nitems, valid_out);
             KM_LAUNCH_CHECK(c);
@@ -1294,11 +1294,11 @@ static int launch_lap_march(km_ctx *c, int R, const T *a, const T *b, int H, int
 
 // the deferred sum of launch_lap_march, on whatever stream c->stream is at the moment (one workgroup of 1024 threads: the single
 // wavefront of kd_valid_sum_units took 35 instead of 5 us over the ~3000 counts of a 10980^2 tile)
-int kd_run_valid_sum(km_ctx *c)
+int kd_run_valid_sum(km_ctx *c, km_valid_job *job)
 {
-    if (!c->valid_job_pending) return KM_OK;
-    c->valid_job_pending = false;
-    sum_u32_kernel<<<1, 1024, 0, c->stream>>>(c->valid_job_partial, c->valid_job_n, c->valid_job_out);
+    if (!job->partial) return KM_OK;
+    sum_u32_kernel<<<1, 1024, 0, c->stream>>>(job->partial, job->n, job->out);
+    *job = km_valid_job();
     KM_LAUNCH_CHECK(c);
     return KM_OK;
 }
@@ -1455,7 +1455,7 @@ int kd_laplacian_u8(km_ctx *c, const uint8_t *d_src, int H, int W, int ksize, ui
 int kd_stretch_laplacian_pair(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref,
                               ptrdiff_t smon, const double *d_mm, int ksize_ref, int ksize_mon, int invert_mon,
                               const double *nodata_ref, const double *nodata_mon, uint8_t *d_lap_ref, uint8_t *d_lap_mon,
-                              uint8_t *d_mask_out, unsigned long long *d_valid)
+                              uint8_t *d_mask_out, unsigned long long *d_valid, km_valid_job *defer)
 {
     lap_coef cf;
     const int R = lap_radius(ksize_ref) > lap_radius(ksize_mon) ? lap_radius(ksize_ref) : lap_radius(ksize_mon);
@@ -1471,9 +1471,9 @@ int kd_stretch_laplacian_pair(km_ctx *c, const void *d_ref, const void *d_mon, i
     if ((R <= 4 && W >= 8 && H >= 8) || march5) {
 #define KM_PAIRM(T)                                                                                                              \
     (d_mask_out ? launch_lap_march<T, true>(c, R, (const T *)d_ref, (const T *)d_mon, H, W, sref, smon, d_mm, cf, invert_mon, nd, \
-                                            d_lap_ref, d_lap_mon, d_mask_out, d_valid)                                           \
+                                            d_lap_ref, d_lap_mon, d_mask_out, d_valid, defer)                                    \
                 : launch_lap_march<T, false>(c, R, (const T *)d_ref, (const T *)d_mon, H, W, sref, smon, d_mm, cf, invert_mon, nd, \
-                                             d_lap_ref, d_lap_mon, nullptr, nullptr))
+                                             d_lap_ref, d_lap_mon, nullptr, nullptr, nullptr))
         switch (dtype) {
         case KM_U8: return KM_PAIRM(uint8_t);
         case KM_U16: return KM_PAIRM(uint16_t);

@@ -99,7 +99,7 @@ int k2_min_eigen(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, 
 // Fused minimum-eigenvalue + candidate pass, 2 pixels per lane (no eig map).  Expects sc->run_max_key, sc->pad0 and
 // sc->shard_cnt[] zeroed (`rezero` does it).  KM_E_UNSUPPORTED (no message) when the case is not covered.
 int k2_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, double quality, km_scalars *sc,
-                      unsigned long long *d_keys, size_t cap, bool rezero)
+                      unsigned long long *d_keys, size_t cap, bool rezero, km_eig_partials *partials)
 {
     if (block < 1 || block > 15) return KM_E_UNSUPPORTED;
     if (!(W >= 2 * block + 8 && H >= 2 * block + 8)) return KM_E_UNSUPPORTED;
@@ -108,7 +108,7 @@ int k2_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, in
         KM_HIP(c, hipMemsetAsync(sc->run_max_shard, 0, sizeof sc->run_max_shard, c->stream));
     }
     if (c->opt_eig3) {   // wide images: 8 pixels per lane (k_eig3.hip), the 2-px item only on the two border strips
-        const int r = k3_eig_candidates(c, d_src, d_mask, H, W, block, quality, sc, d_keys, cap);
+        const int r = k3_eig_candidates(c, d_src, d_mask, H, W, block, quality, sc, d_keys, cap, partials);
         if (r != KM_E_UNSUPPORTED) return r;
     }
     const double scale = 1.0 / (4.0 * (double)block * 255.0), s2 = scale * scale;

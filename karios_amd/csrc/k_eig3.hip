@@ -591,7 +591,7 @@ int k3_eig_candidates_units(km_ctx *c, km_units &U, int block, double quality)
 // Fused minimum-eigenvalue + candidate pass, 8 pixels per lane.  Same contract as k2_eig_candidates (k_eig2.hip), which
 // forwards here; KM_E_UNSUPPORTED (no message) when the case is not covered (narrow images, even block sizes).
 int k3_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, double quality, km_scalars *sc,
-                      unsigned long long *d_keys, size_t cap)
+                      unsigned long long *d_keys, size_t cap, km_eig_partials *partials)
 {
     if (block < 1 || block > 15 || (block & 1) == 0) return KM_E_UNSUPPORTED;
     if (W < 512 || H < 2 * block + 8) return KM_E_UNSUPPORTED;
@@ -607,8 +607,8 @@ int k3_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, in
     default: return KM_E_UNSUPPORTED;
     }
     if (rc) return rc;
-    if (c->eig_defer_max) {          // speculative corner path: kf_rank's first launch takes the maximum of the partials itself
-        c->eig_partial = U.eig_partial[0]; c->eig_npartial = U.eig_npartial[0];
+    if (partials) {                  // speculative corner path: kf_rank's first launch takes the maximum of the partials itself
+        partials->partial = U.eig_partial[0]; partials->n = U.eig_npartial[0];
         return KM_OK;
     }
     eig3_max_kernel<<<1, 1024, 0, c->stream>>>(U.eig_partial[0], U.eig_npartial[0], &sc->max_eig_key);

@@ -604,14 +604,14 @@ static int kf_select_launch(km_ctx *c, const kf_units_args &A, int n, int max_co
 // Ranking of the keys the fused kernel emitted: (maximum, histogram, cut) -> (scatter by value bin + grid cells).  Two launches;
 // everything is enqueued, nothing is read back.  Requires max_corners > 0, min_distance >= 1 and a scalar block zeroed at the
 // start of the call.
-int kf_rank(km_ctx *c, const unsigned long long *d_keys, size_t cap_keys, int H, int W, int max_corners, double quality, double min_distance, km_scalars *sc)
+int kf_rank(km_ctx *c, const unsigned long long *d_keys, size_t cap_keys, int H, int W, int max_corners, double quality, double min_distance, km_scalars *sc,
+            km_eig_partials partials)
 {
     kf_units_args A;
     kf_sizes z;
     const int rc = kf_layout_units(c, 1, &H, &W, max_corners, min_distance, &A, &z);
     if (rc) return rc;
-    A.u[0].keys = d_keys; A.u[0].sc = sc; A.u[0].max_partial = c->eig_partial; A.u[0].n_partial = c->eig_npartial; A.u[0].out_xy = nullptr;
-    c->eig_partial = nullptr; c->eig_npartial = 0;
+    A.u[0].keys = d_keys; A.u[0].sc = sc; A.u[0].max_partial = partials.partial; A.u[0].n_partial = partials.n; A.u[0].out_xy = nullptr;
     return kf_rank_launch(c, A, 1, cap_keys, max_corners, quality, z);
 }
 

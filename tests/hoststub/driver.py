@@ -3,12 +3,14 @@
 Loads tests/hoststub/_build/libkarios_host_asan.so - every api*.hip + staging.hip compiled with g++ -fsanitize=address,undefined
 against the stand-in HIP layer - through the SAME ctypes signatures the product uses (karios_amd._lib.SIGNATURES) and walks the host-side
 bookkeeping: argument validation of every family of entry points, workspace slots (regrow, allocation failure), the page-locked
-staging ring and landing arena (sizes around the chunk boundaries, strided sources), upload tickets, the three-slot frame ring.
+staging ring and landing arena (sizes around the chunk boundaries, strided sources), upload tickets, the three-slot frame ring,
+a failure of every device allocation in turn inside the two submit calls.
 The entry points of the align step have a driver of their own, driver_align.py.  Prints 'HOST-ASAN OK' at the end; any sanitizer report aborts the process.
 """
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -331,6 +333,76 @@ for n_side, cols in ((10980, 0), (10980, 1), (1, 0), (7, 1), (3721, 0), (10007, 
 assert lib.km_phase_plan(0, 0, lv, 16, None, None, None) < 0 and lib.km_phase_plan(10980, 0, lv, 1, None, None, None) < 0
 rc_ = (C.c_double * 2)()
 ok(lib.km_phase_shift(ctx, P(ref), P(mon), 1, H, W, W, W, rc_), "phase_shift")
+
+# ---- allocation failure at EVERY hipMalloc of the two submissions that switch streams: on a fresh context the k-th allocation inside the
+# call fails, k = 0, 1, 2 ... up to the first k at which the call succeeds.  Every failure is KM_E_NOMEM, leaves the stream, lane and
+# event set as it found them (the same call then succeeds and delivers the block of a context that never saw a failure, and another
+# entry point runs on the context) and leaks nothing (the counters at the end).  The rasters belong to the main context: device memory
+# is the device's, not the context's.
+def sweep(what, submit, bytes_want, options=()):
+    def fresh():
+        c2 = C.c_void_p()
+        ok(lib.km_ctx_create(0, C.byref(c2)), "ctx_create (sweep)")
+        for name, value in options:
+            assert lib.km_set_option(c2, name, value) == 0
+        return c2
+
+    def block_of(c2, t):
+        b, nbytes = C.c_void_p(), C.c_size_t()
+        assert lib.km_frame_wait(c2, t, C.byref(b), C.byref(nbytes)) == 0 and nbytes.value == bytes_want, (what, nbytes.value)
+        return C.string_at(b, nbytes.value)
+
+    c2 = fresh()
+    t = C.c_int(-1)
+    assert submit(c2, t) == 0, what
+    want = block_of(c2, t.value)
+    assert lib.km_ctx_destroy(c2) == 0
+    small = rng.integers(0, 256, (9, 11), dtype=np.uint8)
+    for k in range(65):
+        assert k < 64, f"{what}: still failing with the 64th allocation"
+        c2 = fresh()
+        lib.stub_fail_malloc_after(k)
+        rc = submit(c2, t)
+        lib.stub_fail_malloc_after(-1)
+        if rc != 0:
+            assert rc == KM_E_NOMEM and b"hipMalloc" in lib.km_last_error(c2), (what, k, rc, lib.km_last_error(c2))
+            assert submit(c2, t) == 0, (what, k, lib.km_last_error(c2))
+        assert block_of(c2, t.value) == want, f"{what}: block after a failure of allocation {k}"
+        out = np.zeros_like(small)
+        assert lib.km_laplacian_u8(c2, P(small), 9, 11, 7, P(out)) == 0 and np.array_equal(out, small), (what, k)
+        assert lib.km_ctx_destroy(c2) == 0
+        if rc == 0:
+            return k
+    raise AssertionError("unreachable")
+
+
+t_sweep = time.perf_counter()
+steps = [sweep("tile submit", lambda c2, t: lib.km_klt_tile_frame_submit(c2, dr, dm, 1, H, W, W, W, None, 0, None, None, C.byref(prm), 3.0, 5.0, dr, dm, H, W, W, W, 0.4,
+                                                                         cap, C.byref(t)), blk_bytes)]
+Hs, Ws = 64, 640                                   # two units of 512 x 64 and 640 x 48: the smallest widths the batch form accepts
+mon2 = rng.integers(1, 9000, (Hs, Ws)).astype(np.uint16)
+ref2 = rng.integers(1, 9000, (Hs, Ws)).astype(np.uint16)
+dm2, dr2 = C.c_void_p(), C.c_void_p()
+for dptr, a in ((dm2, mon2), (dr2, ref2)):
+    ok(lib.km_dev_alloc(ctx, a.nbytes, C.byref(dptr)), "dev_alloc")
+    ok(lib.km_h2d(ctx, dptr, P(a), a.nbytes), "h2d")
+units2 = (KmUnit * 2)()
+for u, (bx, by, bw, bh) in zip(units2, [(64, 0, 512, 64), (0, 8, 640, 48)]):
+    u.d_ref, u.d_mon, u.sref, u.smon, u.H, u.W = dr2.value + (by * Ws + bx) * es, dm2.value + (by * Ws + bx) * es, Ws, Ws, bh, bw
+    u.d_ref_full, u.d_mon_full, u.sref_f, u.smon_f, u.Hf, u.Wf = dr2.value, dm2.value, Ws, Ws, Hs, Ws
+    u.x_off, u.y_off = float(bx), float(by)
+prm2 = params(max_corners=cap, win_size=21)        # (a 48-row unit: its half-size level must stay taller than the window)
+for piped in (0, 1):
+    # (pipelined: the tail is enqueued by km_frame_wait's caller - here km_frame_flush, the submitting thread's way)
+    def submit_units(c2, t):
+        rc = lib.km_klt_units_frame_submit(c2, units2, 2, 1, None, None, C.byref(prm2), 0.4, cap, C.byref(t))
+        return rc if rc else lib.km_frame_flush(c2, t.value)
+    steps.append(sweep(f"units submit (pipeline {piped})", submit_units, 2 * blk_bytes, ((b"units_pipeline", piped),)))
+t_sweep = time.perf_counter() - t_sweep
+assert all(k >= 5 for k in steps), steps           # (each call really allocates: the sweep walked failures, not one success)
+print(f"allocation-failure sweep: {steps} failing allocations per call, {t_sweep:.1f} s")
+for dptr in (dm2, dr2):
+    ok(lib.km_dev_free(ctx, dptr), "dev_free")
 
 for dptr in (dm, dr, sink):
     ok(lib.km_dev_free(ctx, dptr), "dev_free")

@@ -160,7 +160,7 @@ int kd_count_nonzero(km_ctx *, const uint8_t *m, size_t n, unsigned long long *v
 }
 int kd_laplacian_u8(km_ctx *, const uint8_t *s, int H, int W, int, uint8_t *d) { memmove(d, s, (size_t)H * W); return KM_OK; }
 int kd_stretch_laplacian_pair(km_ctx *c, const void *ref, const void *mon, int dtype, int H, int W, ptrdiff_t sr, ptrdiff_t sm, const double *mm, int, int, int inv,
-                              const double *nr, const double *nm, uint8_t *lr, uint8_t *lm, uint8_t *mask, unsigned long long *valid)
+                              const double *nr, const double *nm, uint8_t *lr, uint8_t *lm, uint8_t *mask, unsigned long long *valid, km_valid_job *)
 {
     kd_to_uint8(c, ref, dtype, H, W, sr, mm, 0, lr);
     kd_to_uint8(c, mon, dtype, H, W, sm, mm + 2, inv, lm);
@@ -176,8 +176,8 @@ int kd_min_eigen(km_ctx *, const uint8_t *s, const uint8_t *mask, int H, int W, 
     return KM_OK;
 }
 int k2_min_eigen(km_ctx *, const uint8_t *, const uint8_t *, int, int, int, float *, unsigned *) { return KM_E_UNSUPPORTED; }
-int k2_eig_candidates(km_ctx *, const uint8_t *, const uint8_t *, int, int, int, double, km_scalars *, unsigned long long *, size_t, bool) { return KM_E_UNSUPPORTED; }
-int k3_eig_candidates(km_ctx *, const uint8_t *, const uint8_t *, int, int, int, double, km_scalars *, unsigned long long *, size_t) { return KM_E_UNSUPPORTED; }
+int k2_eig_candidates(km_ctx *, const uint8_t *, const uint8_t *, int, int, int, double, km_scalars *, unsigned long long *, size_t, bool, km_eig_partials *) { return KM_E_UNSUPPORTED; }
+int k3_eig_candidates(km_ctx *, const uint8_t *, const uint8_t *, int, int, int, double, km_scalars *, unsigned long long *, size_t, km_eig_partials *) { return KM_E_UNSUPPORTED; }
 // candidates: every 7th pixel of every 5th row, keys written up to the capacity the caller reserved
 int kd_candidates(km_ctx *, const float *eig, const uint8_t *, int H, int W, double, km_scalars *sc, unsigned long long *keys, size_t cap, bool)
 {
@@ -235,7 +235,7 @@ int km_exclusive_scan(km_ctx *, const unsigned *in, unsigned *out, size_t n, int
     return KM_OK;
 }
 size_t kf_kept_capacity(int max_corners) { return (size_t)max_corners * 8; }
-int kf_rank(km_ctx *, const unsigned long long *, size_t, int, int, int, double, double, km_scalars *) { return KM_E_UNSUPPORTED; }
+int kf_rank(km_ctx *, const unsigned long long *, size_t, int, int, int, double, double, km_scalars *, km_eig_partials) { return KM_E_UNSUPPORTED; }
 int kf_select(km_ctx *, int, int, int, double, float *, int, km_scalars *) { return KM_E_UNSUPPORTED; }
 int kd_pyrdown_u8(km_ctx *, const uint8_t *s, int H, int W, uint8_t *d)
 {
@@ -326,7 +326,7 @@ int kz_zncc_filtered(km_ctx *, const void *, const void *, int, int, int, int, i
                      const int *d_n, const float *score, float thr, double *out)
 {
     const int m = std::min(*d_n, n);
-    for (int i = 0; i < m; i++) out[i] = score[i] >= thr ? (double)x0[i] : NAN;
+    for (int i = 0; i < n; i++) out[i] = i < m && score[i] >= thr ? (double)x0[i] : NAN;      // (the whole column: blocks compare byte for byte)
     return KM_OK;
 }
 int kz_zncc_windows(km_ctx *, const void *, const void *, int, int, int, int, int, int, ptrdiff_t, ptrdiff_t, const int *uv, int, int count, double *out, uint8_t *fl)
@@ -348,7 +348,7 @@ int kp_phase_shift(km_ctx *c, const void *a, const void *b, int dtype, int H, in
     return KM_OK;
 }
 void kp_destroy(km_ctx *) {}
-int kd_run_valid_sum(km_ctx *c) { c->valid_job_pending = false; return KM_OK; }
+int kd_run_valid_sum(km_ctx *, km_valid_job *job) { *job = km_valid_job(); return KM_OK; }
 
 // ---- batched units (api_units.hip): every stage touches the first and last byte / element of what the host laid out for it
 int kd_minmax_units(km_ctx *, const km_units &U, double *const *out, int)
@@ -426,8 +426,7 @@ int kz_zncc_units(km_ctx *, const km_score_units &A, int n_units, int, int n, fl
     for (int u = 0; u < n_units; u++) {
         const km_score_unit &s = A.u[u];
         const int m = std::min(*s.d_n, n);
-        for (int i = 0; i < m; i++) s.out[i] = s.score[i] >= thr ? (double)s.x0[i] : NAN;
-        s.out[n - 1] = s.out[n - 1];
+        for (int i = 0; i < n; i++) s.out[i] = i < m && s.score[i] >= thr ? (double)s.x0[i] : NAN;
     }
     return KM_OK;
 }
