@@ -31,42 +31,29 @@ void *km_ws_peek(km_ctx *c, int slot) { return c->lane ? c->ws_b[slot].p : c->ws
 
 void *km_ws(km_ctx *c, int slot, size_t bytes)
 {
-    km_buf &b = c->lane ? c->ws_b[slot] : c->ws[slot];
+    km_dev_mem &b = c->lane ? c->ws_b[slot] : c->ws[slot];
     if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes) return b.p;
-    if (b.p) {
-        // The library's streams may still use the old buffer: it is RETIRED, not freed - work already queued keeps a valid buffer,
-        // new work gets the new one, and nothing synchronises (round 3 did hipDeviceSynchronize + hipFree here: a device-wide stall
-        // under the feet of every other context on the GPU).  Retired buffers are released when the context is next synchronised
-        // by its owner (km_ctx_sync) or destroyed.  Slots only grow, and by 6 % head-room at least: a handful of regrows per context.
-        c->retired.push_back(b.p);
-        b.p = nullptr; b.cap = 0;
-    }
-    size_t want = bytes + bytes / 16 + 256;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) {
-        km_fail(c, KM_E_NOMEM, "hipMalloc(%zu) for workspace slot %d: %s", want, slot, hipGetErrorString(e));
-        return nullptr;
-    }
-    b.p = p; b.cap = want;
-    return p;
+    // The library's streams may still use the old buffer: it is RETIRED, not freed - work already queued keeps a valid buffer,
+    // new work gets the new one, and nothing synchronises (round 3 did hipDeviceSynchronize + hipFree here: a device-wide stall
+    // under the feet of every other context on the GPU).  Retired buffers are released when the context is next synchronised
+    // by its owner (km_ctx_sync) or destroyed.  Slots only grow, and by 6 % head-room at least: a handful of regrows per context.
+    const size_t headroom = bytes / 16 + 256;
+    const hipError_t e = b.reserve(bytes, headroom, &c->retired);
+    if (e != hipSuccess) km_fail(c, KM_E_NOMEM, "hipMalloc(%zu) for workspace slot %d: %s", bytes + headroom, slot, hipGetErrorString(e));
+    return b.p;
 }
 
 void *km_pinned_rb(km_ctx *c, size_t bytes)
 {
-    if (c->pinned_rb_cap >= bytes) return c->pinned_rb;
-    if (c->pinned_rb) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->pinned_rb); c->pinned_rb = nullptr; c->pinned_rb_cap = 0; }
-    void *p = nullptr;
-    const hipError_t e = hipHostMalloc(&p, bytes + 256, hipHostMallocDefault);
-    if (e != hipSuccess) { km_fail(c, KM_E_NOMEM, "hipHostMalloc(%zu): %s", bytes + 256, hipGetErrorString(e)); return nullptr; }
-    c->pinned_rb = p; c->pinned_rb_cap = bytes + 256;
-    return p;
+    if (c->pinned_rb.cap < bytes && c->pinned_rb.p) (void)hipStreamSynchronize(c->stream);   // (the copies that land in the old block)
+    const hipError_t e = c->pinned_rb.reserve(bytes, 256);
+    if (e != hipSuccess) km_fail(c, KM_E_NOMEM, "hipHostMalloc(%zu): %s", bytes + 256, hipGetErrorString(e));
+    return c->pinned_rb.p;
 }
 
 int km_wait_readback(km_ctx *c)
 {
-    if (!c->ev_readback) KM_HIP(c, hipEventCreateWithFlags(&c->ev_readback, hipEventDisableTiming));
+    { const int rc = km_event(c, &c->ev_readback); if (rc) return rc; }
     static const bool no_defer = km_dev_env("KARIOS_HIP_NO_DEFER") != nullptr;   // A/B switch: wait first, run the jobs afterwards
     KM_HIP(c, hipEventRecord(c->ev_readback, c->stream));
     if (!c->deferred.empty() && !no_defer && !c->opt_no_defer) {
@@ -123,11 +110,11 @@ int km_ctx_create(int device, km_ctx **out)
     c->device = device;
     memset(&c->stats, 0, sizeof c->stats);
     memset(c->evs_used, 0, sizeof c->evs_used);
-    if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) {
-        int rc = km_fail(nullptr, KM_E_HIP, "stream creation on device %d: %s", device, hipGetErrorString(e));
+    if ((e = hipSetDevice(device)) != hipSuccess || (e = c->main_stream.create(hipStreamNonBlocking, 0)) != hipSuccess) {
         delete c;
-        return rc;
+        return km_fail(nullptr, KM_E_HIP, "stream creation on device %d: %s", device, hipGetErrorString(e));
     }
+    c->stream = c->main_stream;
     if (const char *e = getenv("KARIOS_HIP_FUSED_EIG")) c->fused_eig = atoi(e) != 0;
     if (const char *e = getenv("KARIOS_HIP_EIG3")) c->opt_eig3 = atoi(e) != 0;
     if (const char *e = getenv("KARIOS_HIP_AUX_PYRAMID")) c->opt_aux_pyramid = atoi(e) != 0;
@@ -143,47 +130,9 @@ int km_ctx_destroy(km_ctx *c)
     if (!c) return KM_OK;
     (void)hipSetDevice(c->device);
     (void)km_units_flush(c);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->chain_stream) (void)hipStreamSynchronize(c->chain_stream);
-    kp_destroy(c);
-    if (c->ev_readback) (void)hipEventDestroy(c->ev_readback);
-    if (c->pinned_rb) (void)hipHostFree(c->pinned_rb);
-    km_ring_destroy(c);
-    for (km_frame_slot &f : c->fslot) {
-        if (f.host) (void)hipHostFree(f.host);
-        if (f.done) (void)hipEventDestroy(f.done);
-        if (f.sunk) (void)hipEventDestroy(f.sunk);
-    }
-    for (int i = 0; i < WS_COUNT; i++)
-        if (c->ws[i].p) (void)hipFree(c->ws[i].p);
-    if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    if (c->d2h_stream) (void)hipStreamSynchronize(c->d2h_stream);
-    for (void *p : c->retired) (void)hipFree(p);
-    c->retired.clear();
-    if (c->ev_ready)
-        for (int k = 0; k <= KM_FRAME_SLOTS; k++)
-            for (int i = 0; i < ST_COUNT; i++) { (void)hipEventDestroy(c->evs[k][i][0]); (void)hipEventDestroy(c->evs[k][i][1]); }
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
-    if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
-    if (c->d2h_stream) { (void)hipStreamSynchronize(c->d2h_stream); (void)hipStreamDestroy(c->d2h_stream); }
-    if (c->chain_stream) { (void)hipStreamSynchronize(c->chain_stream); (void)hipStreamDestroy(c->chain_stream); }
-    for (int l = 0; l < 2; l++)
-        for (int i = 0; i < KM_LANE_EVENTS; i++)
-            if (c->ev_lane[l][i]) (void)hipEventDestroy(c->ev_lane[l][i]);
-    for (int i = 0; i < WS_COUNT; i++)
-        if (c->ws_b[i].p) (void)hipFree(c->ws_b[i].p);
-    if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-    if (c->ev_lk_start) (void)hipEventDestroy(c->ev_lk_start);
-    if (c->ev_mm) (void)hipEventDestroy(c->ev_mm);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (hipEvent_t e : c->upload_marks) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->free_marks) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
-    km_units_free(c);
-    delete c;
+    for (hipStream_t s : {c->main_stream.h, c->chain_stream.h, c->aux_stream.h, c->copy_stream.h, c->d2h_stream.h})
+        if (s) (void)hipStreamSynchronize(s);
+    delete c;      // (every resource has an owner: km_ctx's member order is the release order)
     return KM_OK;
 }
 
@@ -199,7 +148,6 @@ int km_ctx_sync(km_ctx *c)
         // workspace buffers replaced by larger ones: nothing of this context uses them any more once its streams are idle
         if (c->aux_stream) KM_HIP(c, hipStreamSynchronize(c->aux_stream));
         if (c->copy_stream) KM_HIP(c, hipStreamSynchronize(c->copy_stream));
-        for (void *p : c->retired) (void)hipFree(p);
         c->retired.clear();
         c->retired_mark = 0;
     }
@@ -287,8 +235,8 @@ int km_set_profiling(km_ctx *c, int enable)
 {
     if (!c) return km_fail(nullptr, KM_E_ARG, "null context");
     if (enable && !c->ev_ready) {
-        for (int k = 0; k <= KM_FRAME_SLOTS; k++)
-            for (int i = 0; i < ST_COUNT; i++) { KM_HIP(c, hipEventCreate(&c->evs[k][i][0])); KM_HIP(c, hipEventCreate(&c->evs[k][i][1])); }
+        for (auto &set : c->evs)
+            for (auto &span : set) { KM_HIP(c, span[0].create(0)); KM_HIP(c, span[1].create(0)); }   // (flags 0: timing events, what hipEventCreate makes)
         c->ev_ready = true;
     }
     c->profiling = enable != 0;
@@ -410,10 +358,7 @@ int km_upload_async(km_ctx *c, void *dst, size_t dst_pitch, const void *src, siz
     if (!c || !dst || !src) return km_fail(c, KM_E_ARG, "km_upload_async: null argument");
     if (dst_pitch < width_bytes || src_pitch < width_bytes) return km_fail(c, KM_E_ARG, "km_upload_async: pitch below the row width");
     KM_HIP(c, hipSetDevice(c->device));
-    if (!c->copy_stream) {
-        KM_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        KM_HIP(c, hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
-    }
+    { int rc; if ((rc = km_stream(c, &c->copy_stream)) || (rc = km_event(c, &c->ev_copy))) return rc; }
     if (rows == 0 || width_bytes == 0) return KM_OK;
     // page-locked source (km_host_alloc / hipHostMalloc / hipHostRegister): DMA'd in place, truly asynchronous.  Pageable source:
     // packed into the context's page-locked ring chunk by chunk (staging.hip) - the call returns when the source has been read,
@@ -429,14 +374,14 @@ int km_upload_mark(km_ctx *c, int *ticket)
     if (!c || !ticket) return km_fail(c, KM_E_ARG, "km_upload_mark: null argument");
     *ticket = -1;
     if (!c->copy_stream) return KM_OK;                      // nothing was ever uploaded asynchronously: ticket -1 = already complete
-    hipEvent_t ev = nullptr;
-    if (!c->free_marks.empty()) { ev = c->free_marks.back(); c->free_marks.pop_back(); }
-    else KM_HIP(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    km_event_h ev;
+    if (!c->free_marks.empty()) { ev = std::move(c->free_marks.back()); c->free_marks.pop_back(); }
+    { const int rc = km_event(c, &ev); if (rc) return rc; }
     KM_HIP(c, hipEventRecord(ev, c->copy_stream));
     size_t slot = 0;
     while (slot < c->upload_marks.size() && c->upload_marks[slot]) slot++;
-    if (slot == c->upload_marks.size()) c->upload_marks.push_back(nullptr);
-    c->upload_marks[slot] = ev;
+    if (slot == c->upload_marks.size()) c->upload_marks.emplace_back();
+    c->upload_marks[slot] = std::move(ev);
     c->copy_pending = false;                                // the caller took charge of the ordering
     *ticket = (int)slot;
     return KM_OK;
@@ -446,11 +391,10 @@ int km_upload_join(km_ctx *c, int ticket)
     if (!c) return km_fail(c, KM_E_ARG, "null context");
     if (ticket < 0) return KM_OK;
     if ((size_t)ticket >= c->upload_marks.size() || !c->upload_marks[ticket]) return km_fail(c, KM_E_ARG, "km_upload_join: unknown ticket %d", ticket);
-    hipEvent_t ev = c->upload_marks[ticket];
+    km_event_h &ev = c->upload_marks[ticket];
     KM_HIP(c, hipStreamWaitEvent(c->stream, ev, 0));        // device-side wait: the host does not block
     if (c->aux_stream) KM_HIP(c, hipStreamWaitEvent(c->aux_stream, ev, 0));
-    c->upload_marks[ticket] = nullptr;
-    c->free_marks.push_back(ev);
+    c->free_marks.push_back(std::move(ev));                 // (leaves the ticket's slot empty)
     return KM_OK;
 }
 int km_upload_wait(km_ctx *c)
@@ -549,7 +493,8 @@ int begin_call(km_ctx *c, int reset)
     return KM_OK;
 }
 
-int km_event(km_ctx *c, hipEvent_t *e) { if (!*e) KM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming)); return KM_OK; }
+int km_event(km_ctx *c, km_event_h *e) { KM_HIP(c, e->create(hipEventDisableTiming)); return KM_OK; }
+int km_stream(km_ctx *c, km_stream_h *s, int priority) { KM_HIP(c, s->create(hipStreamNonBlocking, priority)); return KM_OK; }
 int km_record(km_ctx *c, hipEvent_t ev, hipStream_t s) { KM_HIP(c, hipEventRecord(ev, s)); return KM_OK; }
 int km_wait(km_ctx *c, hipStream_t s, hipEvent_t ev) { KM_HIP(c, hipStreamWaitEvent(s, ev, 0)); return KM_OK; }
 
@@ -558,21 +503,17 @@ int km_wait(km_ctx *c, hipStream_t s, hipEvent_t ev) { KM_HIP(c, hipStreamWaitEv
 // together (both wait for the Laplacians), the main stream's takes the compute units first and this stream's fill what it leaves
 int km_aux_stream(km_ctx *c)
 {
-    if (!c->aux_stream) {
-        int prio_lo = 0, prio_hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        KM_HIP(c, hipStreamCreateWithPriority(&c->aux_stream, hipStreamNonBlocking, c->opt_aux_priority ? prio_lo : 0));
-    }
-    const int rc = km_event(c, &c->ev_fork);
-    return rc ? rc : km_event(c, &c->ev_join);
+    int rc, prio_lo = 0, prio_hi = 0;
+    if (!c->aux_stream && c->opt_aux_priority) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    if ((rc = km_stream(c, &c->aux_stream, prio_lo)) || (rc = km_event(c, &c->ev_fork))) return rc;
+    return km_event(c, &c->ev_join);
 }
 
 // The block-copy stream, made to wait for what c->stream holds so far (its tail event): a submitted frame's blocks leave there
 int km_block_stream(km_ctx *c)
 {
     int rc;
-    if (!c->d2h_stream) KM_HIP(c, hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking));
-    if ((rc = km_event(c, &c->ev_tail)) || (rc = km_record(c, c->ev_tail, c->stream))) return rc;
+    if ((rc = km_stream(c, &c->d2h_stream)) || (rc = km_event(c, &c->ev_tail)) || (rc = km_record(c, c->ev_tail, c->stream))) return rc;
     return km_wait(c, c->d2h_stream, c->ev_tail);
 }
 

@@ -32,7 +32,8 @@ struct km_on_stream {
     ~km_on_stream() { c->stream = prev; }
     km_on_stream(const km_on_stream &) = delete;
 };
-int km_event(km_ctx *c, hipEvent_t *e);                   // creates *e (no timing) unless it exists
+int km_event(km_ctx *c, km_event_h *e);                   // creates *e (no timing) unless it exists
+int km_stream(km_ctx *c, km_stream_h *s, int priority = 0);   // creates *s (non-blocking) unless it exists
 int km_record(km_ctx *c, hipEvent_t ev, hipStream_t s);   // KM_OK or km_fail(...)
 int km_wait(km_ctx *c, hipStream_t s, hipEvent_t ev);     // device-side wait of `s` for `ev`
 int km_aux_stream(km_ctx *c);                             // the second stream with its fork / join events (created on first use)

@@ -75,23 +75,22 @@ void *grow_keep(km_ctx *c, int slot, size_t used, size_t bytes)
 
 void retire_slot(km_ctx *c, int slot)
 {
-    km_buf &b = c->lane ? c->ws_b[slot] : c->ws[slot];
-    if (b.p) { c->retired.push_back(b.p); b.p = nullptr; b.cap = 0; }
+    km_dev_mem &b = c->lane ? c->ws_b[slot] : c->ws[slot];
+    if (b.p) c->retired.push_back(std::move(b));
 }
 
 // Stage times without a synchronisation of their own: an event on the stream where a stage begins; the time between two neighbours
 // is credited to the earlier one's word of the stats.  Only kept when the caller asked for stats.
 struct stage_clock {
-    std::vector<std::pair<int, hipEvent_t>> marks;
+    std::vector<std::pair<int, km_event_h>> marks;
     bool on = false;
-    ~stage_clock() { for (auto &m : marks) (void)hipEventDestroy(m.second); }
     void mark(km_ctx *c, int word)
     {
         if (!on) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
+        km_event_h e;
+        if (e.create(0) != hipSuccess) { on = false; return; }
         (void)hipEventRecord(e, c->stream);
-        marks.emplace_back(word, e);
+        marks.emplace_back(word, std::move(e));
     }
     void read(int64_t *st)          // after the stream has been synchronised
     {

@@ -389,12 +389,7 @@ int frame_sink_check(km_ctx *c, size_t pitch, int n, size_t ob)
 // the slot of a submitted frame: `bytes` of page-locked memory (one eighth of head-room when it grows) and its completion event
 int frame_slot_reserve(km_ctx *c, km_frame_slot *slot, size_t bytes)
 {
-    if (slot->cap < bytes) {
-        if (slot->host) KM_HIP(c, hipHostFree(slot->host));
-        slot->host = nullptr; slot->cap = 0;
-        KM_HIP(c, hipHostMalloc(&slot->host, bytes + bytes / 8, hipHostMallocDefault));
-        slot->cap = bytes + bytes / 8;
-    }
+    KM_HIP(c, slot->host.reserve(bytes, bytes / 8));
     return km_event(c, &slot->done);
 }
 

@@ -66,7 +66,7 @@ static int units_tail(km_ctx *c, km_units_tail &T)
     c->lane = T.lane;
     c->ev_cur = 1 + T.slot;
     c->profile_skip = T.profile_skip;             // (the stage events of THIS submission: sampled with its own tick)
-    hipEvent_t *ev = c->ev_lane[T.lane];
+    km_event_h *ev = c->ev_lane[T.lane];
     if ((rc = km_wait(c, main_stream, ev[EV_JOIN])) || (T.piped && (rc = km_wait(c, main_stream, ev[EV_C_DONE])))) return rc;
     // ---- K7: LK forward + backward of every unit's corners in one launch
     {
@@ -141,18 +141,16 @@ static int units_flush_locked(km_ctx *c)
     return rc;
 }
 
-extern "C++" void km_units_free(km_ctx *c)
-{
-    delete c->utail; c->utail = nullptr;
-    delete c->enqueue_mu; c->enqueue_mu = nullptr;
-}
+// (here, not in the header: the context owns its deferred tail, and km_units_tail is complete in this file only)
+km_ctx::km_ctx() = default;
+km_ctx::~km_ctx() = default;
 
 // join = true (any entry point other than the next batched submission, km_ctx_sync, the option going off): the library's streams also
 // wait for both lanes' chains - whatever follows on them may reuse lane 0's workspace in plain stream order
 extern "C++" int km_units_flush(km_ctx *c, bool join)
 {
-    if (!c || !c->utail || !c->enqueue_mu) return KM_OK;
-    std::lock_guard<std::mutex> lk(*c->enqueue_mu);
+    if (!c || !c->utail) return KM_OK;
+    std::lock_guard<std::mutex> lk(c->enqueue_mu);
     if (c->utail->armed) KM_HIP(c, hipSetDevice(c->device));      // (the fallback of km_frame_wait runs on a thread of the caller's)
     const int rc = units_flush_locked(c);
     return rc || !join ? rc : join_lanes(c);
@@ -204,9 +202,8 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         if (q.W < 512 || q.H < 2 * prm->block_size + 8 || (q.W + 1) / 2 <= prm->win_size || (q.H + 1) / 2 <= prm->win_size) return KM_E_UNSUPPORTED;
         if ((prm->ksize_ref == 11 || prm->ksize_mon == 11) && q.H < 16) return KM_E_UNSUPPORTED;      // (the marching kernel's radius-5 form: kd_stretch_laplacian_units)
     }
-    if (!c->enqueue_mu) c->enqueue_mu = new std::mutex;
-    if (!c->utail) c->utail = new km_units_tail;
-    std::lock_guard<std::mutex> enqueue_lock(*c->enqueue_mu);
+    if (!c->utail) c->utail.reset(new km_units_tail);
+    std::lock_guard<std::mutex> enqueue_lock(c->enqueue_mu);
     km_units_tail &old_tail = *c->utail;
     const bool piped = c->opt_units_pipeline && dtype != KM_U8;
     // (a pipelined submission was the previous one: its tail first, and this one behind both lanes' chains)
@@ -230,8 +227,8 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     if ((rc = km_aux_stream(c))) return rc;
     for (int i = 0; i < KM_LANE_EVENTS; i++)
         if ((rc = km_event(c, &c->ev_lane[lane][i]))) return rc;
-    if (piped && !c->chain_stream) KM_HIP(c, hipStreamCreateWithFlags(&c->chain_stream, hipStreamNonBlocking));
-    hipEvent_t *ev = c->ev_lane[lane];
+    if (piped && (rc = km_stream(c, &c->chain_stream))) return rc;
+    km_event_h *ev = c->ev_lane[lane];
 
     // ---- layout: unit u's slices of the lane's workspace slots
     km_units U;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <functional>
 #include <string>
@@ -47,10 +48,59 @@ enum km_stage {
     ST_COUNT
 };
 
-struct km_buf {
+// ---- owners of the HIP resources a context holds: move-only, released by the destructor (errors ignored: nothing can be done about
+// them at that point), implicitly the raw handle wherever a launch or a hip* call wants one
+template <typename T, typename Kind>     // Kind::destroy(T) releases one
+struct km_handle {
+    T h = nullptr;
+    km_handle() = default;
+    km_handle(km_handle &&o) noexcept : h(o.h) { o.h = nullptr; }
+    km_handle &operator=(km_handle &&o) noexcept { if (this != &o) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ~km_handle() { reset(); }
+    void reset() { if (h) (void)Kind::destroy(h); h = nullptr; }
+    operator T() const { return h; }
+};
+// create(): nothing when the handle exists already
+struct km_stream_h : km_handle<hipStream_t, km_stream_h> {
+    static hipError_t destroy(hipStream_t s) { return hipStreamDestroy(s); }
+    hipError_t create(unsigned flags, int priority) { return h ? hipSuccess : hipStreamCreateWithPriority(&h, flags, priority); }   // (priority 0: the default)
+};
+struct km_event_h : km_handle<hipEvent_t, km_event_h> {
+    static hipError_t destroy(hipEvent_t e) { return hipEventDestroy(e); }
+    hipError_t create(unsigned flags) { return h ? hipSuccess : hipEventCreateWithFlags(&h, flags); }
+};
+// memory that only grows: reserve(bytes) keeps a buffer of at least `bytes`, else replaces it by one of bytes + headroom.  The old buffer
+// is released first, or handed to *retire when work already queued may still use it (km_ws)
+struct km_device_heap {
+    static hipError_t get(void **p, size_t n) { return hipMalloc(p, n); }
+    static hipError_t put(void *p) { return hipFree(p); }
+};
+struct km_pinned_heap {
+    static hipError_t get(void **p, size_t n) { return hipHostMalloc(p, n, hipHostMallocDefault); }
+    static hipError_t put(void *p) { return hipHostFree(p); }
+};
+template <typename Heap>
+struct km_mem {
     void *p = nullptr;
     size_t cap = 0;
+    km_mem() = default;
+    km_mem(km_mem &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    km_mem &operator=(km_mem &&o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~km_mem() { reset(); }
+    void reset() { if (p) (void)Heap::put(p); p = nullptr; cap = 0; }
+    operator void *() const { return p; }
+    hipError_t reserve(size_t bytes, size_t headroom = 0, std::vector<km_mem> *retire = nullptr)
+    {
+        if (cap >= bytes) return hipSuccess;
+        if (p && retire) retire->push_back(std::move(*this));
+        reset();
+        const hipError_t e = Heap::get(&p, bytes + headroom);
+        if (e == hipSuccess) cap = bytes + headroom; else p = nullptr;
+        return e;
+    }
 };
+using km_dev_mem = km_mem<km_device_heap>;
+using km_pinned_mem = km_mem<km_pinned_heap>;
 
 // Grow-only device workspace slots.
 enum km_slot {
@@ -186,10 +236,10 @@ struct km_window {
 #define KM_LANE_EVENTS 8      // events of one lane of the batched units' software pipeline (api_units.hip)
 #define KM_FRAME_SLOTS 3
 struct km_frame_slot {
-    void *host = nullptr;
-    size_t cap = 0, bytes = 0;
-    hipEvent_t done = nullptr;
-    hipEvent_t sunk = nullptr;      // the frame's block is in the frame sink (km_set_frame_sink): recorded on the compute stream behind the copy
+    km_pinned_mem host;
+    size_t bytes = 0;
+    km_event_h done;
+    km_event_h sunk;                // the frame's block is in the frame sink (km_set_frame_sink): recorded on the compute stream behind the copy
     bool sunk_valid = false;
     std::atomic<int> pending{0};
     std::atomic<int> deferred{0};   // pipelined batched submission: the tail (LK .. copy-out) of this frame has not been enqueued yet
@@ -198,8 +248,8 @@ struct km_frame_slot {
 // staging.hip: page-locked ring between caller memory and the device (no runtime copy ever reads or writes pageable memory)
 #define KM_RING_SLOTS 4
 struct km_ring_slot {
-    void *buf = nullptr;
-    hipEvent_t done = nullptr;      // the DMA that reads the slot
+    km_pinned_mem buf;
+    km_event_h done;                // the DMA that reads the slot
     bool busy = false;
 };
 struct km_stage_ring {
@@ -210,49 +260,58 @@ struct km_stage_ring {
 struct km_land_job { void *dst; const void *pinned; size_t bytes; };
 struct km_chk_job { const char *what; const void *host; size_t elem; int H, W; ptrdiff_t stride; const void *d; size_t off; };
 
+struct km_units_tail;   // api_units.hip
 struct km_ctx {
+    km_ctx();
+    ~km_ctx();                 // (both in api_units.hip, where km_units_tail is complete)
     int device = 0;
     int n_cu = 256;            // compute units of the device (wave slots = n_cu * 4 SIMDs * waves per SIMD)
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;   // km_upload_async: uploads of the next pair / tile under the compute of the current one
-    hipEvent_t ev_copy = nullptr;
-    hipStream_t aux_stream = nullptr;    // sync-free tile path: the pyramids (they depend on the Laplacians only) run here next to the
-    hipStream_t d2h_stream = nullptr;    // km_klt_tile_frame_submit: the finished frame block travels to the host here
+    // RELEASE ORDER = the reverse of the member order (km_ctx_destroy synchronises every stream, then deletes the context): every buffer
+    // and event below goes first, the streams after them, the main stream last of all.  A new resource is a new owner member below the
+    // streams and nothing else
+    km_stream_h main_stream;             // created with the context
+    hipStream_t stream = nullptr;        // the CURRENT stream of the launchers: main_stream, or what km_on_stream points it at (not an owner)
+    km_stream_h copy_stream;             // km_upload_async: uploads of the next pair / tile under the compute of the current one
+    km_stream_h aux_stream;              // sync-free tile path: the pyramids (they depend on the Laplacians only) run here next to the
+    km_stream_h d2h_stream;              // km_klt_tile_frame_submit: the finished frame block travels to the host here
     // ---- software-pipelined batched submissions ("units_pipeline", api_units.hip): two LANES (workspace sets) alternate; the dense
     // kernels of both lanes interleave on `stream`, the latency-bound chains (corner selection; frame stage + scores) run on
     // `chain_stream` beside the other lane's dense kernels; a submission's tail (LK, frame stage, scores, copy-out) is enqueued by
     // the NEXT submission (or km_frame_flush)
-    hipStream_t chain_stream = nullptr;
-    hipEvent_t ev_lane[2][KM_LANE_EVENTS] = {};
+    km_stream_h chain_stream;
+    km_event_h ev_copy;                  // join_uploads: whatever copy_stream holds so far
+    km_event_h ev_lane[2][KM_LANE_EVENTS];
     bool lane_f_recorded[2] = {false, false};   // EV_F_DONE of the lane has been recorded: its next submission waits for it
     bool in_units_submit = false;
     bool opt_units_pipeline = false;
     int lane = 0;                        // workspace set km_ws hands out (0: `ws`, 1: `ws_b`)
-    struct km_units_tail *utail = nullptr;   // the deferred tail (armed: enqueue pending)
-    std::mutex *enqueue_mu = nullptr;    // submit / flush / the fallback flush of km_frame_wait
-    hipEvent_t ev_tail = nullptr, frame_copy = nullptr;   // frame_copy: completion of the last block copy (WS_FRAME must not be rewritten before)
-    hipEvent_t ev_lk_start = nullptr, ev_mm = nullptr;   // early min/max: the next unit's K1 starts on aux_stream when this unit's LK launch starts
+    std::unique_ptr<km_units_tail> utail;   // the deferred tail (armed: enqueue pending), made by the first batched submission
+    std::mutex enqueue_mu;               // submit / flush / the fallback flush of km_frame_wait
+    km_event_h ev_tail;
+    hipEvent_t frame_copy = nullptr;     // completion of the last block copy (WS_FRAME must not be rewritten before): an ALIAS of that frame slot's `done`, not an owner
+    km_event_h ev_lk_start, ev_mm;       // early min/max: the next unit's K1 starts on aux_stream when this unit's LK launch starts
     bool lk_start_valid = false, lk_start_prev = false;   //   ... ev_lk_start was recorded by the tile call that directly preceded this one
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // chain of small corner-selection kernels on `stream`, joined before LK
+    km_event_h ev_fork, ev_join;         // chain of small corner-selection kernels on `stream`, joined before LK
     bool copy_pending = false;           // uploads queued since the compute stream last waited for the whole copy stream
-    std::vector<hipEvent_t> upload_marks;   // km_upload_mark tickets: events on the copy stream, nullptr = ticket consumed
-    std::vector<hipEvent_t> free_marks;
+    std::vector<km_event_h> upload_marks;   // km_upload_mark tickets: events on the copy stream, empty = ticket consumed
+    std::vector<km_event_h> free_marks;
     km_window window;                    // km_set_image_window
     size_t band_capk = 0;                // km_band_eigen_dev -> km_band_keys_dev: capacity of the candidate keys left in WS_KEYS0
     bool band_fused = false;             //   ... emitted by the fused kernel (else: eig map in WS_EIG, candidates still to be scanned)
     void *frame_sink = nullptr;          // km_set_frame_sink: device-side copy of every frame block
     size_t frame_sink_cap = 0;
     size_t frame_sink_pitch = 0;         // km_set_frame_sink_pitch: distance between the blocks of a batched submission (0: block size)
-    km_buf ws[WS_COUNT];
-    km_buf ws_b[WS_COUNT];               // lane 1 of the pipelined batched submissions
-    std::vector<void *> retired;         // workspace buffers replaced by larger ones (km_ws): freed at the next km_ctx_sync / destroy
+    km_dev_mem ws[WS_COUNT];
+    km_dev_mem ws_b[WS_COUNT];           // lane 1 of the pipelined batched submissions
+    std::vector<km_dev_mem> retired;        // workspace buffers replaced by larger ones (km_ws): freed at the next km_ctx_sync / destroy
     size_t retired_mark = 0;             // ... the first `retired_mark` of them were retired before the running entry point began (begin_call)
     km_stage_ring ring;                  // host -> device staging (staging.hip)
-    void *land = nullptr;                // device -> host landing arena (page-locked), km_d2h_queue / km_d2h_flush
-    size_t land_cap = 0, land_used = 0;
-    hipEvent_t land_ev[2] = {nullptr, nullptr};
+    km_pinned_mem land;                  // device -> host landing arena (page-locked), km_d2h_queue / km_d2h_flush
+    size_t land_used = 0;
+    km_event_h land_ev[2];
     std::vector<km_land_job> land_jobs;
-    void *chk_dev = nullptr, *chk_host = nullptr;   // KARIOS_HIP_UPLOAD_CHECKSUM: row checksums seen by a kernel right behind each upload
+    km_dev_mem chk_dev;                  // KARIOS_HIP_UPLOAD_CHECKSUM: row checksums seen by a kernel right behind each upload
+    km_pinned_mem chk_host;
     size_t chk_used = 0;
     std::vector<km_chk_job> chk_jobs;
     long long chk_armed_total = 0, chk_miss_total = 0;
@@ -260,7 +319,7 @@ struct km_ctx {
     // Independent device work queued by the caller to fill the GPU while the host waits for a small read-back (the two
     // synchronisations of the corner selection): km_wait_readback runs ONE deferred job between the copy and the wait.
     std::vector<std::function<int()>> deferred;
-    hipEvent_t ev_readback = nullptr;
+    km_event_h ev_readback;
     bool profiling = false;
     int fused_eig = 1;         // km_set_option("fused_eig"): 1 = K3+K4 fused (k_eig2.hip, no eig map), 0 = eig map + candidate scan
     // test knobs (km_set_option, 0 = default): shrunken capacities that force the corner detector's retry paths
@@ -293,7 +352,7 @@ struct km_ctx {
     bool opt_no_defer = false; // "defer" 0: the deferred pyramid jobs run after the read-back waits instead of under them
     // stage-timer events: set 0 serves the synchronous calls, sets 1..KM_FRAME_SLOTS the frames in flight of
     // km_klt_tile_frame_submit (a frame's spans are read after ITS completion, while the next one is already recording)
-    hipEvent_t evs[KM_FRAME_SLOTS + 1][ST_COUNT][2];
+    km_event_h evs[KM_FRAME_SLOTS + 1][ST_COUNT][2];
     bool evs_used[KM_FRAME_SLOTS + 1][ST_COUNT];
     int ev_cur = 0;
     bool ev_ready = false;
@@ -301,8 +360,7 @@ struct km_ctx {
     int fslot_next = 0;
     // pinned landing zone of the small mid-pipeline read-backs: a copy into pageable memory blocks the host until the
     // stream has drained, so nothing could be queued behind it (the deferred jobs of km_wait_readback arrived too late)
-    void *pinned_rb = nullptr;
-    size_t pinned_rb_cap = 0;
+    km_pinned_mem pinned_rb;
     km_klt_stats stats;
     int phase_path = 0;            // last km_phase_shift*: 1 = float32 hand-written FFT, 2 = double precision (k_fft64.hip)
     double phase_margin = 0.0;     // (max - second largest) / max of |cc| seen by the float32 path
@@ -377,14 +435,12 @@ static inline int km_pick_rows(int H, int nstrips, int halo, long wave_slots, in
 void *km_ws(km_ctx *ctx, int slot, size_t bytes);  // nullptr on failure (error set); the slot of the context's current lane
 void *km_ws_peek(km_ctx *ctx, int slot);           // the slot's current buffer (no growth)
 int km_units_flush(km_ctx *c, bool join = true);   // api_units.hip: enqueue the deferred tail of a pipelined batched submission (no-op without one)
-void km_units_free(km_ctx *c);                     // ... its host-side state (km_ctx_destroy)
 // staging.hip.  Host -> device: returns when `src` has been read completely; the DMAs (from the ring) are ordered on stream s.
 int km_h2d_staged(km_ctx *c, hipStream_t s, void *dst, size_t dst_pitch, const void *src, size_t src_pitch, size_t width_bytes, size_t rows);
 static inline int km_h2d_small(km_ctx *c, void *dst, const void *src, size_t bytes) { return km_h2d_staged(c, c->stream, dst, bytes, src, bytes, bytes, 1); }
 // Device -> host on c->stream: queue any number of results, then flush (completes the stream, copies them out of the landing arena)
 int km_d2h_queue(km_ctx *c, void *dst, const void *d_src, size_t bytes);
 int km_d2h_flush(km_ctx *c);
-void km_ring_destroy(km_ctx *c);
 bool km_upload_check_enabled();
 int km_upload_check_arm(km_ctx *c, const char *what, const void *host, size_t elem, int H, int W, ptrdiff_t stride, const void *d);
 int km_upload_check_verify(km_ctx *c);
@@ -629,7 +685,6 @@ int kmi_batch(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int Hr
 // k_phase.hip
 int kp_phase_shift(km_ctx *c, const void *d_a, const void *d_b, int dtype, int H, int W,
                    ptrdiff_t stride_a, ptrdiff_t stride_b, double out_rc[2]);
-void kp_destroy(km_ctx *c);
 // k_fft64.hip: the double-precision evaluation (any side length)
 int kp_phase_shift_f64(km_ctx *c, const void *d_a, const void *d_b, int dtype, int H, int W, ptrdiff_t stride_a, ptrdiff_t stride_b,
                        double out_rc[2]);

@@ -8,11 +8,6 @@
 // transform (k_fft64.hip) otherwise, under `phase_fp64`, and for the side lengths the float32 kernels do not factor.
 #include "common.hpp"
 
-void kp_destroy(km_ctx *c)
-{
-    c->f64_h = c->f64_w = 0;      // (the tables live in workspace slots, which go with the context)
-}
-
 int kp_phase_shift(km_ctx *c, const void *d_a, const void *d_b, int dtype, int H, int W, ptrdiff_t stride_a, ptrdiff_t stride_b,
                    double out_rc[2])
 {

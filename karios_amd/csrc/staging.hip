@@ -135,33 +135,15 @@ bool is_page_locked(const void *p)
 static int ring_ready(km_ctx *c)
 {
     km_stage_ring &r = c->ring;
-    if (r.slot[0].buf) return KM_OK;
+    if (r.chunk) return KM_OK;
     size_t chunk = (size_t)8 << 20;     // 4 x 8 MB: 50 GB/s from pageable memory on the GPU box (4 MB: 45.6, 1 - 2 MB: 30; page-locked source: 57.5)
     if (const char *e = km_dev_env("KARIOS_HIP_RING_CHUNK_KB")) { const long v = atol(e); if (v >= 64 && v <= (1 << 18)) chunk = (size_t)v << 10; }
-    for (int i = 0; i < KM_RING_SLOTS; i++) {
-        KM_HIP(c, hipHostMalloc(&r.slot[i].buf, chunk, hipHostMallocDefault));
-        KM_HIP(c, hipEventCreateWithFlags(&r.slot[i].done, hipEventDisableTiming));
-        r.slot[i].busy = false;
+    for (km_ring_slot &sl : r.slot) {
+        KM_HIP(c, sl.buf.reserve(chunk));
+        KM_HIP(c, sl.done.create(hipEventDisableTiming));
     }
-    r.chunk = chunk;
+    r.chunk = chunk;      // (set last: a ring that failed half-way is completed by the next call)
     return KM_OK;
-}
-
-void km_ring_destroy(km_ctx *c)
-{
-    for (int i = 0; i < KM_RING_SLOTS; i++) {
-        if (c->ring.slot[i].done) { (void)hipEventSynchronize(c->ring.slot[i].done); (void)hipEventDestroy(c->ring.slot[i].done); }
-        if (c->ring.slot[i].buf) (void)hipHostFree(c->ring.slot[i].buf);
-        c->ring.slot[i] = km_ring_slot();
-    }
-    for (int i = 0; i < 2; i++) { if (c->land_ev[i]) (void)hipEventDestroy(c->land_ev[i]); c->land_ev[i] = nullptr; }
-    if (c->land) (void)hipHostFree(c->land);
-    c->land = nullptr; c->land_cap = c->land_used = 0;
-    c->land_jobs.clear();
-    if (c->chk_dev) (void)hipFree(c->chk_dev);
-    if (c->chk_host) (void)hipHostFree(c->chk_host);
-    c->chk_dev = nullptr; c->chk_host = nullptr;
-    c->chk_jobs.clear();
 }
 
 int km_h2d_staged(km_ctx *c, hipStream_t s, void *dst, size_t dpitch, const void *src, size_t spitch, size_t wb, size_t rows)
@@ -186,14 +168,14 @@ int km_h2d_staged(km_ctx *c, hipStream_t s, void *dst, size_t dpitch, const void
         if (wb > r.chunk) {                                      // piece of one long row
             size_t n = wb - col;
             if (n > r.chunk) n = r.chunk;
-            copy_rows((char *)sl.buf, n, sp + row * spitch + col, n, n, 1);
+            copy_rows((char *)sl.buf.p, n, sp + row * spitch + col, n, n, 1);
             KM_HIP(c, hipMemcpyAsync(dp + row * dpitch + col, sl.buf, n, hipMemcpyHostToDevice, s));
             col += n;
             if (col == wb) { col = 0; row++; }
         } else {
             size_t nr = r.chunk / wb;
             if (nr > rows - row) nr = rows - row;
-            copy_rows((char *)sl.buf, wb, sp + row * spitch, spitch, wb, nr);
+            copy_rows((char *)sl.buf.p, wb, sp + row * spitch, spitch, wb, nr);
             if (dpitch == wb) KM_HIP(c, hipMemcpyAsync(dp + row * dpitch, sl.buf, wb * nr, hipMemcpyHostToDevice, s));
             else KM_HIP(c, hipMemcpy2DAsync(dp + row * dpitch, dpitch, sl.buf, wb, wb, nr, hipMemcpyHostToDevice, s));
             row += nr;
@@ -208,9 +190,8 @@ int km_h2d_staged(km_ctx *c, hipStream_t s, void *dst, size_t dpitch, const void
 static int land_ready(km_ctx *c)
 {
     if (c->land) return KM_OK;
-    size_t cap = (size_t)8 << 20;
-    KM_HIP(c, hipHostMalloc(&c->land, cap, hipHostMallocDefault));
-    c->land_cap = cap; c->land_used = 0;
+    KM_HIP(c, c->land.reserve((size_t)8 << 20));
+    c->land_used = 0;
     return KM_OK;
 }
 
@@ -218,15 +199,15 @@ int km_d2h_queue(km_ctx *c, void *dst, const void *d_src, size_t bytes)
 {
     if (bytes == 0) return KM_OK;
     { const int rc = land_ready(c); if (rc) return rc; }
-    if (bytes > c->land_cap / 2) {
+    if (bytes > c->land.cap / 2) {
         // large result: two halves of the arena alternate - the DMA of piece k+1 runs while the host copies piece k out
         { const int rc = km_d2h_flush(c); if (rc) return rc; }
-        const size_t half = c->land_cap / 2;
-        if (!c->land_ev[0]) for (int i = 0; i < 2; i++) KM_HIP(c, hipEventCreateWithFlags(&c->land_ev[i], hipEventDisableTiming));
+        const size_t half = c->land.cap / 2;
+        for (km_event_h &e : c->land_ev) KM_HIP(c, e.create(hipEventDisableTiming));
         const size_t np = (bytes + half - 1) / half;
         auto issue = [&](size_t k) -> int {
             const size_t off = k * half, n = bytes - off < half ? bytes - off : half;
-            KM_HIP(c, hipMemcpyAsync((char *)c->land + (k & 1) * half, (const char *)d_src + off, n, hipMemcpyDeviceToHost, c->stream));
+            KM_HIP(c, hipMemcpyAsync((char *)c->land.p + (k & 1) * half, (const char *)d_src + off, n, hipMemcpyDeviceToHost, c->stream));
             KM_HIP(c, hipEventRecord(c->land_ev[k & 1], c->stream));
             return KM_OK;
         };
@@ -235,14 +216,14 @@ int km_d2h_queue(km_ctx *c, void *dst, const void *d_src, size_t bytes)
             if (k + 1 < np) { const int rc = issue(k + 1); if (rc) return rc; }
             KM_HIP(c, hipEventSynchronize(c->land_ev[k & 1]));
             const size_t off = k * half, n = bytes - off < half ? bytes - off : half;
-            copy_rows((char *)dst + off, n, (const char *)c->land + (k & 1) * half, n, n, 1);
+            copy_rows((char *)dst + off, n, (const char *)c->land.p + (k & 1) * half, n, n, 1);
             // (piece k+2 reuses this half: it is issued in the next trip, after this copy-out)
         }
         return KM_OK;
     }
     const size_t need = (bytes + 63) & ~(size_t)63;
-    if (c->land_used + need > c->land_cap) { const int rc = km_d2h_flush(c); if (rc) return rc; }
-    void *p = (char *)c->land + c->land_used;
+    if (c->land_used + need > c->land.cap) { const int rc = km_d2h_flush(c); if (rc) return rc; }
+    void *p = (char *)c->land.p + c->land_used;
     c->land_used += need;
     KM_HIP(c, hipMemcpyAsync(p, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
     c->land_jobs.push_back({dst, p, bytes});
@@ -265,7 +246,6 @@ int km_d2h_flush(km_ctx *c)
         if (c->copy_stream) KM_HIP(c, hipStreamSynchronize(c->copy_stream));
         if (c->d2h_stream) KM_HIP(c, hipStreamSynchronize(c->d2h_stream));
         const size_t n = c->retired_mark < c->retired.size() ? c->retired_mark : c->retired.size();
-        for (size_t i = 0; i < n; i++) (void)hipFree(c->retired[i]);
         c->retired.erase(c->retired.begin(), c->retired.begin() + (ptrdiff_t)n);
         c->retired_mark = 0;
     }
@@ -291,13 +271,13 @@ bool km_upload_check_enabled()
 int km_upload_check_arm(km_ctx *c, const char *what, const void *host, size_t elem, int H, int W, ptrdiff_t stride, const void *d)
 {
     if (!km_upload_check_enabled() || H <= 0) return KM_OK;
-    if (!c->chk_dev) {
-        KM_HIP(c, hipMalloc(&c->chk_dev, (size_t)KM_CHK_ROWS * 8));
-        KM_HIP(c, hipHostMalloc(&c->chk_host, (size_t)KM_CHK_ROWS * 8, hipHostMallocDefault));
+    if (!c->chk_host) {
+        KM_HIP(c, c->chk_dev.reserve((size_t)KM_CHK_ROWS * 8));
+        KM_HIP(c, c->chk_host.reserve((size_t)KM_CHK_ROWS * 8));
         c->chk_used = 0;
     }
     if (c->chk_used + (size_t)H > KM_CHK_ROWS) return KM_OK;    // arena full until the next verification: this upload goes unchecked
-    unsigned long long *dsum = (unsigned long long *)c->chk_dev + c->chk_used, *hsum = (unsigned long long *)c->chk_host + c->chk_used;
+    unsigned long long *dsum = (unsigned long long *)c->chk_dev.p + c->chk_used, *hsum = (unsigned long long *)c->chk_host.p + c->chk_used;
     { const int rk = kf_row_checksum(c, d, (size_t)W * elem, H, dsum); if (rk) return rk; }
     KM_HIP(c, hipMemcpyAsync(hsum, dsum, (size_t)H * 8, hipMemcpyDeviceToHost, c->stream));
     c->chk_jobs.push_back({what, host, elem, H, W, stride, d, c->chk_used});
@@ -311,7 +291,7 @@ int km_upload_check_verify(km_ctx *c)
 {
     if (c->chk_jobs.empty()) return KM_OK;
     for (const km_chk_job &j : c->chk_jobs) {
-        const unsigned long long *seen = (const unsigned long long *)c->chk_host + j.off;
+        const unsigned long long *seen = (const unsigned long long *)c->chk_host.p + j.off;
         const size_t rb = (size_t)j.W * j.elem;
         int bad = 0, first = -1, last = -1;
         for (int y = 0; y < j.H; y++)
@@ -319,10 +299,10 @@ int km_upload_check_verify(km_ctx *c)
         if (!bad) continue;
         c->chk_miss_total++;
         // the stream is complete now: what does the same kernel see?
-        unsigned long long *dsum = (unsigned long long *)c->chk_dev + j.off;
+        unsigned long long *dsum = (unsigned long long *)c->chk_dev.p + j.off;
         (void)kf_row_checksum(c, j.d, rb, j.H, dsum);
         std::vector<unsigned long long> again((size_t)j.H);
-        unsigned long long *mine = (unsigned long long *)c->chk_host + j.off;   // (this job's own landing words: consumed above)
+        unsigned long long *mine = (unsigned long long *)c->chk_host.p + j.off;   // (this job's own landing words: consumed above)
         (void)hipMemcpyAsync(mine, dsum, (size_t)j.H * 8, hipMemcpyDeviceToHost, c->stream);
         (void)hipStreamSynchronize(c->stream);
         memcpy(again.data(), mine, (size_t)j.H * 8);

@@ -40,9 +40,28 @@ struct stub_state {
     std::mutex m;
     std::map<const char *, size_t> pinned;
     long device_allocs = 0, host_allocs = 0, pageable_async_copies = 0;
+    long streams = 0, events = 0;    // alive (like the two allocation counts: up where the stand-in creates one, down where it destroys one)
     int fail_malloc_after = -1;      // test knob: the n-th hipMalloc from now fails
+    int fail_host_malloc_after = -1; //   ... the n-th hipHostMalloc
+    int fail_create_after = -1;      //   ... the n-th creation of a stream or an event
 };
 stub_state &stub();
+// true: this call is the one a knob condemned (the knob then disarms itself)
+static inline bool stub_fails_now(int &knob)
+{
+    if (knob == 0) { knob = -1; return true; }
+    if (knob > 0) knob--;
+    return false;
+}
+template <typename T>
+static inline hipError_t stub_create(T **out, long &alive, int arg)
+{
+    *out = nullptr;
+    if (stub_fails_now(stub().fail_create_after)) return hipErrorOutOfMemory;
+    *out = new T{arg};
+    alive++;
+    return hipSuccess;
+}
 
 static inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : e == hipErrorOutOfMemory ? "hipErrorOutOfMemory" : "hipError(stub)"; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
@@ -63,14 +82,14 @@ static inline hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemc
 static inline hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t) { memset(dst, v, n); return hipSuccess; }
 static inline hipError_t hipHostRegister(void *, size_t, unsigned) { return hipSuccess; }
 
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = new stub_stream{0}; return hipSuccess; }
-static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int p) { *s = new stub_stream{p}; return hipSuccess; }
-static inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
+static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return stub_create(s, stub().streams, 0); }
+static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int p) { return stub_create(s, stub().streams, p); }
+static inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) stub().streams--; delete s; return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t e, unsigned) { return e ? hipSuccess : hipErrorInvalidValue; }
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = new stub_event{0}; return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = new stub_event{0}; return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return stub_create(e, stub().events, 0); }
+static inline hipError_t hipEventCreate(hipEvent_t *e) { return stub_create(e, stub().events, 0); }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) stub().events--; delete e; return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { if (!e) return hipErrorInvalidValue; e->recorded++; return hipSuccess; }
 static inline hipError_t hipEventSynchronize(hipEvent_t e) { return e ? hipSuccess : hipErrorInvalidValue; }
 static inline hipError_t hipEventQuery(hipEvent_t e) { return e ? hipSuccess : hipErrorInvalidValue; }   // (the stand-in executes everything at once: always complete)

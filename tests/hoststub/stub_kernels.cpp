@@ -28,8 +28,7 @@ static bool is_pinned(const void *p)
 hipError_t hipMalloc(void **p, size_t n)
 {
     stub_state &s = stub();
-    if (s.fail_malloc_after == 0) { s.fail_malloc_after = -1; *p = nullptr; return hipErrorOutOfMemory; }
-    if (s.fail_malloc_after > 0) s.fail_malloc_after--;
+    if (stub_fails_now(s.fail_malloc_after)) { *p = nullptr; return hipErrorOutOfMemory; }
     *p = malloc(n ? n : 1);
     s.device_allocs++;
     return *p ? hipSuccess : hipErrorOutOfMemory;
@@ -37,7 +36,7 @@ hipError_t hipMalloc(void **p, size_t n)
 hipError_t hipFree(void *p) { if (p) { free(p); stub().device_allocs--; } return hipSuccess; }
 hipError_t hipHostMalloc(void **p, size_t n, unsigned)
 {
-    *p = malloc(n ? n : 1);
+    *p = stub_fails_now(stub().fail_host_malloc_after) ? nullptr : malloc(n ? n : 1);
     if (!*p) return hipErrorOutOfMemory;
     stub_state &s = stub();
     std::lock_guard<std::mutex> g(s.m);
@@ -347,7 +346,6 @@ int kp_phase_shift(km_ctx *c, const void *a, const void *b, int dtype, int H, in
     c->phase_path = 1;
     return KM_OK;
 }
-void kp_destroy(km_ctx *) {}
 int kd_run_valid_sum(km_ctx *, km_valid_job *job) { *job = km_valid_job(); return KM_OK; }
 
 // ---- batched units (api_units.hip): every stage touches the first and last byte / element of what the host laid out for it

@@ -267,3 +267,45 @@ def test_early_minmax_of_back_to_back_units_belongs_to_the_right_unit():
     pd.testing.assert_frame_equal(want[3].reset_index(drop=True), p3.result().to_frame().reset_index(drop=True), check_exact=True)
     pd.testing.assert_frame_equal(want[0].reset_index(drop=True), p0.result().to_frame().reset_index(drop=True), check_exact=True)
     ctx.close(); plain.close()
+
+
+def test_contexts_can_be_created_used_and_closed_repeatedly(ops):
+    """Every stream, event and buffer of a context has an owner that releases it with the context (csrc/common.hpp).  Three fresh
+    contexts in turn go through the lazy creation sites a frame stream reaches - stage timers, the copy stream with a ticket, a
+    submitted tile, two pipelined batched submissions with their flush - and are closed; a fourth one, created after all that, still
+    works.  Frames must not depend on which context made them: header and every row of every column equal bit for bit (`same_rows`
+    of tests/test_gpu_units.py: the words as integers - a score below the threshold is a NaN, which no float comparison finds equal
+    to itself - and no further than the last row, behind which a column is device memory no kernel wrote).  (Nothing is
+    measured here: that no handle or allocation is left behind is proven on the CPU against the stand-in HIP layer,
+    tests/test_ctx_lifetime_host.py.)"""
+    from karios_amd._lib import Context, pinned_empty
+    from karios_amd.core import KLTConfiguration
+    from karios_amd.resident import ResidentPair, submit_units
+    from test_gpu_units import same_rows
+    conf = KLTConfiguration(maxCorners=64, blocksize=3, matching_winsize=25)
+    mon, ref = synth.make_pair(128, 512, 0.5, 0.25, seed=5)
+    assert mon.dtype == np.uint16
+
+    def life_of_a_context():
+        ctx = Context(0)
+        ctx.set_profiling(True)
+        mon_p, ref_p = pinned_empty(mon.shape, mon.dtype, ctx), pinned_empty(ref.shape, ref.dtype, ctx)
+        mon_p[:], ref_p[:] = mon, ref
+        pair = ResidentPair.upload(mon_p, ref_p, ctx=ctx)
+        tile = pair.submit_tile(conf, zncc_threshold=0.4)
+        ctx.set_option("units_pipeline", 1)
+        units = [(pair, (0, 0, 512, 64), None), (pair, (0, 64, 512, 64), None)]      # two units of 64 x 512
+        batches = [submit_units(units, conf, 0.4), submit_units(units, conf, 0.4)]
+        assert None not in batches
+        raws = [tile.wait()] + [r for b in batches for r in b.wait()]               # (the last wait flushes the deferred tail)
+        assert all(r.flags == 0 and r.n_rows > 0 for r in raws), [(r.flags, r.n_rows) for r in raws]
+        del pair, tile, batches                  # (the frames' blocks are copies: they outlive the context)
+        ctx.close()
+        assert ctx.handle is None
+        return raws
+
+    first = life_of_a_context()
+    assert len(first) == 5
+    for cycle in (2, 3, 4):                  # (4: the context created after three went through create, use, close)
+        for k, (got, want) in enumerate(zip(life_of_a_context(), first)):
+            assert same_rows(got, want), (cycle, k)
