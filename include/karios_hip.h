@@ -610,6 +610,42 @@ int km_sift_detect_and_compute_dev(km_ctx *ctx, const uint8_t *d_img, int H, int
                                    float *d_size, float *d_angle, float *d_response, int *d_octave, void *d_desc, int desc_dtype,
                                    ptrdiff_t desc_stride, int *count, int64_t *stats);
 
+/* ---- KariosAPI.analyze_accuracy on resident data (api_score.hip, k_accuracy.hip, accuracy_math.hpp) ------------------------------------
+ * The arithmetic is restated in tests/accuracy_restatement.py (the definition the library is held to, bit for bit).
+ *
+ * np.count_nonzero of the monitored raster with the pixels under mask == 0 set to 0 (karios/api/core.py:284-290): an H x W raster
+ * (KM_U8, KM_U16, KM_I16 or KM_F32; anything else KM_E_ARG) with a row stride in elements, mask NULL or H x W uint8 with a row
+ * stride in bytes.  A pixel counts when it is non-zero - float32 by its bits: NaN and denormals count, -0.0 does not - and its
+ * mask byte, if any, is non-zero.  *count is host memory in both forms.  The count is a sum of integers: the same whatever the
+ * order.  The device form's only synchronisation is the copy of the 8-byte result. */
+int km_count_valid_pixels(km_ctx *ctx, const void *img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *mask, ptrdiff_t mask_stride,
+                          int64_t *count);
+int km_count_valid_pixels_dev(km_ctx *ctx, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *d_mask,
+                              ptrdiff_t mask_stride, int64_t *count);
+/* GeometricStat of karios/accuracy_analysis/accuracy_statistics.py: apply_confidence (:82-110), compute_stats (:112-156) and the
+ * sorted radial errors compute_percentile (:224-238) reads, for float32 columns dx, dy, score of n rows (n <= 2^24).
+ * The sample is the rows with (double)score > thr in row order; carto != 0 negates dy first (:73-74).  stats: for x, y and the
+ * score in turn {min, max, median, mean, std} as numpy 2 computes them in float32 (the sum in blocks of 8192 elements, numpy's
+ * pairwise tree inside a block; mean = sum / (float)n; std from the float32 squares of the float32 deviations).  order: for
+ * percent k the elements [k' - 1] and [k'] of the ascending radial errors sqrt(x x + y y), x = dx (float)factor, y = dy (float)factor,
+ * every operation a float32 rounding of its own; p = percents[k] * sample in float64, k' = (int)p, index -1 is the largest element;
+ * NaN where k' is no index (sample == 0, percent >= 1).  The interpolation between the two stays with the caller.  With
+ * n_nan != 0 (a NaN in dx or dy of the sample) minimum, maximum and median are not numpy's: take them from numpy.  sample == 0
+ * leaves stats NaN.  n_percent <= KM_ACC_MAX_PERCENTS.  `out` is host memory in both forms; the device form reads dx, dy and score
+ * from the device and copies nothing else than `out`. */
+#define KM_ACC_MAX_PERCENTS 8
+typedef struct km_accuracy_result {
+    int64_t sample;                            /* rows above the threshold */
+    int64_t n_nan;                             /* ... of which dx or dy is NaN */
+    float stats[15];                           /* {min, max, median, mean, std} of x, of y, of the score */
+    float pad;
+    float order[2 * KM_ACC_MAX_PERCENTS];      /* r[k' - 1], r[k'] per percent */
+} km_accuracy_result;
+int km_accuracy_stats(km_ctx *ctx, const float *dx, const float *dy, const float *score, int n, double thr, int carto, double factor,
+                      int n_percent, const double *percents, km_accuracy_result *out);
+int km_accuracy_stats_dev(km_ctx *ctx, const float *d_dx, const float *d_dy, const float *d_score, int n, double thr, int carto, double factor,
+                          int n_percent, const double *percents, km_accuracy_result *out);
+
 #ifdef __cplusplus
 }
 #endif

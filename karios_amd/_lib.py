@@ -53,6 +53,15 @@ class KmUnit(C.Structure):
                 ("d_mask", C.c_void_p), ("smask", C.c_ssize_t)]
 
 
+ACC_MAX_PERCENTS = 8           # KM_ACC_MAX_PERCENTS
+
+
+class AccuracyResult(C.Structure):
+    """km_accuracy_result of include/karios_hip.h."""
+    _fields_ = [("sample", C.c_int64), ("n_nan", C.c_int64), ("stats", C.c_float * 15), ("pad", C.c_float),
+                ("order", C.c_float * (2 * ACC_MAX_PERCENTS))]
+
+
 UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
 E_ARG = -1                     # KM_E_ARG
 E_UNSUPPORTED = -4             # KM_E_UNSUPPORTED
@@ -162,6 +171,10 @@ SIGNATURES = {
                                         C.POINTER(C.c_int64)]),
     "km_sift_detect_and_compute_dev": (_i, [_vp, _vp, _i, _i, _sz, _i, _i, _d, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _sz, _pi,
                                             C.POINTER(C.c_int64)]),
+    "km_count_valid_pixels": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, C.POINTER(C.c_int64)]),
+    "km_count_valid_pixels_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, C.POINTER(C.c_int64)]),
+    "km_accuracy_stats": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _d, _i, _pd, C.POINTER(AccuracyResult)]),
+    "km_accuracy_stats_dev": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _d, _i, _pd, C.POINTER(AccuracyResult)]),
 }
 
 _lib = None

@@ -187,6 +187,15 @@ enum km_slot {
     WS_SF_DESC,     //   ... and their descriptors
     WS_SF_PERM,     //   the final order
     WS_SF_OUT,      //   results of the host-API form
+    WS_AC_IN,       // api_score.hip (accuracy): dx | dy | score of the host-API form
+    WS_AC_COLS,     //   the sample's columns x | y | c
+    WS_AC_BSUM,     //   sums of the 8192-blocks of the three columns
+    WS_AC_STATE,    //   ka_state, the result block, the pixel count
+    WS_AC_PART,     // k_accuracy.hip: per-workgroup pixel counts
+    WS_AC_FLAG,     //   above-threshold flags and their exclusive scan
+    WS_AC_SCAN,     //   tile sums of that scan
+    WS_AC_KEYS0,    //   order keys of the four columns
+    WS_AC_KEYS1,    //   ... the sort's second buffer
     WS_COUNT
 };
 

@@ -786,3 +786,152 @@ def sift_detect_and_compute(image, *, contrast_threshold: float = 0.02, edge_thr
         st["calls"] = attempt + 1
         out += (st,)
     return out
+
+
+# ---- KariosAPI.analyze_accuracy (csrc/api_score.hip, k_accuracy.hip) ---------------------------------------------------------------
+ACCURACY_STAT_NAMES = tuple(f"{k}_{col}" for col in "xyc" for k in ("min", "max", "median", "mean", "std"))
+ACCURACY_MAX_ROWS = 1 << 24          # beyond it float32(n) is not n: numpy on the host
+
+
+def _on_device(a):
+    return hasattr(a, "data_ptr")
+
+
+def count_valid_pixels(arr, mask=None, ctx: Context | None = None) -> int:
+    """np.count_nonzero of `arr` with the pixels under mask == 0 set to 0 (core.py:284-290): a 2-D uint8 / uint16 / int16 /
+    float32 raster and an optional uint8 mask of its shape, both numpy arrays or both torch tensors on the context's device (rows
+    contiguous, a row stride is fine).  float32 counts by its bits: NaN and denormals are non-zero, -0.0 is zero."""
+    if _on_device(arr):
+        import torch
+        if arr.dim() != 2 or (arr.shape[1] > 1 and arr.stride(1) != 1):
+            raise ValueError("count_valid_pixels: expected a 2-D tensor with contiguous rows")
+        dt = np.dtype(str(arr.dtype).replace("torch.", ""))
+        H, W = int(arr.shape[0]), int(arr.shape[1])
+        stride = int(arr.stride(0)) if H > 1 else W
+        img_arg, mask_arg, mstride = C.c_void_p(arr.data_ptr()), None, 0
+        if mask is not None:
+            if not _on_device(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or (W > 1 and mask.stride(1) != 1):
+                raise ValueError("count_valid_pixels: the mask must be a uint8 tensor of the raster's shape with contiguous rows")
+            mask_arg, mstride = C.c_void_p(mask.data_ptr()), (int(mask.stride(0)) if H > 1 else W)
+        what = "km_count_valid_pixels_dev"
+    else:
+        a = as_image(arr)
+        dt = a.dtype
+        H, W = a.shape
+        stride = row_stride(a)
+        img_arg, mask_arg, mstride = ptr(a), None, 0
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.shape != a.shape:
+                raise ValueError("count_valid_pixels: mask shape differs from the raster's")
+            m = as_image(m if m.dtype == np.uint8 else (m != 0).astype(np.uint8))
+            mask_arg, mstride = ptr(m), row_stride(m)
+        what = "km_count_valid_pixels"
+    if dt not in PREP_DTYPES:
+        raise KariosHipError(f"count_valid_pixels: unsupported pixel type {dt} (uint8, uint16, int16, float32)")
+    if H < 1 or W < 1:
+        return 0
+    c = _ctx(ctx)
+    if _on_device(arr):
+        import torch
+        torch.cuda.synchronize(arr.device)
+    n = C.c_int64()
+    c.check(getattr(c.lib, what)(c.handle, img_arg, _lib._DTYPES[dt], H, W, stride, mask_arg, mstride, C.byref(n)), what)
+    return int(n.value)
+
+
+class AccuracyStatistics:
+    """Result of `accuracy_statistics`: `sample` rows above the threshold, `n_nan` of them with a NaN in dx or dy, `stats` a dict of
+    np.float32 by ACCURACY_STAT_NAMES (None for an empty sample), `ce` one np.float32 per percent (None where the reference's
+    index expression raises IndexError), `path` "device" or "host"."""
+
+    def __init__(self, sample, n_nan, stats, ce, path):
+        self.sample, self.n_nan, self.stats, self.ce, self.path = sample, n_nan, stats, ce, path
+
+
+def _ce_ranks(percent, n):
+    """compute_percentile's indices (accuracy_statistics.py:231-236) -> (k - 1, k, p - k) or None where it raises IndexError."""
+    if n == 0:
+        return None
+    p = float(percent) * n
+    k = int(p)
+    return (k - 1, k, p - k) if 0 <= k < n else None
+
+
+def _accuracy_host(dx, dy, score, confidence, carto, factor, percents):
+    """The reference's own numpy expressions (accuracy_statistics.py:82-238) on host arrays of any dtype."""
+    dx, dy, score = np.asarray(dx), np.asarray(dy), np.asarray(score)
+    keep = score > confidence
+    x, y, c = dx[keep], (-dy if carto else dy)[keep], score[keep]
+    n = int(x.size)
+    n_nan = int(np.count_nonzero(np.isnan(x) | np.isnan(y)))
+    stats = None
+    if n:
+        with np.errstate(invalid="ignore"):
+            vals = [f(v) for v in (x, y, c) for f in (np.min, np.max, np.median, np.mean, np.std)]
+        stats = dict(zip(ACCURACY_STAT_NAMES, vals))
+    ce = []
+    if percents:
+        xs, ys = x * factor, y * factor
+        v_s = np.sort(np.sqrt(xs * xs + ys * ys))
+        for percent in percents:
+            r = _ce_ranks(percent, n)
+            ce.append(None if r is None else v_s[r[0]] + (v_s[r[1]] - v_s[r[0]]) * r[2])
+    return AccuracyStatistics(n, n_nan, stats, tuple(ce), "host")
+
+
+def accuracy_statistics(dx, dy, score, confidence, carto: bool = False, factor=1.0, percents=(0.9, 0.95), ctx: Context | None = None):
+    """GeometricStat's numbers (accuracy_statistics.py:82-238) for the columns dx, dy, score of a frame -> AccuracyStatistics: the
+    sample `score > confidence` (a Python float compares in float32 like `Series.gt`, an np.float64 in float64), dy negated with
+    `carto`, minimum / maximum / median / mean / standard deviation of x, y and the score as numpy computes them in float32, and
+    compute_percentile(percent, factor) for every percent.  float32 numpy arrays, or float32 torch tensors on the context's
+    device: the sample, the sums and the order statistics are computed on the GPU and 96 bytes come back.  numpy on the host takes
+    the call where the GPU form is not defined: columns that are not float32, more than 2^24 rows, an np.float64 `factor` (numpy
+    then computes the radial errors in float64) and - after the device call reported it - a NaN in dx or dy of the sample."""
+    percents = tuple(float(p) for p in percents)
+    dev = _on_device(dx)
+    if dev != _on_device(dy) or dev != _on_device(score):
+        raise ValueError("accuracy_statistics: dx, dy and score must all be numpy arrays or all be device tensors")
+
+    def to_host(a):
+        return a.detach().cpu().numpy() if dev else np.asarray(a)
+
+    cols = (dx, dy, score)
+    if dev:
+        import torch
+        f32_cols = all(a.dtype == torch.float32 and a.dim() == 1 and a.is_contiguous() for a in cols)
+        n = int(dx.shape[0])
+    else:
+        cols = tuple(np.asarray(a) for a in cols)
+        f32_cols = all(a.dtype == np.float32 and a.ndim == 1 for a in cols)
+        n = int(cols[0].shape[0]) if cols[0].ndim else 0
+    if any(int(a.shape[0]) != n for a in cols if len(a.shape)):
+        raise ValueError("accuracy_statistics: dx, dy and score differ in length")
+    if len(percents) > _lib.ACC_MAX_PERCENTS or any(not p >= 0 for p in percents):
+        raise ValueError(f"accuracy_statistics: at most {_lib.ACC_MAX_PERCENTS} percents, none negative")
+    if not f32_cols or n > ACCURACY_MAX_ROWS or isinstance(factor, np.float64) or not isinstance(confidence, (float, int, np.floating, np.integer)):
+        return _accuracy_host(*(to_host(a) for a in cols), confidence, carto, factor, percents)
+    thr = float(confidence) if isinstance(confidence, np.float64) else float(np.float32(confidence))
+    c = _ctx(ctx)
+    if dev:
+        torch.cuda.synchronize(dx.device)
+        args = [C.c_void_p(a.data_ptr()) if n else None for a in cols]
+        what = "km_accuracy_stats_dev"
+    else:
+        cols = tuple(np.ascontiguousarray(a) for a in cols)
+        args = [ptr(a) if n else None for a in cols]
+        what = "km_accuracy_stats"
+    res = _lib.AccuracyResult()
+    q = (C.c_double * max(len(percents), 1))(*percents)
+    c.check(getattr(c.lib, what)(c.handle, *args, n, thr, int(bool(carto)), float(np.float32(factor)), len(percents), q, C.byref(res)), what)
+    if res.n_nan:
+        return _accuracy_host(*(to_host(a) for a in cols), confidence, carto, factor, percents)
+    sample = int(res.sample)
+    stats = dict(zip(ACCURACY_STAT_NAMES, np.array(res.stats, np.float32))) if sample else None
+    order = np.array(res.order, np.float32)
+    ce = []
+    for k, percent in enumerate(percents):
+        r = _ce_ranks(percent, sample)
+        # the interpolation of accuracy_statistics.py:237 on the two float32 order statistics (the fraction is a Python float)
+        ce.append(None if r is None else order[2 * k] + (order[2 * k + 1] - order[2 * k]) * r[2])
+    return AccuracyStatistics(sample, 0, stats, tuple(ce), "device")

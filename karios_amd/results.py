@@ -6,7 +6,9 @@
   * `filter_by_dn_values`  - `KariosAPI._filter_by_dn_values` (core.py:650-737): drop the key points under which the
                               reference or monitored image holds one of the excluded DN values / its no-data value;
   * `_check_quality`       - `KariosAPI._check_quality` (core.py:491-506): the dynamic range between the 2nd and 98th percentile
-                              of both rasters, a warning when it is 10 or less.
+                              of both rasters, a warning when it is 10 or less;
+  * `analyze_accuracy`     - `KariosAPI.analyze_accuracy` (core.py:268-328): valid pixels of the monitored raster under the mask,
+                              `GeometricStat`'s statistics, CE90 / CE95 and the line of `correl_res.txt`.
 
 The pixel work (ZNCC, MI / NMI, DN gather) runs on the device through `ResidentPair`; the column arithmetic and the
 CSV formatting are the reference's own numpy / pandas expressions.
@@ -14,6 +16,7 @@ CSV formatting are the reference's own numpy / pandas expressions.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Iterable
 
@@ -24,6 +27,8 @@ import pandas as pd
 
 from . import ops
 from ._lib import KariosHipError
+from .accuracy_analysis import GeometricStat
+from .core.configuration import AccuracyAnalysisConfiguration
 from .frames import radial_angle_columns
 from .resident import ResidentPair
 
@@ -102,3 +107,44 @@ def _check_quality(monitored_image, reference_image) -> tuple:
     if min_max_ref[1] - min_max_ref[0] <= 10:
         logger.warning("Low dynamic range detected for reference, you could get poor results")
     return min_max_mon, min_max_ref
+
+
+@dataclass
+class AccuracyAnalysis:
+    """Result of `analyze_accuracy` (the reference's dataclass of the same name, core.py:79-90)."""
+
+    statistics: GeometricStat
+    mean_x: float
+    mean_y: float
+    std_x: float
+    std_y: float
+    ce90: float
+    ce95: float
+    valid_pixels: int
+    total_pixels: int
+
+
+def analyze_accuracy(points, pair: ResidentPair, confidence_threshold: float = 0.4, carto: bool = False, pixel_size=None,
+                     stats_file=None, ref_name: str = "ref", mon_name: str = "mon") -> AccuracyAnalysis:
+    """`KariosAPI.analyze_accuracy` (core.py:268-328) for the points of `match_images` and the pair they came from: the valid
+    pixels of the monitored raster under the pair's mask are counted where the raster lives (`ops` / km_count_valid_pixels_dev on
+    pair.mon_ptr / pair.mask_ptr), the statistics and CE90 / CE95 come from `GeometricStat` on the GPU.  `carto`: the monitored
+    image has a pixel resolution (`have_pixel_resolution()`); `pixel_size`: the resolution CE is scaled by (None: 1.0, core.py:314);
+    `stats_file`: where the line of `correl_res.txt` goes (None: not written)."""
+    c = pair.ctx
+    pair._ready()
+    stats = GeometricStat(AccuracyAnalysisConfiguration(confidence_threshold=confidence_threshold), points, carto, ctx=c)
+    n = C.c_int64()
+    c.check(c.lib.km_count_valid_pixels_dev(c.handle, C.c_void_p(pair.mon_ptr), pair.code, pair.y_size, pair.x_size, pair.x_size,
+                                            C.c_void_p(pair.mask_ptr) if pair.mask_ptr else None, pair.x_size, C.byref(n)),
+            "km_count_valid_pixels_dev")
+    nb_valid_pixel = int(n.value)
+    total_pixels = pair.x_size * pair.y_size
+    stats.compute_stats(nb_valid_pixel)
+    if stats_file is not None:
+        stats.update_statistic_file(ref_name, mon_name, str(stats_file))
+    img_res = pixel_size if pixel_size is not None else 1.0
+    ce90 = stats.compute_percentile(0.9, img_res)
+    ce95 = stats.compute_percentile(0.95, img_res)
+    return AccuracyAnalysis(statistics=stats, mean_x=stats.mean_x, mean_y=stats.mean_y, std_x=stats.std_x, std_y=stats.std_y, ce90=ce90,
+                            ce95=ce95, valid_pixels=nb_valid_pixel, total_pixels=total_pixels)
