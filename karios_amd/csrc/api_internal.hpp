@@ -68,6 +68,3 @@ int mark_lk_start(km_ctx *c);                        // records ev_lk_start on c
 int frame_sink_check(km_ctx *c, size_t pitch, int n, size_t ob);
 int frame_slot_reserve(km_ctx *c, km_frame_slot *slot, size_t bytes);
 int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, size_t ob, size_t ob_al, int n, void *sink, size_t sink_pitch, hipStream_t s);
-
-// api_units.hip: Laplacian kernel sizes the batched stretch + Laplacian pass covers (k_dense.hip kd_stretch_laplacian_units)
-static inline bool km_units_ksize_supported(int k) { return k >= 1 && k <= 11 && (k & 1); }

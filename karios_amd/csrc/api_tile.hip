@@ -327,7 +327,7 @@ static int klt_tile_dev_impl(km_ctx *c, km_call_modes &m, const void *d_ref, con
             km_on_stream on(c, c->aux_stream);
             {
                 km_stage_timer t(c, ST_MINMAX);
-                if ((rc = kd_minmax_pair_ws(c, d_ref, d_mon, dtype, H, W, sref, smon, mm_early, WS_MM_PARTIAL))) return rc;
+                if ((rc = kd_minmax(c, d_ref, dtype, H, W, sref, mm_early, d_mon, smon, WS_MM_PARTIAL))) return rc;
             }
             if ((rc = km_record(c, c->ev_mm, c->aux_stream))) return rc;
         }
@@ -336,7 +336,7 @@ static int klt_tile_dev_impl(km_ctx *c, km_call_modes &m, const void *d_ref, con
         c->stats.path_flags |= KM_PATH_MM_EARLY;
     } else if (dtype != KM_U8) {
         km_stage_timer t(c, ST_MINMAX);
-        if ((rc = kd_minmax_pair(c, d_ref, d_mon, dtype, H, W, sref, smon, &sc->mm[0]))) return rc;
+        if ((rc = kd_minmax(c, d_ref, dtype, H, W, sref, &sc->mm[0], d_mon, smon))) return rc;
     }   // (u8 input: mm stays 0 from the scalar block the entry point zeroed)
     {
         km_stage_timer t(c, ST_LAPLACIAN);
@@ -676,7 +676,7 @@ int km_klt_auto_ksize_frame_dev(km_ctx *c, const void *d_ref, const void *d_mon,
     }
     if (dtype != KM_U8) {
         km_stage_timer t(c, ST_MINMAX);
-        if ((rc = kd_minmax_pair(c, d_ref, d_mon, dtype, H, W, sref, smon, &sc->mm[0]))) return rc;
+        if ((rc = kd_minmax(c, d_ref, dtype, H, W, sref, &sc->mm[0], d_mon, smon))) return rc;
     }
     // ---- arena: 2*nk Laplacians, 2*nk pyramids, nk corner lists, nk*nk track pairs, counters
     km_pyr probe;

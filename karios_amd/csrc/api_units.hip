@@ -183,7 +183,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     if (!spec_path_covers(c, prm) || prm->max_level != 1 || cap > 32768) return KM_E_UNSUPPORTED;
     if (prm->block_size < 1 || prm->block_size > 15 || (prm->block_size & 1) == 0 || !c->opt_eig3 || !c->opt_lk2 || prm->win_size <= 2 || prm->win_size > 40)
         return KM_E_UNSUPPORTED;
-    if (!km_units_ksize_supported(prm->ksize_ref) || !km_units_ksize_supported(prm->ksize_mon)) return KM_E_UNSUPPORTED;
+    if (!km_lap_ksize_ok(prm->ksize_ref) || !km_lap_ksize_ok(prm->ksize_mon)) return KM_E_UNSUPPORTED;
     const bool with_zncc = units[0].d_ref_full != nullptr;
     const bool user_mask = units[0].d_mask != nullptr;
     const bool with_mi = with_zncc && c->opt_frame_mi;

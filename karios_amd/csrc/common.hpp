@@ -137,7 +137,7 @@ enum km_slot {
     WS_FFT_TW1,
     WS_FFT_TOP2,    // per-row (largest, second-largest) |cc| of the last inverse pass
     WS_MI_TABLE,    // c ln c, c = 0 .. 57^2 (k_mi.hip)
-    WS_LAP_VALID,   // k_dense.hip: per-wave counts of valid pixels of the Laplacian pass (summed later, maybe on the second stream)
+    WS_LAP_VALID,   // k_lap.hip: per-wave counts of valid pixels of the Laplacian pass (summed later, maybe on the second stream)
     WS_FRAME_CNT,   // k_frame.hip: per-workgroup counts of the compaction (a slot of its own: the frame stage of unit k may run beside the Laplacian / eigenvalue kernels of unit k + 1, which own WS_PARTIAL)
     WS_F64_TWX,     // k_fft64.hip: exp(-2 pi i j / W), exp(-2 pi i j / H) ...
     WS_F64_TWY,
@@ -426,13 +426,15 @@ __device__ __forceinline__ bool km_xcd_tile(unsigned ntiles, unsigned &tile)
 
 // Rows per work item of a marching kernel (one wavefront walks `rows` output rows of one column strip, re-reading
 // `halo` rows): the value in [lo, hi] that minimises  ceil(items / wave_slots) * (rows + halo), i.e. whole rounds of
-// resident waves times the work of one item - a grid that needs 2.02 rounds costs three.
-static inline int km_pick_rows(int H, int nstrips, int halo, long wave_slots, int lo, int hi)
+// resident waves times the work of one item - a grid that needs 2.02 rounds costs three.  A batch of n units: the items
+// of all units' strips share the resident waves (one unit: km_pick_rows).
+static inline int km_pick_rows_units(const int *H, const int *nstrips, int n, int halo, long wave_slots, int lo, int hi)
 {
     int best = lo;
     double best_cost = 1e300;
     for (int r = lo; r <= hi; r++) {
-        const long items = (long)nstrips * ((H + r - 1) / r);
+        long items = 0;
+        for (int u = 0; u < n; u++) items += (long)nstrips[u] * ((H[u] + r - 1) / r);
         const long rounds = (items + wave_slots - 1) / wave_slots;
         // a thinly filled last round still lasts about half an item (fewer waves per SIMD, each one faster)
         const double last = (double)(items - (rounds - 1) * wave_slots) / (double)wave_slots;
@@ -440,6 +442,10 @@ static inline int km_pick_rows(int H, int nstrips, int halo, long wave_slots, in
         if (cost < best_cost) { best_cost = cost; best = r; }
     }
     return best;
+}
+static inline int km_pick_rows(int H, int nstrips, int halo, long wave_slots, int lo, int hi)
+{
+    return km_pick_rows_units(&H, &nstrips, 1, halo, wave_slots, lo, hi);
 }
 void *km_ws(km_ctx *ctx, int slot, size_t bytes);  // nullptr on failure (error set); the slot of the context's current lane
 void *km_ws_peek(km_ctx *ctx, int slot);           // the slot's current buffer (no growth)
@@ -509,6 +515,22 @@ static inline size_t km_any_dtype_size(int dtype)
     return dtype == KM_F64 ? 8 : (dtype == KM_I32 || dtype == KM_U32) ? 4 : km_dtype_size(dtype);
 }
 
+// The pixel type of a KM_U8 / KM_U16 / KM_I16 / KM_F32 code: returns f(T()) with T the type, f a generic callable that returns a KM_*
+// code - the launchers whose kernels differ in T alone.  Another code: KM_E_ARG with the caller's wording (`bad_fmt` takes the code).
+template <typename F>
+static inline int km_with_pixel_type(km_ctx *c, int dtype, const char *bad_fmt, F &&f)
+{
+    switch (dtype) {
+    case KM_U8: return f(uint8_t());
+    case KM_U16: return f(uint16_t());
+    case KM_I16: return f(int16_t());
+    case KM_F32: return f(float());
+    default: return km_fail(c, KM_E_ARG, bad_fmt, dtype);
+    }
+}
+// Laplacian kernel sizes the stretch + Laplacian pass covers (k_lap.hip lap_make_plan; api_units.hip asks before it builds a batch)
+static inline bool km_lap_ksize_ok(int k) { return k >= 1 && k <= 11 && (k & 1); }
+
 // per-unit arguments of the batched scoring kernels (k_zncc.hip, k_mi.hip): by value in the kernel arguments
 struct km_score_unit {
     const void *ref, *mon;                // rasters the chips are cut from
@@ -524,18 +546,23 @@ struct km_score_units {
 };
 
 // ---- launchers implemented in the kernel translation units (all asynchronous) ----
-// k_dense.hip
-int kd_minmax(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride,
-              double *d_mm /* [2] */);
-int kd_minmax_pair_ws(km_ctx *c, const void *d_a, const void *d_b, int dtype, int H, int W, ptrdiff_t sa, ptrdiff_t sb, double *d_mm, int ws_slot);
-int kd_minmax_pair(km_ctx *c, const void *d_a, const void *d_b, int dtype, int H, int W, ptrdiff_t sa, ptrdiff_t sb,
-                   double *d_mm /* [4]: min_a, max_a, min_b, max_b */);
+// k_raster.hip
+// min / max of one image (d_b == nullptr: d_mm[0..1]) or of both rasters of a pair in one launch (d_mm = {min_a, max_a, min_b, max_b});
+// the partials go to a workspace slot of the caller's choice (the early min / max of the next unit runs beside kernels that use WS_PARTIAL)
+int kd_minmax(km_ctx *c, const void *d_a, int dtype, int H, int W, ptrdiff_t sa, double *d_mm, const void *d_b = nullptr, ptrdiff_t sb = 0,
+              int ws_slot = WS_PARTIAL);
 int kd_to_uint8(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride,
                 const double *d_mm, int invert, uint8_t *d_out);
 int kd_auto_mask(km_ctx *c, const void *d_mon, const void *d_ref, int dtype, int H, int W,
                  ptrdiff_t stride_mon, ptrdiff_t stride_ref, const double *nodata_mon,
                  const double *nodata_ref, uint8_t *d_mask, unsigned long long *d_valid);
 int kd_count_nonzero(km_ctx *c, const uint8_t *d_mask, size_t n, unsigned long long *d_valid);
+// final reductions of n per-workgroup partials on c->stream (one workgroup; *d_out is written, not accumulated)
+int kd_sum_u32(km_ctx *c, const unsigned *d_partial, unsigned n, unsigned long long *d_out);
+int kd_max_u32(km_ctx *c, const unsigned *d_partial, unsigned n, unsigned *d_out);
+int kd_shift_image(km_ctx *c, const void *d_img, int elem_size, int H, int W, ptrdiff_t stride,
+                   int y_off, int x_off, void *d_out);
+// k_lap.hip
 // the sum of the per-item valid-pixel counts of kd_stretch_laplacian_pair, left to the caller (partial == nullptr: nothing pending)
 struct km_valid_job {
     const unsigned *partial = nullptr;
@@ -551,6 +578,7 @@ int kd_stretch_laplacian_pair(km_ctx *c, const void *d_ref, const void *d_mon, i
                               int invert_mon, const double *nodata_ref, const double *nodata_mon,
                               uint8_t *d_lap_ref, uint8_t *d_lap_mon, uint8_t *d_mask_out,
                               unsigned long long *d_valid, km_valid_job *defer = nullptr);   // defer: the sum into d_valid becomes the caller's job (null: summed now)
+// k_eigmap.hip: the two-kernel form (kd_min_eigen here, kd_candidates below)
 int kd_min_eigen(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block,
                  float *d_eig, unsigned int *d_max_key);
 // k_frame.hip: DN-value filter of the key points (core.py:650-737)
@@ -572,12 +600,12 @@ int k2_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, in
 // k_eig3.hip
 int k3_eig_candidates(km_ctx *c, const uint8_t *d_src, const uint8_t *d_mask, int H, int W, int block, double quality, km_scalars *sc,
                       unsigned long long *d_keys, size_t cap, km_eig_partials *partials = nullptr);
+// k_eigmap.hip
 int kd_candidates(km_ctx *c, const float *d_eig, const uint8_t *d_mask, int H, int W,
                   double quality, km_scalars *d_sc, unsigned long long *d_keys, size_t cap, bool rezero);
+// k_raster.hip
 int kd_pyrdown_u8(km_ctx *c, const uint8_t *d_src, int H, int W, uint8_t *d_dst);
 int kd_pyrdown_u8_pair(km_ctx *c, const uint8_t *d_src_a, const uint8_t *d_src_b, int H, int W, uint8_t *d_dst_a, uint8_t *d_dst_b);
-int kd_shift_image(km_ctx *c, const void *d_img, int elem_size, int H, int W, ptrdiff_t stride,
-                   int y_off, int x_off, void *d_out);
 // k_select.hip
 int ks_sort_keys_desc(km_ctx *c, unsigned long long *d_keys, size_t n, unsigned long long **d_sorted);
 // k_sort.hip: the ordering primitives of the exact fallback paths (hand-written; no library)

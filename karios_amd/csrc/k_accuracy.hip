@@ -245,13 +245,8 @@ __global__ void ka_empty_kernel(ka_state *st, km_accuracy_result *out)
 int ka_count_valid(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *d_mask, ptrdiff_t mask_stride,
                    unsigned long long *d_count)
 {
-    switch (dtype) {
-    case KM_U8: return count_valid_t<uint8_t>(c, d_img, H, W, stride, d_mask, mask_stride, d_count);
-    case KM_U16: return count_valid_t<uint16_t>(c, d_img, H, W, stride, d_mask, mask_stride, d_count);
-    case KM_I16: return count_valid_t<int16_t>(c, d_img, H, W, stride, d_mask, mask_stride, d_count);
-    case KM_F32: return count_valid_t<float>(c, d_img, H, W, stride, d_mask, mask_stride, d_count);
-    default: return km_fail(c, KM_E_ARG, "count_valid_pixels: bad dtype %d", dtype);
-    }
+    return km_with_pixel_type(c, dtype, "count_valid_pixels: bad dtype %d",
+                              [&](auto t) { return count_valid_t<decltype(t)>(c, d_img, H, W, stride, d_mask, mask_stride, d_count); });
 }
 
 int ka_compact(km_ctx *c, const float *d_dx, const float *d_dy, const float *d_score, int n_max, double thr, int carto, float *d_cols, ka_state *st)

@@ -2,7 +2,7 @@
 // karios/matcher/klt.py:120, 494; algorithm SURVEY.md App. A.2: Sobel 3x3 REFLECT_101 -> products -> box filter
 // blockSize x blockSize with its own REFLECT_101 border on the product images -> lambda_min) + its maximum over the mask.
 //
-// Same arithmetic as eig_kernel (k_dense.hip) - exact integer sums, fp64 scaling, individually rounded float32
+// Same arithmetic as eig_kernel (k_eigmap.hip) - exact integer sums, fp64 scaling, individually rounded float32
 // operations, correctly rounded sqrt - in the register-light formulation found with the fused experiment (k_eigc.hip):
 //   * one wavefront owns 128 columns (2 per lane, one 16-bit load per row) and marches down its rows;
 //   * vertical box sum  V += P(row entering) - P(row leaving): the products of BOTH rows are recomputed from the source

@@ -1178,13 +1178,7 @@ int kp_phase_shift_f64(km_ctx *c, const void *d_a, const void *d_b, int dtype, i
         last.want_best = true;
         if (dtype != KM_U8 && dtype != KM_U16 && dtype != KM_I16 && dtype != KM_F32) return km_fail(c, KM_E_ARG, "phase_shift: bad dtype %d", dtype);
     } else {
-        switch (dtype) {
-        case KM_U8: rc = launch_pack<uint8_t>(c, d_a, d_b, stride_a, stride_b, H, W, z); break;
-        case KM_U16: rc = launch_pack<uint16_t>(c, d_a, d_b, stride_a, stride_b, H, W, z); break;
-        case KM_I16: rc = launch_pack<int16_t>(c, d_a, d_b, stride_a, stride_b, H, W, z); break;
-        case KM_F32: rc = launch_pack<float>(c, d_a, d_b, stride_a, stride_b, H, W, z); break;
-        default: return km_fail(c, KM_E_ARG, "phase_shift: bad dtype %d", dtype);
-        }
+        rc = km_with_pixel_type(c, dtype, "phase_shift: bad dtype %d", [&](auto t) { return launch_pack<decltype(t)>(c, d_a, d_b, stride_a, stride_b, H, W, z); });
         if (rc) return rc;
     }
 

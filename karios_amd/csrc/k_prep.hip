@@ -406,22 +406,15 @@ int kp_order_statistics(km_ctx *c, const void *d_src, int dtype, int H, int W, p
     kp_q4 q4;
     for (int j = 0; j < KP_MAX_Q; j++) q4.q[j] = j < n_q ? q[j] : 0.0;
     KM_HIP(c, hipMemsetAsync(st, 0, sizeof(kp_state), c->stream));
+    return km_with_pixel_type(c, dtype, "order_statistics: dtype %d (uint8, uint16, int16 and float32 only)", [&](auto t) {
+        using T = decltype(t);
 #ifdef KM_DEV   // the per-pixel-atomic form exists in the development build only (the A/B of DESIGN 12.1)
-#define KP_RUN(T)                                                                                              \
-    (plain ? select_run<T, true>(c, (const T *)d_src, H, W, ss, exclude, q4, n_q, st)                          \
-           : select_run<T, false>(c, (const T *)d_src, H, W, ss, exclude, q4, n_q, st))
+        if (plain) return select_run<T, true>(c, (const T *)d_src, H, W, ss, exclude, q4, n_q, st);
 #else
-    (void)plain;
-#define KP_RUN(T) select_run<T, false>(c, (const T *)d_src, H, W, ss, exclude, q4, n_q, st)
+        (void)plain;
 #endif
-    switch (dtype) {
-    case KM_U8: return KP_RUN(uint8_t);
-    case KM_U16: return KP_RUN(uint16_t);
-    case KM_I16: return KP_RUN(int16_t);
-    case KM_F32: return KP_RUN(float);
-    }
-#undef KP_RUN
-    return km_fail(c, KM_E_ARG, "order_statistics: dtype %d (uint8, uint16, int16 and float32 only)", dtype);
+        return select_run<T, false>(c, (const T *)d_src, H, W, ss, exclude, q4, n_q, st);
+    });
 }
 
 int kp_stretch(km_ctx *c, const void *d_src, int dtype, int H, int W, ptrdiff_t ss, double lo, double hi, uint8_t *d_dst, ptrdiff_t ds)
@@ -433,13 +426,11 @@ int kp_stretch(km_ctx *c, const void *d_src, int dtype, int H, int W, ptrdiff_t 
         return KM_OK;
     }
     const double range = hi - lo;
-    switch (dtype) {
-    case KM_U8: stretch_kernel<uint8_t><<<g, 256, 0, c->stream>>>((const uint8_t *)d_src, ss, H, W, lo, range, d_dst, ds); break;
-    case KM_U16: stretch_kernel<uint16_t><<<g, 256, 0, c->stream>>>((const uint16_t *)d_src, ss, H, W, lo, range, d_dst, ds); break;
-    case KM_I16: stretch_kernel<int16_t><<<g, 256, 0, c->stream>>>((const int16_t *)d_src, ss, H, W, lo, range, d_dst, ds); break;
-    case KM_F32: stretch_kernel<float><<<g, 256, 0, c->stream>>>((const float *)d_src, ss, H, W, lo, range, d_dst, ds); break;
-    default: return km_fail(c, KM_E_ARG, "stretch_percentile_u8: dtype %d (uint8, uint16, int16 and float32 only)", dtype);
-    }
+    if (int rc = km_with_pixel_type(c, dtype, "stretch_percentile_u8: dtype %d (uint8, uint16, int16 and float32 only)", [&](auto t) {
+            using T = decltype(t);
+            stretch_kernel<T><<<g, 256, 0, c->stream>>>((const T *)d_src, ss, H, W, lo, range, d_dst, ds);
+            return KM_OK;
+        })) return rc;
     KM_LAUNCH_CHECK(c);
     return KM_OK;
 }

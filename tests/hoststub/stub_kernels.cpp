@@ -117,15 +117,11 @@ static void minmax_of(const void *img, int dtype, int H, int W, ptrdiff_t stride
     mm[0] = mn; mm[1] = mx;
 }
 
-int kd_minmax(km_ctx *, const void *d, int dtype, int H, int W, ptrdiff_t s, double *mm) { minmax_of(d, dtype, H, W, s, mm); return KM_OK; }
-int kd_minmax_pair(km_ctx *, const void *a, const void *b, int dtype, int H, int W, ptrdiff_t sa, ptrdiff_t sb, double *mm)
+int kd_minmax(km_ctx *, const void *a, int dtype, int H, int W, ptrdiff_t sa, double *mm, const void *b, ptrdiff_t sb, int)
 {
-    minmax_of(a, dtype, H, W, sa, mm); minmax_of(b, dtype, H, W, sb, mm + 2);
+    minmax_of(a, dtype, H, W, sa, mm);
+    if (b) minmax_of(b, dtype, H, W, sb, mm + 2);
     return KM_OK;
-}
-int kd_minmax_pair_ws(km_ctx *c, const void *a, const void *b, int dtype, int H, int W, ptrdiff_t sa, ptrdiff_t sb, double *mm, int)
-{
-    return kd_minmax_pair(c, a, b, dtype, H, W, sa, sb, mm);
 }
 int kd_to_uint8(km_ctx *, const void *d, int dtype, int H, int W, ptrdiff_t s, const double *mm, int invert, uint8_t *out)
 {

@@ -106,6 +106,43 @@ def test_tile_prefilter_bit_exact(ops, O, dtype, span, shape):
         assert mk2 is None and nv2 is None and np.array_equal(lr2, want_r) and np.array_equal(lm2, want_m)
 
 
+def _plan_boundary_pair(dtype, shape):
+    """A small pair for the plan's boundaries: full-range values, zeros, the no-data values 7 (ref) and 9 (mon), a few NaN in float32."""
+    span = {"uint8": 255, "uint16": 12345, "int16": 1020, "float32": 4000}[np.dtype(dtype).name]
+    ref, mon = _prefilter_case(dtype, shape, span, seed=shape[0] * 100 + shape[1])
+    ref[2, 3] = ref[3, 1] = 7
+    mon[4, 1] = 9
+    if np.dtype(dtype) == np.float32:
+        ref[ref != ref] = 11.0                                  # (the NaN of _prefilter_case are random: place them here instead)
+        ref[1, 2] = mon[shape[0] - 2, shape[1] - 3] = ref[5, 5] = np.nan
+    return ref, mon
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.int16, np.float32])
+def test_tile_prefilter_bit_exact_at_the_plan_boundaries(ops, O, dtype):
+    """The switch between the marching and the general form of the stretch + Laplacian pass (k_lap.hip lap_make_plan): 8 x 8 for radius
+    <= 4, 16 x 16 for radius 5 - shapes either side of both thresholds in each dimension, kernel pairs of every radius, mixed sizes and
+    11 beside 1.  `test_tile_prefilter_bit_exact` starts at 50 x 253 and only ever takes the marching form."""
+    for shape in [(7, 40), (40, 7), (8, 8), (8, 9), (15, 16), (16, 15), (16, 16), (15, 40)]:
+        ref, mon = _plan_boundary_pair(dtype, shape)
+        u8 = {inv: O.to_uint8(mon, invert=inv) for inv in (False, True)}
+        u8_ref = O.to_uint8(ref)
+        masks = {nd: O.auto_mask(mon, ref, nodata_mon=nd[1], nodata_ref=nd[0]) for nd in [(None, None), (7.0, 9.0)]}
+        for kr, km in [(1, 1), (7, 7), (3, 9), (9, 9), (11, 11), (11, 1)]:
+            inv = (kr, km) in [(3, 9), (11, 1)]
+            nr, nm = (7.0, 9.0) if (kr, km) == (3, 9) else (None, None)            # the one no-data pair
+            what = (shape, kr, km)
+            want_r, want_m = O.laplacian_u8(u8_ref, kr), O.laplacian_u8(u8[inv], km)
+            want_mask, want_valid = masks[(nr, nm)]
+            lr, lm, mk, nv = ops.tile_prefilter(ref, mon, nodata_ref=nr, nodata_mon=nm, ref_ksize=kr, mon_ksize=km, invert_mon=inv)
+            assert np.array_equal(lr, want_r), what
+            assert np.array_equal(lm, want_m), what
+            assert np.array_equal(mk, want_mask), what
+            assert nv == want_valid, what
+            lr2, lm2, mk2, nv2 = ops.tile_prefilter(ref, mon, ref_ksize=kr, mon_ksize=km, invert_mon=inv, with_mask=False)
+            assert mk2 is None and nv2 is None and np.array_equal(lr2, want_r) and np.array_equal(lm2, want_m), what
+
+
 @pytest.mark.parametrize("ksize", [1, 3, 5, 7, 9, 11])
 def test_laplacian_bit_exact(ops, O, ksize):
     for i, shape in enumerate(SHAPES):

@@ -289,7 +289,7 @@ print("rank", rank, "ok")
 
 
 def test_stretch_exact_multiples():
-    """The integer formulation of `_to_uint8` the HIP kernels use (k_dense.hip, "uint8 stretch of 16-bit integer images"):
+    """The integer formulation of `_to_uint8` the HIP kernels use (k_lap.hip, "uint8 stretch of 16-bit integer images"):
     numpy's trunc(fl(fl(d / r) * 255)) equals floor(255 * d / r) for every integer d in [0, r], r <= 65535 - in
     particular at the exact multiples 255 * d == k * r, where only fl(k / 255) * 255 >= k keeps the truncation at k."""
     k = np.arange(256, dtype=np.float64)
@@ -301,6 +301,62 @@ def test_stretch_exact_multiples():
         assert np.array_equal(want, got.astype(np.uint8)), r
         fma_form = np.floor(d.astype(np.float64) * (255.0 / r) + 0.5 / r)          # what the kernel evaluates (one fma)
         assert np.array_equal(fma_form.astype(np.int64), got), r
+
+
+def _pick_rows_restated(units, halo, slots, lo, hi):
+    """The rows choice as the marching Laplacian's launcher spelled it before it shared km_pick_rows_units with km_pick_rows
+    (common.hpp): whole rounds of resident waves x the work of one item, over the items of every unit; the first minimum wins."""
+    best, rows = 1e300, lo
+    for r in range(lo, hi + 1):
+        items = sum(s * ((H + r - 1) // r) for H, s in units)
+        rounds = (items + slots - 1) // slots
+        last = float(items - (rounds - 1) * slots) / float(slots)
+        cost = (float(rounds - 1) + 0.5 + 0.5 * last) * float(r + halo)
+        if cost < best:
+            best, rows = cost, r
+    return rows
+
+
+def test_laplacian_rows_choice_is_km_pick_rows(tmp_path):
+    """k_lap.hip lapm_items takes its rows per item from km_pick_rows_units (common.hpp), the function km_pick_rows is the one-unit case
+    of: for one unit both return the restated choice, for a batch the same formula over the sum of the units' items.  Host code only:
+    common.hpp compiles with g++ against the stand-in HIP header of tests/hoststub."""
+    import subprocess
+    src, exe, cases = tmp_path / "rows.cpp", tmp_path / "rows", tmp_path / "cases.txt"
+    src.write_text(r'''
+#include "common.hpp"
+#include <stdio.h>
+int main(int argc, char **argv)
+{
+    FILE *f = fopen(argv[1], "r");
+    if (!f) return 2;
+    int halo, n;
+    long slots;
+    while (fscanf(f, "%d %ld %d", &halo, &slots, &n) == 3) {
+        int H[KM_UNITS_MAX], s[KM_UNITS_MAX];
+        if (n < 1 || n > KM_UNITS_MAX) return 2;
+        for (int u = 0; u < n; u++) if (fscanf(f, "%d %d", &H[u], &s[u]) != 2) return 2;
+        printf("%d %d\n", km_pick_rows_units(H, s, n, halo, slots, 32, 160), n == 1 ? km_pick_rows(H[0], s[0], halo, slots, 32, 160) : -1);
+    }
+    return 0;
+}
+''')
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "karios_amd", "csrc"),
+                           "-I", os.path.join(ROOT, "tests", "hoststub"), str(src), "-o", str(exe)])
+    rng = np.random.default_rng(11)
+    single = [(2 * R, slots, [(H, s)]) for H in (8, 33, 512, 3000, 10980) for s in (1, 3, 13, 45) for R in range(1, 6) for slots in (2048, 4096)]
+    mixes = [(2 * int(rng.integers(1, 6)), int(rng.choice([1024, 2048, 4096, 8192])),
+              [(int(rng.choice([8, 33, 512, 1830, 3000, 5490, 10980])), int(rng.integers(1, 46))) for _ in range(int(rng.integers(2, 17)))]) for _ in range(80)]
+    mixes.append((8, 4096, [(5490, 23)] * 16))
+    cases.write_text("".join(f"{halo} {slots} {len(u)} " + " ".join(f"{H} {s}" for H, s in u) + "\n" for halo, slots, u in single + mixes))
+    out = subprocess.run([str(exe), str(cases)], capture_output=True, text=True, timeout=120, check=True).stdout.split("\n")
+    got = [tuple(int(v) for v in line.split()) for line in out if line]
+    assert len(got) == len(single) + len(mixes)
+    for (halo, slots, units), (rows_units, rows_one) in zip(single + mixes, got):
+        want = _pick_rows_restated(units, halo, slots, 32, 160)
+        assert rows_units == want, (halo, slots, units, rows_units, want)
+        assert rows_one == (want if len(units) == 1 else -1), (halo, slots, units, rows_one, want)
+    assert len({g[0] for g in got}) > 10            # (the sweep reaches many different choices, not one clamp value)
 
 
 def test_oracle_thread_team_respects_the_cpu_quota(O):
@@ -505,7 +561,7 @@ def test_inline_assembly_hazard_scan_of_the_device_code(tmp_path):
         pytest.skip("hipcc not available")
     csrc = os.path.join(ROOT, "karios_amd", "csrc")
     srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith(".hip") and ("asm" in open(os.path.join(csrc, f)).read() or f in ("k_eig2.hip", "k_eig3.hip"))]
-    assert {"k_eig3.hip", "k_lk.hip", "k_dense.hip", "k_fft.hip"} <= set(srcs), srcs
+    assert {"k_eig3.hip", "k_lk.hip", "k_lap.hip", "k_fft.hip"} <= set(srcs), srcs
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
              "-fno-gpu-flush-denormals-to-zero", "-I/opt/rocm/include", "--cuda-device-only", "-S"]      # (the Makefile's flags)
 

@@ -119,7 +119,7 @@ def test_laplacian_vs_scipy(O, ksize):
 
 
 def test_laplacian_11_is_the_binomial_of_the_unsaturated_laplacian_9(O):
-    """What the marching kernel's radius-5 form rests on (k_dense.hip lap_march_item): OpenCV's size-11 derivative / smoothing kernels
+    """What the marching kernel's radius-5 form rests on (k_lap.hip lap_march_item): OpenCV's size-11 derivative / smoothing kernels
     are the size-9 kernels convolved with [1 2 1], so Laplacian_11 = ([1 2 1] x [1 2 1]) * (kd9 x ks9 + ks9 x kd9) on the REFLECT_101
     extension, saturated once at the end - also for images smaller than the kernel (multiple reflections)."""
     kd9, ks9, kd11, ks11 = (O.sobel_kernel(9, 2), O.sobel_kernel(9, 0), O.sobel_kernel(11, 2), O.sobel_kernel(11, 0))
