@@ -186,7 +186,8 @@ def fft_form(request, ops):
 def test_fast_phase_correlation_equals_double_precision_path(ops, O, shape, fft_form):
     """k_fft.hip (float32, radices 2/3/4/5/7/61; rows of length 61 * M as 61-point transforms + M-point transforms per wavefront)
     against the double-precision path (k_fft64.hip, hand-written as well) and the oracle: same integer shifts on shifted copies (clear peak -> fast path is
-    trusted), and the double path takes over when the peak is split evenly."""
+    trusted).  That the double path takes over when the peak is split is NOT tested here (every pair below has one clear peak):
+    tests/test_gpu_phase_accuracy.py::test_one_percent_rule_hands_weak_peaks_to_complex128 holds the 1 % rule on both sides."""
     from karios_amd._lib import default_context
     H, W = shape
     ctx = default_context()
