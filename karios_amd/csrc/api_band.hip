@@ -67,7 +67,7 @@ int km_band_eigen_dev(km_ctx *c, const uint8_t *d_lap_ref, const uint8_t *d_mask
     if (!d_mask || !local_max_key || !(quality > 0) || block < 1) return km_fail(c, KM_E_ARG, "band_eigen: bad arguments");
     km_scalars *sc = scalars(c);
     if (!sc) return KM_E_NOMEM;
-    KM_HIP(c, hipMemsetAsync(&sc->max_eig_key, 0, sizeof(km_scalars) - offsetof(km_scalars, max_eig_key), c->stream));
+    if ((rc = clear_corner_scalars(c, sc))) return rc;
     c->band_capk = (size_t)H * W / 4 + 4096 * KM_NSHARD;       // generous: the running threshold of a band is only its own maximum's
     unsigned long long *keys = (unsigned long long *)km_ws(c, WS_KEYS0, c->band_capk * sizeof(unsigned long long));
     if (!keys) return KM_E_NOMEM;

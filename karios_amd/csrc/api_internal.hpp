@@ -1,13 +1,50 @@
-// Helpers shared by the entry-point translation units (api*.hip).
+// Helpers shared by the entry-point translation units (api*.hip): the start of a call and its argument checks, the streams and events
+// of a context, caller memory <-> device, the stages of a tile (api_tile.hip), the frame block - its ONE layout (km_frame_layout), its
+// slots and its way out (api_frame.hip) - and the arena of the kernel-size search (api_auto.hip).
 #pragma once
 #include "common.hpp"
+
+#include <cstddef>
+
+static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // stage timers are cleared per pipeline: the KLT entry points own [ST_MINMAX, ST_LK], ZNCC owns ST_ZNCC
 enum { RESET_NONE = 0, RESET_KLT = 1, RESET_ZNCC = 2 };
 int begin_call(km_ctx *c, int reset = RESET_NONE);   // start of every entry point: device, pending uploads, stale jobs, stage timers
 int check_image(km_ctx *c, const void *p, int H, int W, ptrdiff_t stride, const char *what);
 int check_params(km_ctx *c, const km_klt_params *p);
-int frame_block_free(km_ctx *c);                     // WS_FRAME may be rewritten once the previous submitted frame's block has left
+// ---- the argument checks the tile entry points share (api_tile.hip), in the order in which their errors win
+int tile_call_begin(km_ctx *c, const char *who, const km_klt_params *prm, const void *ref, const void *mon, int H, int W, ptrdiff_t sref,
+                    ptrdiff_t smon);                 // begin_call(RESET_KLT), the parameters, the two images
+int check_dtype(km_ctx *c, const char *who, int dtype);
+int check_frame_width(km_ctx *c, const char *who, const char *what, int W);   // the device-side frame ordering holds at most 65535 columns
+int check_capacity(km_ctx *c, const km_klt_params *prm, int cap);
+// a user mask as the kernels index it - dense rows: the mask itself, or the box of a larger resident mask packed into WS_MASK (1 B/px copy)
+int dense_mask(km_ctx *c, const uint8_t *d_mask, ptrdiff_t smask, int H, int W, const uint8_t **dense);
+static inline int corner_limit(const km_klt_params *prm, int cap) { return prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap; }
+// the corner part of a scalar block back to zero; the min / max and the valid-pixel count in front of it stay
+static inline int clear_corner_scalars(km_ctx *c, km_scalars *sc)
+{
+    KM_HIP(c, hipMemsetAsync(&sc->max_eig_key, 0, sizeof(km_scalars) - offsetof(km_scalars, max_eig_key), c->stream));
+    return KM_OK;
+}
+// the two-level pyramid of a unit: level 0 the Laplacian itself, level 1 in `l1`
+static inline void pyr_two_level(km_pyr &P, const uint8_t *l0, const uint8_t *l1, int H, int W)
+{
+    P.img[0] = l0; P.H[0] = H; P.W[0] = W;
+    P.img[1] = l1; P.H[1] = (H + 1) / 2; P.W[1] = (W + 1) / 2;
+    P.levels = 1;
+}
+// c->stats from a km_scalars read-back: the maximum eigenvalue and the min / max always, of the rest what the caller's path owns
+enum { KS_VALID = 1, KS_CANDIDATES = 2, KS_TIES = 4 };
+static inline void stats_from_scalars(km_ctx *c, const km_scalars &h, int what)
+{
+    c->stats.max_eig = h.max_eig;
+    c->stats.min_ref = h.mm[0]; c->stats.max_ref = h.mm[1]; c->stats.min_mon = h.mm[2]; c->stats.max_mon = h.mm[3];
+    if (what & KS_VALID) c->stats.valid_pixels = (int64_t)h.valid;
+    if (what & KS_CANDIDATES) c->stats.n_candidates = (int64_t)h.cut[3];
+    if (what & KS_TIES) c->stats.tie_rows = (int32_t)h.tie_rows;
+}
 
 // ---- modes of one tile call.  The entry point creates it; it travels klt_tile_dev_impl -> klt_track_dev -> read_stats / fetch_tracks (api_tile.hip)
 struct km_call_modes {
@@ -64,7 +101,61 @@ int gftt_dev(km_ctx *c, const uint8_t *d_img, const uint8_t *d_mask, int H, int 
              float *d_xy, int cap, km_scalars *sc);
 int read_stats(km_ctx *c, km_scalars *sc, km_call_modes *m = nullptr);   // m: a call that may have taken the speculative corner path
 int mark_lk_start(km_ctx *c);                        // records ev_lk_start on c->stream: the next unit's early min / max may start beside this LK launch
-// ---- a frame block's way out (api_tile.hip): the slot's page-locked buffer and completion event; n blocks to the sink and to the slot
+
+// ---- the frame block (the counterpart of karios_amd.frames.block_words / block_to_frame):
+//   header (4 x int32: rows kept, corners, flags, candidates) | x0 | y0 | dx | dy | score | index bits (float32, cap each)
+//   | zncc [| mutual_info_score | mi_score] (float64, cap each)
+struct km_frame_layout {
+    int cap = 0;
+    size_t fb = 0;       // bytes up to the end of the float32 columns
+    size_t ob = 0;       // bytes of a whole block
+    size_t ob_al = 0;    // pitch of the blocks of a batch (256-byte aligned)
+    km_frame_layout() = default;
+    km_frame_layout(int cap_, bool with_zncc, bool with_mi)
+        : cap(cap_), fb(16 + (size_t)cap_ * 6 * sizeof(float)),
+          ob(fb + (with_zncc ? (size_t)cap_ * sizeof(double) : 0) + (with_mi ? (size_t)cap_ * 2 * sizeof(double) : 0)), ob_al(up256(ob)) {}
+    enum { X0 = 0, Y0, DX, DY, SCORE, INDEX };                  // float32 columns
+    enum { ZNCC = 0, MUTUAL_INFO, MI_SCORE };                   // float64 score columns
+    const int *header(const char *block) const { return (const int *)block; }
+    const float *col(const char *block, int i) const { return (const float *)(block + 16) + (size_t)i * cap; }
+    double *score_col(char *block, int k) const { return (double *)(block + fb) + (size_t)k * cap; }
+    // the rows a score kernel reads and the column it writes: ZNCC (out), or the two MI columns (out, out2)
+    void score_unit(km_score_unit &s, char *block, bool mi) const
+    {
+        s.x0 = col(block, X0); s.y0 = col(block, Y0); s.dx = col(block, DX); s.dy = col(block, DY); s.score = col(block, SCORE);
+        s.d_n = header(block);
+        s.out = score_col(block, mi ? MUTUAL_INFO : ZNCC); s.out2 = mi ? score_col(block, MI_SCORE) : nullptr;
+    }
+};
+
+// ---- api_frame.hip: the frame slots, the sink and a block's way out
+int frame_block_free(km_ctx *c);                     // WS_FRAME may be rewritten once the previous submitted frame's block has left
 int frame_sink_check(km_ctx *c, size_t pitch, int n, size_t ob);
+// the next frame slot, free to be written (a block nobody waited for is waited for here), and c->ev_cur on its stage events.  who: the
+// entry point that refuses a slot whose submission is still deferred (nullptr: none can be)
+int frame_slot_claim(km_ctx *c, const char *who, int *k, km_frame_slot **slot);
 int frame_slot_reserve(km_ctx *c, km_frame_slot *slot, size_t bytes);
-int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, size_t ob, size_t ob_al, int n, void *sink, size_t sink_pitch, hipStream_t s);
+int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, const km_frame_layout &L, int n, void *sink, size_t sink_pitch, hipStream_t s);
+void frame_slot_commit(km_ctx *c, int k, int *ticket);   // the claimed slot is pending: its ticket, and the ring moves on
+
+// ---- api_auto.hip: the arena of the kernel-size search, offsets from a 256-byte aligned base
+struct km_auto_arena {
+    size_t na = 0, pts = 0, pyr_bytes = 0;          // pitches: a Laplacian, a point list, one image's pyramid levels
+    size_t lap_ref = 0, lap_mon = 0;                // nk Laplacians each
+    size_t pyr = 0;                                 // 2 nk pyramids: reference kernel k at 2k, its monitored twin at 2k + 1
+    size_t p0 = 0;                                  // nk corner lists
+    size_t trk = 0;                                 // nk * nk track pairs: p1 of a combination at 2 * combo, p0r at 2 * combo + 1
+    size_t counts = 0, counts_bytes = 0;            // int32: [nk] corners per reference kernel, [nk * nk] kept tracks
+    size_t total = 0;
+};
+static inline km_auto_arena km_auto_arena_of(int nk, int H, int W, size_t pyr_bytes, int cap)
+{
+    km_auto_arena a;
+    const size_t k = (size_t)nk;
+    a.na = up256((size_t)H * W); a.pts = up256((size_t)cap * 2 * sizeof(float)); a.pyr_bytes = pyr_bytes;
+    a.lap_ref = 0; a.lap_mon = a.lap_ref + k * a.na; a.pyr = a.lap_mon + k * a.na;
+    a.p0 = a.pyr + 2 * k * pyr_bytes; a.trk = a.p0 + k * a.pts;
+    a.counts = a.trk + 2 * k * k * a.pts; a.counts_bytes = 4096;
+    a.total = a.counts + a.counts_bytes;
+    return a;
+}

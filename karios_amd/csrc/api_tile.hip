@@ -1,9 +1,8 @@
 // Tile entry points of libkarios_hip.so: the device-resident KLT tile pipeline (KLT._match_tile, klt.py:236-349: stretch -> Laplacians -> mask
 // -> goodFeaturesToTrack -> LK forward / backward), the frame forms (FB test, score, (x0, y0) order and the score columns in the same
-// device call), the asynchronous submission and the batched kernel-size search.  Batched units: api_units.hip.
+// device call) and the asynchronous submission.  Batched units: api_units.hip; the kernel-size search: api_auto.hip; the frame block's
+// slots and its way out: api_frame.hip.
 #include "api_internal.hpp"
-#include <time.h>
-#include <sys/prctl.h>
 
 #include <cstring>
 
@@ -104,9 +103,7 @@ int gftt_dev(km_ctx *c, const uint8_t *d_img, const uint8_t *d_mask, int H, int 
             km_stage_timer t(c, ST_SORT);
             if ((rc = ks_topk_prefilter(c, keys, capk, k_target, sc, quality, &kept, &nkept, &ntotal, &hs, attempt > 0))) return rc;
         }
-        c->stats.valid_pixels = (int64_t)hs.valid;
-        c->stats.max_eig = hs.max_eig;
-        c->stats.min_ref = hs.mm[0]; c->stats.max_ref = hs.mm[1]; c->stats.min_mon = hs.mm[2]; c->stats.max_mon = hs.mm[3];
+        stats_from_scalars(c, hs, KS_VALID);
         if (fused && hs.pad0 != 0u) {   // candidates were dropped: repeat with the eig-map + candidate kernels
             fused_overflow = true;
             c->stats.path_flags |= KM_PATH_STAGE_FALLBACK;
@@ -149,14 +146,9 @@ int read_stats(km_ctx *c, km_scalars *sc, km_call_modes *m)
     KM_FLUSH(c);
     c->stats.n_init = h.n_corners;
     c->stats.n_select_batches = h.n_batches;
-    c->stats.max_eig = h.max_eig;
-    c->stats.min_ref = h.mm[0]; c->stats.max_ref = h.mm[1]; c->stats.min_mon = h.mm[2]; c->stats.max_mon = h.mm[3];
-    if (m && m->spec_used) {   // the speculative corner path read nothing back on the way: its diagnostics arrive here
-        c->stats.valid_pixels = (int64_t)h.valid;
-        c->stats.n_candidates = (int64_t)h.cut[3];
-        m->spec_flags = h.flags;
-    }
-    c->stats.tie_rows = (int32_t)h.tie_rows;
+    const bool spec = m && m->spec_used;   // the speculative corner path read nothing back on the way: its diagnostics arrive here
+    stats_from_scalars(c, h, KS_TIES | (spec ? KS_VALID | KS_CANDIDATES : 0));
+    if (spec) m->spec_flags = h.flags;
     if (h.n_cand == 0xffffffffu) return km_fail(c, KM_E_INTERNAL, "corner grid cell overflow");
     return KM_OK;
 }
@@ -232,7 +224,7 @@ static int klt_track_dev(km_ctx *c, km_call_modes &m, km_valid_job vjob, const u
             if (forked) KM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));   // (whatever happens next reuses the pyramid buffers)
             if (rc == KM_E_UNSUPPORTED) {   // (grid too large for the fixed-slot cells: nothing irreversible was enqueued)
                 spec = false;
-                KM_HIP(c, hipMemsetAsync(&sc->max_eig_key, 0, sizeof(km_scalars) - offsetof(km_scalars, max_eig_key), c->stream));
+                if ((rc = clear_corner_scalars(c, sc))) return rc;
             } else if (rc) return rc;
         }
         if (spec) {
@@ -269,7 +261,7 @@ static int klt_track_dev(km_ctx *c, km_call_modes &m, km_valid_job vjob, const u
         const int rc2 = rc ? (c->deferred.clear(), rc) : km_run_deferred(c);
         if (rc2) return rc2;
     }
-    const int n_max = d_p0_in ? n_p0 : (prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap);
+    const int n_max = d_p0_in ? n_p0 : corner_limit(prm, cap);
     {
         km_stage_timer t(c, ST_LK);
         if (spec && !c->lk_start_valid) {
@@ -294,6 +286,40 @@ int check_params(km_ctx *c, const km_klt_params *p)
     return KM_OK;
 }
 
+int tile_call_begin(km_ctx *c, const char *who, const km_klt_params *prm, const void *ref, const void *mon, int H, int W, ptrdiff_t sref, ptrdiff_t smon)
+{
+    int rc;
+    if ((rc = begin_call(c, RESET_KLT)) || (rc = check_params(c, prm)) || (rc = check_image(c, ref, H, W, sref, who)) || (rc = check_image(c, mon, H, W, smon, who)))
+        return rc;
+    return KM_OK;
+}
+
+int check_dtype(km_ctx *c, const char *who, int dtype) { return km_dtype_size(dtype) ? KM_OK : km_fail(c, KM_E_ARG, "%s: bad dtype %d", who, dtype); }
+
+// the frame's (x0, y0) ordering buckets the rows by tile column (k_frame.hip: x0 - x_off < 65536); wider tiles are refused, not mis-ordered
+int check_frame_width(km_ctx *c, const char *who, const char *what, int W)
+{
+    return W <= 65535 ? KM_OK : km_fail(c, KM_E_ARG, "%s: %s of %d columns (the device-side frame ordering holds at most 65535)", who, what, W);
+}
+
+int check_capacity(km_ctx *c, const km_klt_params *prm, int cap)
+{
+    return prm->max_corners > 0 && cap < prm->max_corners ? km_fail(c, KM_E_ARG, "capacity %d < maxCorners %d", cap, prm->max_corners) : KM_OK;
+}
+
+int dense_mask(km_ctx *c, const uint8_t *d_mask, ptrdiff_t smask, int H, int W, const uint8_t **dense)
+{
+    *dense = d_mask;
+    if (smask == W) return KM_OK;
+    // box of a larger resident mask: the kernels index masks densely, so pack the box first (1 B/px copy)
+    if (smask < W) return km_fail(c, KM_E_ARG, "mask stride %td < width %d", smask, W);
+    uint8_t *packed = (uint8_t *)km_ws(c, WS_MASK, (size_t)H * W);
+    if (!packed) return KM_E_NOMEM;
+    KM_HIP(c, hipMemcpy2DAsync(packed, (size_t)W, d_mask, (size_t)smask, (size_t)W, (size_t)H, hipMemcpyDeviceToDevice, c->stream));
+    *dense = packed;
+    return KM_OK;
+}
+
 static int klt_tile_dev_impl(km_ctx *c, km_call_modes &m, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
                              const uint8_t *d_mask, ptrdiff_t smask, const double *nodata_ref, const double *nodata_mon, const km_klt_params *prm,
                              float *d_p0, float *d_p1, float *d_p0r, int cap, km_scalars *sc)
@@ -304,14 +330,7 @@ static int klt_tile_dev_impl(km_ctx *c, km_call_modes &m, const void *d_ref, con
     if (!lap_ref || !lap_mon) return KM_E_NOMEM;
     uint8_t *mask_auto = nullptr;
     if (!d_mask) { mask_auto = (uint8_t *)km_ws(c, WS_MASK, n); if (!mask_auto) return KM_E_NOMEM; }
-    else if (smask != W) {
-        // box of a larger resident mask: the kernels index masks densely, so pack the box first (1 B/px copy)
-        if (smask < W) return km_fail(c, KM_E_ARG, "mask stride %td < width %d", smask, W);
-        uint8_t *dense = (uint8_t *)km_ws(c, WS_MASK, n);
-        if (!dense) return KM_E_NOMEM;
-        KM_HIP(c, hipMemcpy2DAsync(dense, (size_t)W, d_mask, (size_t)smask, (size_t)W, (size_t)H, hipMemcpyDeviceToDevice, c->stream));
-        d_mask = dense;
-    }
+    else if ((rc = dense_mask(c, d_mask, smask, H, W, &d_mask))) return rc;
     const double *mm = sc->mm;
     km_valid_job vjob;
     if (dtype != KM_U8 && m.mm_early_allowed && c->opt_mm_early && c->lk_start_prev && c->aux_stream) {
@@ -370,61 +389,15 @@ static int fetch_tracks(km_ctx *c, km_call_modes &m, km_scalars *sc, const float
     return KM_OK;
 }
 
-// The previous submitted frame's block may still be on its way to the host (on the d2h stream): WS_FRAME may be rewritten once it
-// has left - a device-side wait that never stalls in practice (the copy takes 13 us, the next frame is written ~1 ms later).
-int frame_block_free(km_ctx *c)
-{
-    const int rc = c->frame_copy ? km_wait(c, c->stream, c->frame_copy) : KM_OK;
-    if (rc == KM_OK) c->frame_copy = nullptr;
-    return rc;
-}
-
-int frame_sink_check(km_ctx *c, size_t pitch, int n, size_t ob)
-{
-    if (!pitch) pitch = ob;
-    if (!c->frame_sink || (pitch >= ob && c->frame_sink_cap >= pitch * (size_t)(n - 1) + ob)) return KM_OK;
-    return km_fail(c, KM_E_ARG, "frame sink of %zu bytes (pitch %zu) is smaller than %d frame block(s) of %zu bytes", c->frame_sink_cap, pitch, n, ob);
-}
-
-// the slot of a submitted frame: `bytes` of page-locked memory (one eighth of head-room when it grows) and its completion event
-int frame_slot_reserve(km_ctx *c, km_frame_slot *slot, size_t bytes)
-{
-    KM_HIP(c, slot->host.reserve(bytes, bytes / 8));
-    return km_event(c, &slot->done);
-}
-
-// n frame blocks of ob bytes (device pitch ob_al) leave d_out on stream s: into the frame sink, if there is one (km_set_frame_sink: the
-// device-side copy; km_stream_wait_frame lets a stream of the caller - the one an RCCL collective is issued on - wait for exactly this
-// copy), and into the slot's page-locked buffer.  One block travels as a plain copy, several as one strided copy each way
-int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, size_t ob, size_t ob_al, int n, void *sink, size_t sink_pitch, hipStream_t s)
-{
-    int rc;
-    slot->sunk_valid = false;
-    if (sink) {
-        if (n == 1) KM_HIP(c, hipMemcpyAsync(sink, d_out, ob, hipMemcpyDeviceToDevice, s));
-        else KM_HIP(c, hipMemcpy2DAsync(sink, sink_pitch ? sink_pitch : ob, d_out, ob_al, ob, (size_t)n, hipMemcpyDeviceToDevice, s));
-        if ((rc = km_event(c, &slot->sunk)) || (rc = km_record(c, slot->sunk, s))) return rc;
-        slot->sunk_valid = true;
-    }
-    if (n == 1) KM_HIP(c, hipMemcpyAsync(slot->host, d_out, ob, hipMemcpyDeviceToHost, s));
-    else KM_HIP(c, hipMemcpy2DAsync(slot->host, ob, d_out, ob_al, ob, (size_t)n, hipMemcpyDeviceToHost, s));
-    if ((rc = km_record(c, slot->done, s))) return rc;
-    c->frame_copy = slot->done;
-    slot->bytes = ob * n;
-    return KM_OK;
-}
-
 extern "C" {
 
 int km_klt_track(km_ctx *c, const uint8_t *ref_lap, const uint8_t *mon_lap, const uint8_t *mask, int H, int W, const km_klt_params *prm,
                  const float *p0_in, int n_p0, float *p0, float *p1, float *p0r, int cap, int *out_n)
 {
     int rc;
-    if ((rc = begin_call(c, RESET_KLT)) || (rc = check_params(c, prm)) || (rc = check_image(c, ref_lap, H, W, W, "klt_track")) ||
-        (rc = check_image(c, mon_lap, H, W, W, "klt_track")))
-        return rc;
+    if ((rc = tile_call_begin(c, "klt_track", prm, ref_lap, mon_lap, H, W, W, W))) return rc;
     if (!p0 || !p1 || !p0r || !out_n || cap <= 0) return km_fail(c, KM_E_ARG, "klt_track: null output");
-    if (!p0_in && prm->max_corners > 0 && cap < prm->max_corners) return km_fail(c, KM_E_ARG, "capacity %d < maxCorners %d", cap, prm->max_corners);
+    if (!p0_in && (rc = check_capacity(c, prm, cap))) return rc;
     memset(&c->stats, 0, sizeof c->stats);
     void *d_ref, *d_mon, *d_mask = nullptr;
     if ((rc = upload_image(c, WS_U8_A, ref_lap, 1, H, W, W, &d_ref)) || (rc = upload_image(c, WS_U8_B, mon_lap, 1, H, W, W, &d_mon))) return rc;
@@ -452,13 +425,10 @@ int km_klt_tile(km_ctx *c, const void *ref, const void *mon, int dtype, int H, i
                 int *out_n)
 {
     int rc;
-    if ((rc = begin_call(c, RESET_KLT)) || (rc = check_params(c, prm)) || (rc = check_image(c, ref, H, W, sref, "klt_tile")) ||
-        (rc = check_image(c, mon, H, W, smon, "klt_tile")))
-        return rc;
+    if ((rc = tile_call_begin(c, "klt_tile", prm, ref, mon, H, W, sref, smon)) || (rc = check_dtype(c, "klt_tile", dtype))) return rc;
     const size_t es = km_dtype_size(dtype);
-    if (!es) return km_fail(c, KM_E_ARG, "klt_tile: bad dtype %d", dtype);
     if (!p0 || !p1 || !p0r || !out_n || cap <= 0) return km_fail(c, KM_E_ARG, "klt_tile: null output");
-    if (prm->max_corners > 0 && cap < prm->max_corners) return km_fail(c, KM_E_ARG, "capacity %d < maxCorners %d", cap, prm->max_corners);
+    if ((rc = check_capacity(c, prm, cap))) return rc;
     memset(&c->stats, 0, sizeof c->stats);
     void *d_ref, *d_mon, *d_mask = nullptr;
     if ((rc = upload_image(c, WS_RAW_A, ref, es, H, W, sref, &d_ref)) || (rc = upload_image(c, WS_RAW_B, mon, es, H, W, smon, &d_mon))) return rc;
@@ -526,12 +496,9 @@ int km_klt_tile_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, 
                     float *d_p1, float *d_p0r, int cap, int *d_n)
 {
     int rc;
-    if ((rc = begin_call(c, RESET_KLT)) || (rc = check_params(c, prm)) || (rc = check_image(c, d_ref, H, W, sref, "klt_tile_dev")) ||
-        (rc = check_image(c, d_mon, H, W, smon, "klt_tile_dev")))
-        return rc;
-    if (!km_dtype_size(dtype)) return km_fail(c, KM_E_ARG, "klt_tile_dev: bad dtype %d", dtype);
+    if ((rc = tile_call_begin(c, "klt_tile_dev", prm, d_ref, d_mon, H, W, sref, smon)) || (rc = check_dtype(c, "klt_tile_dev", dtype))) return rc;
     if (!d_p0 || !d_p1 || !d_p0r || !d_n || cap <= 0) return km_fail(c, KM_E_ARG, "klt_tile_dev: null output");
-    if (prm->max_corners > 0 && cap < prm->max_corners) return km_fail(c, KM_E_ARG, "capacity %d < maxCorners %d", cap, prm->max_corners);
+    if ((rc = check_capacity(c, prm, cap))) return rc;
     memset(&c->stats, 0, sizeof c->stats);
     km_scalars *sc = scalars(c);
     if (!sc) return KM_E_NOMEM;
@@ -539,6 +506,31 @@ int km_klt_tile_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, 
     km_call_modes m;           // (nobody reads this call's flags: the exact corner path)
     if ((rc = klt_tile_dev_impl(c, m, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc))) return rc;
     KM_HIP(c, hipMemcpyAsync(d_n, &sc->n_corners, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    return KM_OK;
+}
+
+// the score columns of a tile's frame block: ZNCC of the confident rows [and the two MI scores]
+static int tile_frame_scores(km_ctx *c, const km_frame_layout &L, char *d_out, const void *d_ref_full, const void *d_mon_full, int dtype, int Hf, int Wf,
+                             ptrdiff_t sref_f, ptrdiff_t smon_f, int n_max, double zncc_threshold, bool with_mi)
+{
+    int rc;
+    km_score_unit s;
+    {
+        km_stage_timer t(c, ST_ZNCC);
+        L.score_unit(s, d_out, false);
+        if ((rc = kz_zncc_filtered(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, s.x0, s.y0, s.dx, s.dy, n_max, s.d_n, s.score,
+                                   (float)zncc_threshold, s.out)))
+            return rc;
+    }
+    if (with_mi) {
+        // the other two scores of _handle_klt_results (core.py:894-907) for the same rows, behind ZNCC in the same call: the chips of
+        // a key point (57 x 57, around the 43 x 43 ZNCC window) are still in the XCD's L2
+        km_stage_timer t(c, ST_MI);
+        L.score_unit(s, d_out, true);
+        if ((rc = kmi_batch(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, s.x0, s.y0, s.dx, s.dy, n_max, s.d_n, s.score,
+                            (float)zncc_threshold, s.out, s.out2)))
+            return rc;
+    }
     return KM_OK;
 }
 
@@ -550,24 +542,20 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
     // slot != nullptr: km_klt_tile_frame_submit - the block goes to the slot's pinned buffer and the call returns without
     // waiting for the tail of the pipeline (LK, FB test, ZNCC, copy), which then overlaps the caller's next submission
     int rc;
-    if ((rc = begin_call(c, RESET_KLT)) || (rc = check_params(c, prm)) || (rc = check_image(c, d_ref, H, W, sref, "klt_tile_frame_dev")) ||
-        (rc = check_image(c, d_mon, H, W, smon, "klt_tile_frame_dev")))
-        return rc;
+    if ((rc = tile_call_begin(c, "klt_tile_frame_dev", prm, d_ref, d_mon, H, W, sref, smon))) return rc;
     if (with_zncc && ((rc = check_image(c, d_ref_full, Hf, Wf, sref_f, "klt_tile_frame_zncc_dev")) ||
                       (rc = check_image(c, d_mon_full, Hf, Wf, smon_f, "klt_tile_frame_zncc_dev"))))
         return rc;
-    if (!km_dtype_size(dtype)) return km_fail(c, KM_E_ARG, "klt_tile_frame_dev: bad dtype %d", dtype);
-    // the frame's (x0, y0) ordering buckets the rows by tile column (k_frame.hip: x0 - x_off < 65536); wider tiles are refused, not mis-ordered
-    if (W > 65535) return km_fail(c, KM_E_ARG, "klt_tile_frame_dev: tile of %d columns (the device-side frame ordering holds at most 65535)", W);
+    if ((rc = check_dtype(c, "klt_tile_frame_dev", dtype)) || (rc = check_frame_width(c, "klt_tile_frame_dev", "tile", W))) return rc;
     if ((!host_out && !slot) || cap <= 0) return km_fail(c, KM_E_ARG, "klt_tile_frame_dev: null output");
-    if (prm->max_corners > 0 && cap < prm->max_corners) return km_fail(c, KM_E_ARG, "capacity %d < maxCorners %d", cap, prm->max_corners);
+    if ((rc = check_capacity(c, prm, cap))) return rc;
     memset(&c->stats, 0, sizeof c->stats);
     c->evs_used[c->ev_cur][ST_ZNCC] = false; c->evs_used[c->ev_cur][ST_MI] = false;
     km_scalars *sc = scalars(c);
     const size_t pb = (size_t)cap * 2 * sizeof(float);
-    // block: header | x0 | y0 | dx | dy | score | index bits (float32) | zncc [| mutual_info_score | mi_score] (float64)
     const bool with_mi = with_zncc && c->opt_frame_mi;
-    const size_t fb = 16 + (size_t)cap * 6 * sizeof(float), ob = fb + (with_zncc ? (size_t)cap * sizeof(double) : 0) + (with_mi ? (size_t)cap * 2 * sizeof(double) : 0);
+    const km_frame_layout L(cap, with_zncc, with_mi);
+    const size_t ob = L.ob;
     float *d_p0 = (float *)km_ws(c, WS_PTS0, pb), *d_p1 = (float *)km_ws(c, WS_PTS1, pb), *d_p0r = (float *)km_ws(c, WS_PTS2, pb);
     char *d_out = (char *)km_ws(c, WS_FRAME, ob);
     if (!sc || !d_p0 || !d_p1 || !d_p0r || !d_out) return KM_E_NOMEM;
@@ -580,50 +568,29 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
         m.spec_allowed = attempt == 0;
         m.mm_early_allowed = slot != nullptr;     // (the synchronous forms report min / max in their statistics: scalar block)
         if ((rc = klt_tile_dev_impl(c, m, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc))) return rc;
-        const int n_max = prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap;
+        const int n_max = corner_limit(prm, cap);
         if ((rc = frame_block_free(c))) return rc;
         {
             km_stage_timer t(c, ST_FRAME);
             if ((rc = kf_frame(c, d_p0, d_p1, d_p0r, &sc->n_corners, n_max, cap, 0.1f, x_off, y_off, d_out, m.spec_used ? sc : nullptr, W))) return rc;
         }
-        if (with_zncc) {
-            km_stage_timer t(c, ST_ZNCC);
-            const float *f = (const float *)(d_out + 16);
-            if ((rc = kz_zncc_filtered(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, f, f + cap, f + 2 * (size_t)cap,
-                                       f + 3 * (size_t)cap, n_max, (const int *)d_out, f + 4 * (size_t)cap, (float)zncc_threshold,
-                                       (double *)(d_out + fb))))
-                return rc;
-        }
-        if (with_mi) {
-            // the other two scores of _handle_klt_results (core.py:894-907) for the same rows, behind ZNCC in the same call: the chips of
-            // a key point (57 x 57, around the 43 x 43 ZNCC window) are still in the XCD's L2
-            km_stage_timer t(c, ST_MI);
-            const float *f = (const float *)(d_out + 16);
-            double *st = (double *)(d_out + fb) + cap;
-            if ((rc = kmi_batch(c, d_ref_full, d_mon_full, dtype, Hf, Wf, Hf, Wf, sref_f, smon_f, f, f + cap, f + 2 * (size_t)cap, f + 3 * (size_t)cap,
-                                n_max, (const int *)d_out, f + 4 * (size_t)cap, (float)zncc_threshold, st, st + cap)))
-                return rc;
-        }
+        if (with_zncc && (rc = tile_frame_scores(c, L, d_out, d_ref_full, d_mon_full, dtype, Hf, Wf, sref_f, smon_f, n_max, zncc_threshold, with_mi))) return rc;
         if ((rc = frame_sink_check(c, 0, 1, ob))) return rc;      // (a single block ignores the sink's pitch)
         if (slot) {
             // the block leaves on a stream of its own: 13 us of DMA that the next submission's first kernels need not wait for
             // (the next frame is written into WS_FRAME ~1 ms later, behind a wait for this copy: see frame_block_free); the
             // device-side copy into the frame sink leaves there too: on the compute stream it cost the next unit 11 us
             if ((rc = frame_slot_reserve(c, slot, ob)) || (rc = km_block_stream(c))) return rc;
-            return frame_blocks_out(c, slot, d_out, ob, ob, 1, c->frame_sink, 0, c->d2h_stream);
+            return frame_blocks_out(c, slot, d_out, L, 1, c->frame_sink, 0, c->d2h_stream);
         }
         if (c->frame_sink) KM_HIP(c, hipMemcpyAsync(c->frame_sink, d_out, ob, hipMemcpyDeviceToDevice, c->stream));
         km_scalars *land = m.spec_used ? (km_scalars *)km_pinned_rb(c, sizeof(km_scalars)) : nullptr;
         if (land) KM_HIP(c, hipMemcpyAsync(land, sc, sizeof *land, hipMemcpyDeviceToHost, c->stream));   // diagnostics of the sync-free corner path
         KM_D2H(c, host_out, d_out, ob);
         KM_FLUSH(c);
-        c->stats.n_init = ((const int *)host_out)[1];
+        c->stats.n_init = L.header((const char *)host_out)[1];
         if (land) {
-            c->stats.valid_pixels = (int64_t)land->valid;
-            c->stats.n_candidates = (int64_t)land->cut[3];
-            c->stats.tie_rows = (int32_t)land->tie_rows;
-            c->stats.max_eig = land->max_eig;
-            c->stats.min_ref = land->mm[0]; c->stats.max_ref = land->mm[1]; c->stats.min_mon = land->mm[2]; c->stats.max_mon = land->mm[3];
+            stats_from_scalars(c, *land, KS_VALID | KS_CANDIDATES | KS_TIES);
             if (land->flags) {                                   // did not fit the fixed capacities: the exact path decides
                 memset(&c->stats, 0, sizeof c->stats);
                 c->stats.path_flags |= KM_PATH_SPEC_RETRY;
@@ -632,230 +599,6 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
         }
         return KM_OK;
     }
-}
-
-// KLT._match_tile_auto_ksize (klt.py:465-545) on resident data: every Laplacian, pyramid and corner list is built ONCE
-// and stays on the device; the nk*nk tracker runs reuse them.  Best pair = highest inlier ratio, first wins ties, in
-// itertools.product order (mon outer, ref inner).
-int km_klt_auto_ksize_frame_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
-                                const uint8_t *d_mask, ptrdiff_t smask, const double *nodata_ref, const double *nodata_mon, const km_klt_params *prm,
-                                const int *ksizes, int nk, float x_off, float y_off, void *host_out, int cap, double *out_ratios, int *out_best)
-{
-    int rc;
-    if ((rc = begin_call(c, RESET_KLT)) || (rc = check_params(c, prm)) || (rc = check_image(c, d_ref, H, W, sref, "klt_auto_ksize")) ||
-        (rc = check_image(c, d_mon, H, W, smon, "klt_auto_ksize")))
-        return rc;
-    if (!km_dtype_size(dtype)) return km_fail(c, KM_E_ARG, "klt_auto_ksize: bad dtype %d", dtype);
-    if (W > 65535) return km_fail(c, KM_E_ARG, "klt_auto_ksize: tile of %d columns (the device-side frame ordering holds at most 65535)", W);
-    if (!ksizes || nk < 1 || nk > 8 || !host_out || !out_ratios || !out_best || cap <= 0) return km_fail(c, KM_E_ARG, "klt_auto_ksize: bad arguments");
-    if (prm->max_corners > 0 && cap < prm->max_corners) return km_fail(c, KM_E_ARG, "capacity %d < maxCorners %d", cap, prm->max_corners);
-    memset(&c->stats, 0, sizeof c->stats);
-    const size_t n = (size_t)H * W, na = (n + 255) & ~(size_t)255;
-    // scalar blocks: [0] the call's own (min / max, valid pixels, the exact corner path), [1 + k] the corner detection of reference kernel k
-    const size_t sc_stride = (sizeof(km_scalars) + 255) & ~(size_t)255;
-    char *sc_base = (char *)km_ws(c, WS_SCALARS, sc_stride * (size_t)(nk + 1));
-    km_scalars *sc = (km_scalars *)sc_base;
-    if (!sc) return KM_E_NOMEM;
-    KM_HIP(c, hipMemsetAsync(sc_base, 0, sc_stride * (size_t)(nk + 1), c->stream));
-    // ---- mask: the user's (packed to the box) - or the automatic one, which the FIRST Laplacian pass below derives from the raw rasters
-    const uint8_t *mask = d_mask;
-    uint8_t *mask_auto = nullptr;
-    if (!d_mask) {
-        mask_auto = (uint8_t *)km_ws(c, WS_MASK, n);
-        if (!mask_auto) return KM_E_NOMEM;
-        mask = mask_auto;
-    } else {
-        if (smask < W) return km_fail(c, KM_E_ARG, "mask stride %td < width %d", smask, W);
-        if (smask != W) {
-            uint8_t *dense = (uint8_t *)km_ws(c, WS_MASK, n);
-            if (!dense) return KM_E_NOMEM;
-            KM_HIP(c, hipMemcpy2DAsync(dense, (size_t)W, d_mask, (size_t)smask, (size_t)W, (size_t)H, hipMemcpyDeviceToDevice, c->stream));
-            mask = dense;
-        }
-        if ((rc = kd_count_nonzero(c, mask, n, &sc->valid))) return rc;
-    }
-    if (dtype != KM_U8) {
-        km_stage_timer t(c, ST_MINMAX);
-        if ((rc = kd_minmax(c, d_ref, dtype, H, W, sref, &sc->mm[0], d_mon, smon))) return rc;
-    }
-    // ---- arena: 2*nk Laplacians, 2*nk pyramids, nk corner lists, nk*nk track pairs, counters
-    km_pyr probe;
-    size_t pyr_bytes = 0;
-    build_pyramid_single(c, nullptr, H, W, prm->win_size, prm->max_level, nullptr, &probe, &pyr_bytes);
-    const size_t pts = ((size_t)cap * 2 * sizeof(float) + 255) & ~(size_t)255;
-    const size_t total = (size_t)2 * nk * (na + pyr_bytes) + (size_t)nk * pts + (size_t)2 * nk * nk * pts + 4096;
-    uint8_t *arena = (uint8_t *)km_ws(c, WS_AUTO, total);
-    if (!arena) return KM_E_NOMEM;
-    uint8_t *lap_ref = arena, *lap_mon = lap_ref + (size_t)nk * na, *pyr_store = lap_mon + (size_t)nk * na;
-    uint8_t *p0_store = pyr_store + (size_t)2 * nk * pyr_bytes, *trk_store = p0_store + (size_t)nk * pts;
-    int *d_counts = (int *)(trk_store + (size_t)2 * nk * nk * pts);      // [nk] corners per ref kernel, [nk*nk] kept tracks
-    KM_HIP(c, hipMemsetAsync(d_counts, 0, (size_t)(nk + nk * nk) * sizeof(int), c->stream));
-    km_pyr PR[8], PM[8];
-    {
-        // the uint8 stretch (klt.py:42-49; [+ 255 - x, klt.py:419]) rides in every Laplacian pass, as in the tile pipeline: both images
-        // of a kernel size in ONE launch from the raw rasters - the marching kernel for k <= 7; no uint8 copies of the rasters exist
-        km_stage_timer t(c, ST_LAPLACIAN);
-        for (int k = 0; k < nk; k++) {
-            const bool first = k == 0 && mask_auto != nullptr;
-            if ((rc = kd_stretch_laplacian_pair(c, d_ref, d_mon, dtype, H, W, sref, smon, sc->mm, ksizes[k], ksizes[k], prm->invert_mon, nodata_ref, nodata_mon,
-                                                lap_ref + (size_t)k * na, lap_mon + (size_t)k * na, first ? mask_auto : nullptr, first ? &sc->valid : nullptr)))
-                return rc;
-        }
-    }
-    const int n_lim = prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap;
-    // ---- ONE pipeline for the whole search where the batched forms cover the case (round 6; two-level pyramids, maxCorners > 0, the
-    // synchronisation-free corner path): the 2 nk pyramids in one launch, the nk corner detections as one batch of units (fused
-    // eigenvalue pass + selection chains side by side, nothing read back in between), the nk^2 tracker runs as ONE LK launch and one
-    // count launch.  Two host synchronisations per search (corner counts + flags; inlier counts) instead of nk + 2, 4 + 2 nk launches of
-    // dense kernels instead of 7 nk + 2 nk^2.  Anything the batched forms refuse goes through the loops below, run by run.
-    int n_p0[8];
-    const int *d_np0[8];                                             // device word holding the corner count of reference kernel k
-    bool corners_done = false, tracks_done = false;
-    const bool batchable = prm->max_level == 1 && probe.levels == 1 && nk <= KM_UNITS_MAX && nk * nk <= KM_LK_JOBS_MAX && spec_path_covers(c, prm) &&
-                           c->opt_eig3 && c->opt_lk2 && W >= 512 && H >= 2 * prm->block_size + 8;
-    km_units U;
-    if (batchable) {
-        U.n = nk; U.dtype = KM_U8; U.capk = n / 8 + 4096 * KM_NSHARD;
-        unsigned long long *keys = (unsigned long long *)km_ws(c, WS_KEYS0, U.capk * sizeof(unsigned long long) * (size_t)nk);
-        if (!keys) return KM_E_NOMEM;
-        for (int k = 0; k < nk; k++) {
-            U.H[k] = H; U.W[k] = W; U.x_off[k] = 0.f; U.y_off[k] = 0.f;
-            U.lap_ref[k] = lap_ref + (size_t)k * na; U.lap_mon[k] = lap_mon + (size_t)k * na; U.mask[k] = const_cast<uint8_t *>(mask);
-            U.sc[k] = (km_scalars *)(sc_base + sc_stride * (size_t)(k + 1));
-            U.keys[k] = keys + U.capk * (size_t)k;
-            U.p0[k] = (float *)(p0_store + (size_t)k * pts);
-            U.eig_partial[k] = nullptr; U.eig_npartial[k] = 0;
-            km_pyr &A = U.A[k], &B = U.B[k];
-            A.img[0] = U.lap_ref[k]; B.img[0] = U.lap_mon[k];
-            A.H[0] = B.H[0] = H; A.W[0] = B.W[0] = W;
-            A.img[1] = pyr_store + (size_t)(2 * k) * pyr_bytes; B.img[1] = pyr_store + (size_t)(2 * k + 1) * pyr_bytes;
-            A.H[1] = B.H[1] = (H + 1) / 2; A.W[1] = B.W[1] = (W + 1) / 2;
-            A.levels = B.levels = 1;
-            d_np0[k] = &U.sc[k]->n_corners;
-        }
-        {
-            km_stage_timer t(c, ST_PYRAMID);
-            if ((rc = kd_pyrdown_units(c, U, 1))) return rc;
-        }
-        for (int k = 0; k < nk; k++) { PR[k] = U.A[k]; PM[k] = U.B[k]; }
-        {
-            km_stage_timer t(c, ST_EIGEN);
-            rc = k3_eig_candidates_units(c, U, prm->block_size, prm->quality_level);
-        }
-        if (rc == KM_OK) {
-            km_stage_timer t(c, ST_SELECT);
-            rc = kf_rank_select_units(c, U, prm->max_corners, prm->quality_level, prm->min_distance, cap);
-        }
-        if (rc != KM_OK && rc != KM_E_UNSUPPORTED) return rc;
-        if (rc == KM_OK) {
-            unsigned flags[8];
-            for (int k = 0; k < nk; k++) { KM_D2H(c, &n_p0[k], &U.sc[k]->n_corners, sizeof(int)); KM_D2H(c, &flags[k], &U.sc[k]->flags, sizeof(unsigned)); }
-            KM_FLUSH(c);
-            for (int k = 0; k < nk; k++) {
-                if (!flags[k]) continue;
-                // the unit did not fit the fixed capacities of the synchronisation-free corner path: its corners through the exact one
-                c->stats.path_flags |= KM_PATH_SPEC_RETRY;
-                KM_HIP(c, hipMemsetAsync(&sc->max_eig_key, 0, sizeof(km_scalars) - offsetof(km_scalars, max_eig_key), c->stream));
-                if ((rc = gftt_dev(c, lap_ref + (size_t)k * na, mask, H, W, prm->max_corners, prm->quality_level, prm->min_distance, prm->block_size, U.p0[k], cap, sc)))
-                    return rc;
-                KM_HIP(c, hipMemcpyAsync(&U.sc[k]->n_corners, &sc->n_corners, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-                KM_D2H(c, &n_p0[k], &sc->n_corners, sizeof(int));
-                KM_FLUSH(c);
-            }
-            corners_done = true;
-        }
-    }
-    if (!corners_done) {
-        {
-            km_stage_timer t(c, ST_PYRAMID);
-            for (int k = 0; k < nk; k++)
-                if ((rc = build_pyramid_single(c, lap_ref + (size_t)k * na, H, W, prm->win_size, prm->max_level, pyr_store + (size_t)(2 * k) * pyr_bytes, &PR[k], nullptr)) ||
-                    (rc = build_pyramid_single(c, lap_mon + (size_t)k * na, H, W, prm->win_size, prm->max_level, pyr_store + (size_t)(2 * k + 1) * pyr_bytes, &PM[k], nullptr)))
-                    return rc;
-        }
-        // ---- corners of every reference Laplacian (klt.py:494), one after the other
-        for (int k = 0; k < nk; k++) {
-            float *p0 = (float *)(p0_store + (size_t)k * pts);
-            // gftt_dev starts from a clean scalar block; the min/max and the valid-pixel count gathered above stay
-            KM_HIP(c, hipMemsetAsync(&sc->max_eig_key, 0, sizeof(km_scalars) - offsetof(km_scalars, max_eig_key), c->stream));
-            if ((rc = gftt_dev(c, lap_ref + (size_t)k * na, mask, H, W, prm->max_corners, prm->quality_level, prm->min_distance, prm->block_size, p0, cap, sc)))
-                return rc;
-            KM_HIP(c, hipMemcpyAsync(&d_counts[k], &sc->n_corners, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-            KM_D2H(c, &n_p0[k], &sc->n_corners, sizeof(int));
-            d_np0[k] = &d_counts[k];
-        }
-        KM_FLUSH(c);
-    }
-    // ---- nk*nk tracker runs (mon kernel outer, ref kernel inner)
-    if (corners_done) {
-        km_lk_job jobs[KM_LK_JOBS_MAX];
-        km_count_jobs CJ;
-        for (int im = 0; im < nk; im++)
-            for (int ir = 0; ir < nk; ir++) {
-                const int combo = im * nk + ir;
-                km_lk_job &j = jobs[combo];
-                j.A = PR[ir]; j.B = PM[im]; j.pts_in = (const float *)(p0_store + (size_t)ir * pts); j.d_n = d_np0[ir];
-                j.p1 = (float *)(trk_store + (size_t)(2 * combo) * pts); j.p0r = (float *)(trk_store + (size_t)(2 * combo + 1) * pts);
-                CJ.p0[combo] = j.pts_in; CJ.p0r[combo] = j.p0r; CJ.d_n[combo] = j.d_n;      // (a reference kernel without corners: 0 points, count 0)
-            }
-        {
-            km_stage_timer t(c, ST_LK);
-            rc = kl_jobs_launch(c, jobs, nk * nk, n_lim, prm->win_size, prm->max_count, prm->epsilon);
-            if (rc == KM_OK) rc = kf_count_kept_jobs(c, CJ, nk * nk, n_lim, 0.1f, &d_counts[nk]);
-        }
-        if (rc != KM_OK && rc != KM_E_UNSUPPORTED) return rc;
-        tracks_done = rc == KM_OK;
-    }
-    if (!tracks_done) {
-        km_stage_timer t(c, ST_LK);
-        for (int im = 0; im < nk; im++)
-            for (int ir = 0; ir < nk; ir++) {
-                if (n_p0[ir] <= 0) continue;
-                const int combo = im * nk + ir;
-                float *p0 = (float *)(p0_store + (size_t)ir * pts);
-                float *p1 = (float *)(trk_store + (size_t)(2 * combo) * pts), *p0r = (float *)(trk_store + (size_t)(2 * combo + 1) * pts);
-                if ((rc = kl_track(c, PR[ir], PM[im], p0, d_np0[ir], n_lim, prm->win_size, prm->max_count, prm->epsilon, true, p1, p0r)) ||
-                    (rc = kf_count_kept(c, p0, p0r, d_np0[ir], n_lim, 0.1f, &d_counts[nk + combo])))
-                    return rc;
-            }
-    }
-    int kept[64];
-    KM_D2H(c, kept, d_counts + nk, (size_t)nk * nk * sizeof(int));
-    unsigned long long valid = 0;
-    KM_D2H(c, &valid, &sc->valid, sizeof valid);
-    KM_FLUSH(c);
-    c->stats.valid_pixels = (int64_t)valid;
-    double best_ratio = -1.0;
-    int best = -1;
-    for (int im = 0; im < nk; im++)
-        for (int ir = 0; ir < nk; ir++) {
-            const int combo = im * nk + ir;
-            if (n_p0[ir] <= 0) { out_ratios[combo] = 0.0; continue; }          // klt_tracker returned None: score 0, never the best
-            const double ratio = (double)kept[combo] / (double)n_p0[ir];
-            out_ratios[combo] = ratio;
-            if (ratio > best_ratio) { best_ratio = ratio; best = combo; }
-        }
-    const size_t fb = 16 + (size_t)cap * 6 * sizeof(float);
-    char *d_out = (char *)km_ws(c, WS_FRAME, fb);
-    if (!d_out) return KM_E_NOMEM;
-    if ((rc = frame_block_free(c))) return rc;
-    out_best[0] = out_best[1] = -1;
-    if (best < 0) {
-        memset(host_out, 0, 16);
-        return KM_OK;
-    }
-    const int bm = best / nk, br = best % nk;
-    out_best[0] = ksizes[bm]; out_best[1] = ksizes[br];
-    {
-        km_stage_timer t(c, ST_FRAME);
-        if ((rc = kf_frame(c, (const float *)(p0_store + (size_t)br * pts), (const float *)(trk_store + (size_t)(2 * best) * pts),
-                           (const float *)(trk_store + (size_t)(2 * best + 1) * pts), d_np0[br], n_lim, cap, 0.1f, x_off, y_off, d_out, nullptr, W)))
-            return rc;
-    }
-    KM_D2H(c, host_out, d_out, fb);
-    KM_FLUSH(c);
-    c->stats.n_init = ((const int *)host_out)[1];
-    return KM_OK;
 }
 
 int km_klt_tile_frame_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
@@ -887,83 +630,15 @@ int km_klt_tile_frame_submit(km_ctx *c, const void *d_ref, const void *d_mon, in
 {
     if (!c) return km_fail(nullptr, KM_E_ARG, "null context");
     if (!ticket) return km_fail(c, KM_E_ARG, "klt_tile_frame_submit: null ticket");
-    const int k = c->fslot_next;
-    km_frame_slot *slot = &c->fslot[k];
-    if (slot->pending.load(std::memory_order_acquire)) {   // never waited for: its block is about to be overwritten
-        KM_HIP(c, hipEventSynchronize(slot->done));
-        slot->pending.store(0, std::memory_order_release);
-    }
-    c->ev_cur = 1 + k;
-    const int rc = tile_frame_impl(c, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, x_off, y_off, d_ref_full,
+    int k;
+    km_frame_slot *slot;
+    int rc = frame_slot_claim(c, nullptr, &k, &slot);
+    if (rc) return rc;
+    rc = tile_frame_impl(c, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, x_off, y_off, d_ref_full,
                                    d_mon_full, Hf, Wf, sref_f, smon_f, d_ref_full != nullptr, zncc_threshold, nullptr, cap, slot);
     c->ev_cur = 0;
     if (rc) return rc;
-    slot->pending.store(1, std::memory_order_release);
-    c->fslot_next = (k + 1) % KM_FRAME_SLOTS;
-    *ticket = k;
+    frame_slot_commit(c, k, ticket);
     return KM_OK;
 }
-
-// Touches only the slot (no context state, no error string): safe from another thread while the context is submitting.
-int km_frame_wait(km_ctx *c, int ticket, const void **block, size_t *bytes)
-{
-    if (!c || ticket < 0 || ticket >= KM_FRAME_SLOTS || !block) return KM_E_ARG;
-    km_frame_slot *slot = &c->fslot[ticket];
-    if (!slot->done || !slot->pending.load(std::memory_order_acquire)) return KM_E_ARG;
-    // The waiting thread has nothing else to do: poll and SLEEP (hipEventSynchronize spins - also on an event created with
-    // hipEventBlockingSync - and kept one CPU per rank at 100 %: 0.72 of every 0.91-ms step; eight ranks want those CPUs for RCCL's proxies)
-    // (the kernel rounds a sleep up by the thread's timer slack, 50 us by default: 1 us for the threads that wait here)
-    // (the slack is this thread's for the duration of the wait only: the caller may be an application thread - ADVICE r5)
-    const int slack_before = prctl(PR_GET_TIMERSLACK, 0UL, 0UL, 0UL, 0UL);
-    (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0UL, 0UL, 0UL);
-    struct slack_restore { int v; ~slack_restore() { if (v > 0) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)v, 0UL, 0UL, 0UL); } } slack_guard{slack_before};
-    // a pipelined batched submission enqueues its tail (LK .. copy-out) with the NEXT submission or km_frame_flush: wait for that first.
-    // Nobody doing either for 100 ms is a caller that forgot to flush - the tail is then enqueued from here (under the context's
-    // enqueue lock; every other entry point of the submitting thread flushes before it touches the context)
-    for (int spins = 0; slot->deferred.load(std::memory_order_acquire); spins++) {
-        if (spins >= 5000) { const int rf = km_units_flush(c, false); if (rf) return rf; break; }
-        struct timespec ts = {0, 20000};
-        nanosleep(&ts, nullptr);
-    }
-    for (;;) {
-        const hipError_t e = hipEventQuery(slot->done);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) return KM_E_HIP;
-        struct timespec ts = {0, 20000};                  // 20 us: a hundredth of a batched submission
-        nanosleep(&ts, nullptr);
-    }
-    slot->pending.store(0, std::memory_order_release);
-    *block = slot->host;
-    if (bytes) *bytes = slot->bytes;
-    return KM_OK;
-}
-
-// Device-side hand-over of a submitted frame's block to a stream of the CALLER: `hip_stream` (a hipStream_t, e.g. the stream an RCCL
-// all-gather of the frame sink is issued on) waits - on the device, the host does not block - until the block of frame `ticket` has
-// been written to the frame sink that was set when the frame was submitted.
-int km_stream_wait_frame(km_ctx *c, int ticket, void *hip_stream)
-{
-    if (!c || ticket < 0 || ticket >= KM_FRAME_SLOTS) return km_fail(c, KM_E_ARG, "km_stream_wait_frame: bad ticket %d", ticket);
-    km_frame_slot *slot = &c->fslot[ticket];
-    if (!slot->sunk || !slot->sunk_valid) return km_fail(c, KM_E_ARG, "km_stream_wait_frame: frame %d was submitted without a frame sink", ticket);
-    KM_HIP(c, hipStreamWaitEvent((hipStream_t)hip_stream, slot->sunk, 0));
-    return KM_OK;
-}
-
-// Stage spans of frame `ticket` (after km_frame_wait; profiling enabled), same order as km_get_stage_ms.
-int km_frame_stage_ms(km_ctx *c, int ticket, float *out, int cap, int *n)
-{
-    if (!c || ticket < 0 || ticket >= KM_FRAME_SLOTS || !out) return KM_E_ARG;
-    const int m = cap < ST_COUNT ? cap : ST_COUNT;
-    for (int i = 0; i < m; i++) {
-        out[i] = 0.f;
-        float ms = 0.f;
-        if (c->ev_ready && c->evs_used[1 + ticket][i] &&
-            hipEventElapsedTime(&ms, c->evs[1 + ticket][i][0], c->evs[1 + ticket][i][1]) == hipSuccess)
-            out[i] = ms;
-    }
-    if (n) *n = m;
-    return KM_OK;
-}
-
 }  // extern "C"

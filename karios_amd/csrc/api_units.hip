@@ -16,8 +16,6 @@
 
 #include <cstring>
 
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- software pipeline over consecutive submissions ("units_pipeline" 1; karios_amd.stream.FrameStream switches it on)
 // A submission is three instruction-bound dense stages - L (stretch + Laplacians + mask), E (fused eigenvalue pass), K (LK) - and two
 // latency-bound chains - C (corner selection: nine launches, between E and K) and F (FB test / frame order / ZNCC / MI, behind K).  In
@@ -39,7 +37,7 @@ struct km_units_tail {
     int n = 0, n_max = 0, cap = 0, dtype = 0;
     bool with_zncc = false, with_mi = false, piped = false, profile_skip = false;
     double zncc_threshold = 0.0;
-    size_t fb = 0, ob = 0, ob_al = 0;
+    km_frame_layout L;
     char *d_out = nullptr;
     void *sink = nullptr;                 // the frame sink as it was set at submission time
     size_t sink_pitch = 0;
@@ -86,11 +84,8 @@ static int units_tail(km_ctx *c, km_units_tail &T)
         km_score_units S;
         for (int u = 0; u < n; u++) {
             km_score_unit &s = S.u[u];
-            const float *f = (const float *)(U.frame[u] + 16);
             s.ref = U.ref_full[u]; s.mon = U.mon_full[u]; s.Href = s.Hmon = U.Hf[u]; s.Wref = s.Wmon = U.Wf[u]; s.sref = U.sref_f[u]; s.smon = U.smon_f[u];
-            s.x0 = f; s.y0 = f + T.cap; s.dx = f + 2 * (size_t)T.cap; s.dy = f + 3 * (size_t)T.cap; s.score = f + 4 * (size_t)T.cap;
-            s.d_n = (const int *)U.frame[u];
-            s.out = (double *)(U.frame[u] + T.fb); s.out2 = nullptr;
+            T.L.score_unit(s, U.frame[u], false);
             s.win = U.win[u];
         }
         {
@@ -98,7 +93,7 @@ static int units_tail(km_ctx *c, km_units_tail &T)
             if ((rc = kz_zncc_units(c, S, n, T.dtype, T.n_max, (float)T.zncc_threshold))) return rc;
         }
         if (T.with_mi) {
-            for (int u = 0; u < n; u++) { S.u[u].out = (double *)(U.frame[u] + T.fb) + T.cap; S.u[u].out2 = S.u[u].out + T.cap; }
+            for (int u = 0; u < n; u++) T.L.score_unit(S.u[u], U.frame[u], true);
             km_stage_timer t(c, ST_MI);
             if ((rc = kmi_units(c, S, n, T.dtype, T.n_max, (float)T.zncc_threshold))) return rc;
         }
@@ -108,7 +103,7 @@ static int units_tail(km_ctx *c, km_units_tail &T)
     // own order - one stream fewer: the runtime maps streams onto FOUR hardware queues, and whenever the copy stream shared one with the
     // main stream its device-side wait for this chain held the next eigenvalue pass up (1 ms per 16-unit step, profiles/timeline_r06_c4.txt)
     if (!T.piped && (rc = km_block_stream(c))) return rc;
-    if ((rc = frame_blocks_out(c, slot, T.d_out, T.ob, T.ob_al, n, T.sink, T.sink_pitch, T.piped ? c->chain_stream : c->d2h_stream))) return rc;
+    if ((rc = frame_blocks_out(c, slot, T.d_out, T.L, n, T.sink, T.sink_pitch, T.piped ? c->chain_stream : c->d2h_stream))) return rc;
     if (T.piped) {      // the lane's next submission may rewrite its scalars / points / frame buffers once this chain (copies included) is through
         if ((rc = km_record(c, ev[EV_F_DONE], c->chain_stream))) return rc;
         c->lane_f_recorded[T.lane] = true;
@@ -156,20 +151,8 @@ extern "C++" int km_units_flush(km_ctx *c, bool join)
     return rc || !join ? rc : join_lanes(c);
 }
 
-extern "C" {
-
-// Enqueue whatever a pipelined batched submission deferred (include/karios_hip.h).  The submitting thread calls it when no further
-// submission follows (FrameStream.drain, PendingBatch.wait on the submitting thread); every other entry point and km_ctx_sync do it
-// themselves.
-int km_frame_flush(km_ctx *c, int ticket)
-{
-    if (!c) return km_fail(nullptr, KM_E_ARG, "null context");
-    if (ticket >= 0 && (ticket >= KM_FRAME_SLOTS || !c->fslot[ticket].deferred.load(std::memory_order_acquire))) return KM_OK;   // not the deferred one
-    return km_units_flush(c, false);
-}
-
-int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype, const double *nodata_ref, const double *nodata_mon,
-                              const km_klt_params *prm, double zncc_threshold, int cap, int *ticket)
+// the argument checks of a batched submission, and what the batch form does not cover (KM_E_UNSUPPORTED, no message: unit by unit then)
+static int units_check_args(km_ctx *c, const km_unit *units, int n, int dtype, const km_klt_params *prm, int cap, const int *ticket)
 {
     int rc;
     if (!c) return km_fail(nullptr, KM_E_ARG, "null context");
@@ -186,7 +169,6 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     if (!km_lap_ksize_ok(prm->ksize_ref) || !km_lap_ksize_ok(prm->ksize_mon)) return KM_E_UNSUPPORTED;
     const bool with_zncc = units[0].d_ref_full != nullptr;
     const bool user_mask = units[0].d_mask != nullptr;
-    const bool with_mi = with_zncc && c->opt_frame_mi;
     if (with_zncc && dtype == KM_F32) return KM_E_UNSUPPORTED;
     for (int u = 0; u < n; u++) {
         const km_unit &q = units[u];
@@ -198,27 +180,45 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         if (with_zncc && ((rc = check_image(c, q.d_ref_full, q.Hf, q.Wf, q.sref_f, "klt_units_frame_submit")) ||
                           (rc = check_image(c, q.d_mon_full, q.Hf, q.Wf, q.smon_f, "klt_units_frame_submit"))))
             return rc;
-        if (q.W > 65535) return km_fail(c, KM_E_ARG, "klt_units_frame_submit: unit of %d columns (the device-side frame ordering holds at most 65535)", q.W);
+        if ((rc = check_frame_width(c, "klt_units_frame_submit", "unit", q.W))) return rc;
         if (q.W < 512 || q.H < 2 * prm->block_size + 8 || (q.W + 1) / 2 <= prm->win_size || (q.H + 1) / 2 <= prm->win_size) return KM_E_UNSUPPORTED;
         if ((prm->ksize_ref == 11 || prm->ksize_mon == 11) && q.H < 16) return KM_E_UNSUPPORTED;      // (the marching kernel's radius-5 form: kd_stretch_laplacian_units)
     }
+    return KM_OK;
+}
+
+extern "C" {
+
+// Enqueue whatever a pipelined batched submission deferred (include/karios_hip.h).  The submitting thread calls it when no further
+// submission follows (FrameStream.drain, PendingBatch.wait on the submitting thread); every other entry point and km_ctx_sync do it
+// themselves.
+int km_frame_flush(km_ctx *c, int ticket)
+{
+    if (!c) return km_fail(nullptr, KM_E_ARG, "null context");
+    if (ticket >= 0 && (ticket >= KM_FRAME_SLOTS || !c->fslot[ticket].deferred.load(std::memory_order_acquire))) return KM_OK;   // not the deferred one
+    return km_units_flush(c, false);
+}
+
+int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype, const double *nodata_ref, const double *nodata_mon,
+                              const km_klt_params *prm, double zncc_threshold, int cap, int *ticket)
+{
+    int rc;
+    if ((rc = units_check_args(c, units, n, dtype, prm, cap, ticket))) return rc;
+    const bool with_zncc = units[0].d_ref_full != nullptr;
+    const bool user_mask = units[0].d_mask != nullptr;
+    const bool with_mi = with_zncc && c->opt_frame_mi;
     if (!c->utail) c->utail.reset(new km_units_tail);
     std::lock_guard<std::mutex> enqueue_lock(c->enqueue_mu);
     km_units_tail &old_tail = *c->utail;
     const bool piped = c->opt_units_pipeline && dtype != KM_U8;
     // (a pipelined submission was the previous one: its tail first, and this one behind both lanes' chains)
     if (!piped && ((rc = units_flush_locked(c)) || (rc = join_lanes(c)))) return rc;
-    const int k = c->fslot_next;
-    km_frame_slot *slot = &c->fslot[k];
-    if (slot->pending.load(std::memory_order_acquire)) {   // never waited for: its block is about to be overwritten
-        if (slot->deferred.load(std::memory_order_acquire)) return km_fail(c, KM_E_ARG, "klt_units_frame_submit: frame slot %d still holds a deferred submission", k);
-        KM_HIP(c, hipEventSynchronize(slot->done));
-        slot->pending.store(0, std::memory_order_release);
-    }
     const int lane = piped ? (old_tail.armed ? 1 - old_tail.lane : 0) : 0;
     hipStream_t const main_stream = c->stream;
     units_scope scope(c, false);
-    c->ev_cur = 1 + k;
+    int k;
+    km_frame_slot *slot;
+    if ((rc = frame_slot_claim(c, "klt_units_frame_submit", &k, &slot))) return rc;
     c->in_units_submit = true;
     if ((rc = begin_call(c, RESET_KLT))) return rc;
     memset(&c->stats, 0, sizeof c->stats);
@@ -248,8 +248,8 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     }
     U.capk = max_px / 8 + 4096 * KM_NSHARD;
     const size_t sc_stride = up256(sizeof(km_scalars)), pb = up256((size_t)cap * 2 * sizeof(float));
-    const size_t fb = 16 + (size_t)cap * 6 * sizeof(float), ob = fb + (with_zncc ? (size_t)cap * sizeof(double) : 0) + (with_mi ? (size_t)cap * 2 * sizeof(double) : 0);
-    const size_t ob_al = up256(ob);
+    const km_frame_layout L(cap, with_zncc, with_mi);
+    const size_t ob = L.ob, ob_al = L.ob_al;
     uint8_t *lap_ref = (uint8_t *)km_ws(c, WS_U8_A, px_total), *lap_mon = (uint8_t *)km_ws(c, WS_U8_B, px_total), *mask = (uint8_t *)km_ws(c, WS_MASK, px_total);
     unsigned long long *keys = (unsigned long long *)km_ws(c, WS_KEYS0, U.capk * sizeof(unsigned long long) * n);
     char *sc = (char *)km_ws(c, WS_SCALARS, sc_stride * n);
@@ -265,12 +265,8 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         U.p0[u] = (float *)(p0 + pb * u); U.p1[u] = (float *)(p1 + pb * u); U.p0r[u] = (float *)(p0r + pb * u);
         U.frame[u] = d_out + ob_al * u;
         U.eig_partial[u] = nullptr; U.eig_npartial[u] = 0;
-        km_pyr &A = U.A[u], &B = U.B[u];
-        A.img[0] = U.lap_ref[u]; B.img[0] = U.lap_mon[u];
-        A.H[0] = B.H[0] = U.H[u]; A.W[0] = B.W[0] = U.W[u];
-        A.img[1] = pyr_a + pyr_off[u]; B.img[1] = pyr_b + pyr_off[u];
-        A.H[1] = B.H[1] = (U.H[u] + 1) / 2; A.W[1] = B.W[1] = (U.W[u] + 1) / 2;
-        A.levels = B.levels = 1;
+        pyr_two_level(U.A[u], U.lap_ref[u], pyr_a + pyr_off[u], U.H[u], U.W[u]);
+        pyr_two_level(U.B[u], U.lap_mon[u], pyr_b + pyr_off[u], U.H[u], U.W[u]);
     }
     if ((rc = frame_sink_check(c, c->frame_sink_pitch, n, ob)) || (rc = frame_slot_reserve(c, slot, ob * n))) return rc;
     // The lane's previous submission must have left its frame stage before its scalars, points and frame buffers are reset - the scalar
@@ -279,7 +275,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     // submission - which need the min / max only - stood behind the other lane's frame stage, which runs beside the previous
     // eigenvalue pass and outlasts it (16 units of 5490^2: 0.8 ms of an idle main stream per step, tools/investigations/stage_order.py).  The main
     // stream waits for the setup in front of the eigenvalue pass, the first kernel of this submission that touches the scalars.
-    const int n_max = prm->max_corners < cap ? prm->max_corners : cap;
+    const int n_max = corner_limit(prm, cap);
     const bool setup_on_aux = piped && dtype != KM_U8;
     auto setup = [&]() -> int {
         KM_HIP(c, hipMemsetAsync(sc, 0, sc_stride * n, c->stream));
@@ -364,7 +360,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     km_units_tail &T = *c->utail;
     T.lane = lane; T.slot = k; T.U = U; T.prm = *prm; T.n = n; T.n_max = n_max; T.cap = cap; T.dtype = dtype;
     T.with_zncc = with_zncc; T.with_mi = with_mi; T.piped = piped; T.zncc_threshold = zncc_threshold; T.profile_skip = c->profile_skip;
-    T.fb = fb; T.ob = ob; T.ob_al = ob_al; T.d_out = d_out;
+    T.L = L; T.d_out = d_out;
     T.sink = c->frame_sink; T.sink_pitch = c->frame_sink_pitch;
     slot->sunk_valid = false;
     if (piped) {
@@ -372,9 +368,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         slot->deferred.store(1, std::memory_order_release);
     } else if ((rc = units_tail(c, T)))
         return rc;
-    slot->pending.store(1, std::memory_order_release);
-    c->fslot_next = (k + 1) % KM_FRAME_SLOTS;
-    *ticket = k;
+    frame_slot_commit(c, k, ticket);
     return KM_OK;
 }
 

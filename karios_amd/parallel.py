@@ -449,7 +449,7 @@ def pack_frame(frame: DataFrame | None, cap: int, with_zncc: bool = False) -> np
         z = np.full(cap, np.nan)
         if "zncc_score" in frame.columns:
             z[:n] = frame["zncc_score"].to_numpy(np.float64)
-        blk[4 + 6 * cap:] = z.view(np.float32)
+        blk[frames.block_words(cap):] = z.view(np.float32)
     return blk
 
 

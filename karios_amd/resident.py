@@ -502,7 +502,7 @@ class ResidentPair:
         bx_off, by_off, bx, by, off = self._box(box)
         prm = make_params(conf, 1, 1, bool(invert_mon))
         cap = prm.max_corners if prm.max_corners > 0 else max(1, (bx * by) // 4)
-        buf = np.empty(4 + 6 * cap, np.float32)
+        buf = np.empty(frames.block_words(cap), np.float32)
         ks = np.ascontiguousarray(candidates, np.int32)
         nk = len(ks)
         ratios = np.zeros(nk * nk, np.float64)

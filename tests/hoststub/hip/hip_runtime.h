@@ -44,6 +44,8 @@ struct stub_state {
     int fail_malloc_after = -1;      // test knob: the n-th hipMalloc from now fails
     int fail_host_malloc_after = -1; //   ... the n-th hipHostMalloc
     int fail_create_after = -1;      //   ... the n-th creation of a stream or an event
+    bool lk_jobs_unsupported = false;   // kl_jobs_launch answers KM_E_UNSUPPORTED: the kernel-size search with batched corners, trackers one by one
+    bool corners_like_exact = false;    // kf_rank_select_units finds the corners the stand-ins of the exact path find
 };
 stub_state &stub();
 // true: this call is the one a knob condemned (the knob then disarms itself)

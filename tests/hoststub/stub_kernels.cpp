@@ -90,6 +90,7 @@ void stub_counters(long out[3])
     out[0] = stub().device_allocs; out[1] = stub().host_allocs; out[2] = stub().pageable_async_copies;
 }
 void stub_fail_malloc_after(int n) { stub().fail_malloc_after = n; }
+void stub_lk_jobs_unsupported(int on) { stub().lk_jobs_unsupported = on != 0; }
 }
 
 // ------------------------------------------------------------------ pixel access
@@ -384,8 +385,24 @@ int kd_pyrdown_units(km_ctx *, const km_units &U, int level)
     }
     return KM_OK;
 }
-int kf_rank_select_units(km_ctx *, const km_units &U, int max_corners, double, double, int cap)
+// corners_like_exact (tests/hoststub/frame_main.cpp): the corners the stand-ins of the exact path (kd_min_eigen, kd_candidates, the sort,
+// ks_select) find in the unit's Laplacian, so that every form of the kernel-size search must agree; "spec_flag" flags every unit
+int kf_rank_select_units(km_ctx *c, const km_units &U, int max_corners, double, double, int cap)
 {
+    for (int u = 0; u < U.n && stub().corners_like_exact; u++) {
+        const int H = U.H[u], W = U.W[u];
+        std::vector<float> eig((size_t)H * W);
+        std::vector<unsigned long long> keys((size_t)H * W / 8 + 4096 * KM_NSHARD);
+        km_scalars sc = {};
+        unsigned max_key;
+        unsigned long long *sorted;
+        kd_min_eigen(c, U.lap_ref[u], U.mask[u], H, W, 0, eig.data(), &max_key);
+        kd_candidates(c, eig.data(), U.mask[u], H, W, 0.0, &sc, keys.data(), keys.size(), false);
+        ks_sort_keys_desc(c, keys.data(), std::min((size_t)sc.n_cand, keys.size()), &sorted);
+        ks_select(c, sorted, std::min((size_t)sc.n_cand, keys.size()), H, W, max_corners, 0.0, U.p0[u], cap, &sc, nullptr, true);
+        U.sc[u]->n_corners = sc.n_corners; U.sc[u]->flags = (unsigned)c->opt_spec_flag;
+    }
+    if (stub().corners_like_exact) return KM_OK;
     for (int u = 0; u < U.n; u++) {
         const int n = std::min(std::min(max_corners, cap), 40 + u);
         for (int i = 0; i < n; i++) { U.p0[u][2 * i] = (float)(20 + 7 * i % (U.W[u] - 40)); U.p0[u][2 * i + 1] = (float)(20 + 11 * i % (U.H[u] - 40)); }
@@ -394,8 +411,24 @@ int kf_rank_select_units(km_ctx *, const km_units &U, int max_corners, double, d
     }
     return KM_OK;
 }
-int kl_jobs_launch(km_ctx *, const km_lk_job *, int, int, int, int, double) { return KM_E_UNSUPPORTED; }   // (the search then runs its trackers one by one)
-int kf_count_kept_jobs(km_ctx *, const km_count_jobs &, int, int, float, int *) { return KM_OK; }
+// per job what kl_track / kf_count_kept do; the knob lk_jobs_unsupported: refused (the search then runs its trackers one by one)
+int kl_jobs_launch(km_ctx *c, const km_lk_job *jobs, int n_jobs, int n_max, int win, int max_count, double eps)
+{
+    if (stub().lk_jobs_unsupported) return KM_E_UNSUPPORTED;
+    for (int j = 0; j < n_jobs; j++) {
+        const int rc = kl_track(c, jobs[j].A, jobs[j].B, jobs[j].pts_in, jobs[j].d_n, n_max, win, max_count, eps, true, jobs[j].p1, jobs[j].p0r, nullptr);
+        if (rc) return rc;
+    }
+    return KM_OK;
+}
+int kf_count_kept_jobs(km_ctx *c, const km_count_jobs &J, int n_jobs, int n_max, float thr, int *counts)
+{
+    for (int j = 0; j < n_jobs; j++) {
+        const int rc = kf_count_kept(c, J.p0[j], J.p0r[j], J.d_n[j], n_max, thr, &counts[j]);
+        if (rc) return rc;
+    }
+    return KM_OK;
+}
 static km_units g_lk_units[2];       // (per workspace lane: a pipelined submission prepares its table before the previous one's LK is launched)
 int kl_units_prepare(km_ctx *c, const km_units &U, int, int, int, double) { g_lk_units[c->lane & 1] = U; return KM_OK; }
 int kl_units_launch(km_ctx *c, int n_units, int n_max, int win)
@@ -429,7 +462,7 @@ int kmi_units(km_ctx *, const km_score_units &A, int n_units, int, int n, float)
     for (int u = 0; u < n_units; u++) {
         const km_score_unit &s = A.u[u];
         const int m = std::min(*s.d_n, n);
-        for (int i = 0; i < m; i++) { s.out[i] = s.x0[i]; s.out2[i] = -s.x0[i]; }
+        for (int i = 0; i < n; i++) { s.out[i] = i < m ? (double)s.x0[i] : NAN; s.out2[i] = i < m ? -(double)s.x0[i] : NAN; }      // (the whole columns)
     }
     return KM_OK;
 }

@@ -595,7 +595,8 @@ def _rest_of_submit_wait_test(pair, conf, boxes, want):
 
 def test_auto_ksize_batched_search_matches_oracle_loop(ops, O):
     """km_klt_auto_ksize_frame_dev == the reference's 5x5 loop (klt.py:465-545) done with the oracle:
-    every inlier ratio, the winning pair (first maximum in itertools.product order) and the winner's frame."""
+    every inlier ratio, the winning pair (first maximum in itertools.product order) and the winner's frame.  At 300 columns it
+    exercises the run-by-run forms of the search; the batched ones (W >= 512) are held by tests/test_gpu_auto_ksize.py."""
     import itertools
     from karios_amd.core import KLTConfiguration
     from karios_amd.resident import ResidentPair
