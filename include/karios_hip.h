@@ -125,6 +125,13 @@ int km_set_profiling(km_ctx *ctx, int enable);
  *                  mutual_info_service.py:73-130) and `mi_score` (ZNCCService.compute_mi, zncc_service.py:240-287) of the same rows -
  *                  the whole scoring of KariosAPI._handle_klt_results (api/core.py:894-907) in the tile call: two more float64 columns
  *                  of `cap` entries behind the zncc column (NaN where score < threshold or the chip leaves the image); 0 (default)
+ *   "frame_clip"   1: every entry point that produces a frame block (km_klt_tile_frame_dev, km_klt_tile_frame_zncc_dev,
+ *                  km_klt_tile_frame_submit, km_klt_units_frame_submit) applies the tracker's iterative 3-sigma / 20-px outlier clip
+ *                  (klt.py:52-71, `outliers_filtering`; km_sigma_clip_dev) to the block between the frame stage and the scores: header
+ *                  word 0 becomes the number of survivors, the rows stay in (x0, y0) order, the index column becomes the row's position
+ *                  among the survivors, the score columns are those of the survivors.  A block of more than 32768 rows is refused
+ *                  (KM_E_UNSUPPORTED, nothing queued).  The value is read when the call is made: a pipelined submission keeps the
+ *                  value of its own call.  0 (default)
  *   "phase_fp64"   1: km_phase_shift* always evaluates in double precision (k_fft64.hip), the reference's precision; 0 (default):
  *                  hand-written float32 FFT where the image sides factor into {2,3,5,7,61}, double precision only when the
  *                  float32 correlation peak is not at least 1 % above every other sample
@@ -346,7 +353,7 @@ int km_klt_tile_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype
  * test / score of klt_tracker (klt.py:142-155) and the (x0, y0) ordering (klt.py:341-348) on the device.
  * host_out receives, in ONE device-to-host copy, 4 int32 {n_rows, n_init, 0, 0} followed by 6*cap float32:
  * x0 | y0 | dx | dy | score | index (int32 bit pattern: the row's label after pandas' in-place sort).
- * The optional 3-sigma outlier filter (klt.py:161-163) is not applied here. */
+ * The optional 3-sigma outlier filter (klt.py:161-163) is applied with km_set_option "frame_clip" 1 (cap <= 32768), not otherwise. */
 int km_klt_tile_frame_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int H, int W,
                           ptrdiff_t stride_ref, ptrdiff_t stride_mon, const uint8_t *d_mask,
                           ptrdiff_t stride_mask, const double *nodata_ref, const double *nodata_mon,
@@ -389,7 +396,8 @@ int km_mi_batch_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype
  * out_ratios[im*nk + ir] = inlier ratio len(points)/Ninit of (ksizes[im], ksizes[ir]) (0 where the reference's
  * klt_tracker returns None); the best pair is the first maximum; out_best = {mon_ksize, ref_ksize} or {-1,-1}.
  * host_out: frame block of the best pair (layout of km_klt_tile_frame_dev).  prm->ksize_* are ignored, prm->invert_mon
- * applies (255 - uint8(mon) before the Laplacians, klt.py:419); outlier filtering is not part of this entry point. */
+ * applies (255 - uint8(mon) before the Laplacians, klt.py:419); outlier filtering is not part of this entry point ("frame_clip" is
+ * ignored here: the inlier ratios would need a clip per combination). */
 int km_klt_auto_ksize_frame_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int H,
                                 int W, ptrdiff_t stride_ref, ptrdiff_t stride_mon,
                                 const uint8_t *d_mask, ptrdiff_t stride_mask,
@@ -645,6 +653,20 @@ int km_accuracy_stats(km_ctx *ctx, const float *dx, const float *dy, const float
                       int n_percent, const double *percents, km_accuracy_result *out);
 int km_accuracy_stats_dev(km_ctx *ctx, const float *d_dx, const float *d_dy, const float *d_score, int n, double thr, int carto, double factor,
                           int n_percent, const double *percents, km_accuracy_result *out);
+
+/* The tracker's iterative outlier clip (karios/matcher/klt.py:52-71) on resident float32 displacement columns, for n_units <=
+ * KM_UNITS_PER_SUBMISSION independent units in ONE launch.  Unit k: d_dx[k], d_dy[k] of n[k] <= 32768 rows (KM_E_UNSUPPORTED beyond).
+ * Repeat: mu = mean, s = std of each column as numpy 2 computes them in float32 (km_accuracy_stats); keep the rows with
+ * |dx - mu_x| < 3 s_x, |dy - mu_y| < 3 s_y, |dx - mu_x| < 20 and |dy - mu_y| < 20 (float32, strict; NaN compares false); stop when
+ * a round keeps every row or none is left, else go on with the compacted columns.  d_keep_index[k] (n[k] int32, device) receives the
+ * survivors' row indices in ascending order, d_result[k] (device) their number and the rounds computed.  The pointer tables and n
+ * are host arrays.  Asynchronous on the context stream; call km_ctx_sync (or copy with km_d2h) before reading results. */
+typedef struct km_clip_result {
+    int32_t count;                             /* survivors */
+    int32_t rounds;                            /* rounds whose statistics were computed (0 for an empty unit) */
+} km_clip_result;
+int km_sigma_clip_dev(km_ctx *ctx, const float *const *d_dx, const float *const *d_dy, const int *n, int n_units, int32_t *const *d_keep_index,
+                      km_clip_result *d_result);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,12 @@ class AccuracyResult(C.Structure):
                 ("order", C.c_float * (2 * ACC_MAX_PERCENTS))]
 
 
+class ClipResult(C.Structure):
+    """km_clip_result of include/karios_hip.h."""
+    _fields_ = [("count", C.c_int32), ("rounds", C.c_int32)]
+
+
+CLIP_MAX_ROWS = 32768          # rows one unit of km_sigma_clip_dev / the "frame_clip" stage holds
 UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
 E_ARG = -1                     # KM_E_ARG
 E_UNSUPPORTED = -4             # KM_E_UNSUPPORTED
@@ -175,6 +181,7 @@ SIGNATURES = {
     "km_count_valid_pixels_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, C.POINTER(C.c_int64)]),
     "km_accuracy_stats": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _d, _i, _pd, C.POINTER(AccuracyResult)]),
     "km_accuracy_stats_dev": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _d, _i, _pd, C.POINTER(AccuracyResult)]),
+    "km_sigma_clip_dev": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _pi, _i, C.POINTER(_vp), _vp]),
 }
 
 _lib = None

@@ -166,6 +166,7 @@ int km_set_option(km_ctx *c, const char *name, int value)
     if (strcmp(name, "aux_pyramid") == 0) { c->opt_aux_pyramid = value != 0; return KM_OK; }
     if (strcmp(name, "mm_early") == 0) { c->opt_mm_early = value != 0; return KM_OK; }
     if (strcmp(name, "frame_mi") == 0) { c->opt_frame_mi = value != 0; return KM_OK; }
+    if (strcmp(name, "frame_clip") == 0) { c->opt_frame_clip = value != 0; return KM_OK; }
     if (strcmp(name, "units_pipeline") == 0) {
         if (!value) { const int rf = km_units_flush(c); if (rf) return rf; }
         c->opt_units_pipeline = value != 0;

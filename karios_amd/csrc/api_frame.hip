@@ -2,6 +2,7 @@
 // kernel-size search (api_auto.hip): the frame slots (claim, reserve, commit), the frame sink, the copies of n blocks laid out by
 // km_frame_layout (api_internal.hpp), and what the caller does with a ticket: km_frame_wait, km_stream_wait_frame, km_frame_stage_ms.
 #include "api_internal.hpp"
+#include "k_clip.hpp"
 #include <time.h>
 #include <sys/prctl.h>
 
@@ -48,6 +49,26 @@ int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, const km
     c->frame_copy = slot->done;
     slot->bytes = ob * n;
     return KM_OK;
+}
+
+bool frame_clip_covers(int cap) { return cap <= cl::MAX_ROWS; }
+
+// unit k's working columns are slices of the lane's WS_CL_COLS; nobody reads the per-unit record here
+int frame_blocks_clip(km_ctx *c, char *const *d_blocks, int n, int cap)
+{
+    if (n < 1 || n > KC_UNITS_MAX || !frame_clip_covers(cap)) return km_fail(c, KM_E_INTERNAL, "frame clip: %d blocks of %d rows", n, cap);
+    const size_t rows = kc_ws_rows(cap);
+    float *ws = (float *)km_ws(c, WS_CL_COLS, rows * 4 * sizeof(float) * (size_t)n);
+    if (!ws) return KM_E_NOMEM;
+    kc_units A;
+    for (int k = 0; k < n; k++) {
+        kc_unit &u = A.u[k];
+        u = kc_unit();
+        float *base = ws + rows * 4 * (size_t)k;
+        u.frame = d_blocks[k]; u.cap = cap;
+        u.u = base; u.v = base + rows; u.idx = (int32_t *)(base + 2 * rows); u.lab = (int32_t *)(base + 3 * rows);
+    }
+    return kc_clip_units(c, A, n);
 }
 
 int frame_slot_claim(km_ctx *c, const char *who, int *k_out, km_frame_slot **slot_out)

@@ -137,6 +137,10 @@ int frame_slot_claim(km_ctx *c, const char *who, int *k, km_frame_slot **slot);
 int frame_slot_reserve(km_ctx *c, km_frame_slot *slot, size_t bytes);
 int frame_blocks_out(km_ctx *c, km_frame_slot *slot, const char *d_out, const km_frame_layout &L, int n, void *sink, size_t sink_pitch, hipStream_t s);
 void frame_slot_commit(km_ctx *c, int k, int *ticket);   // the claimed slot is pending: its ticket, and the ring moves on
+// "frame_clip": the tracker's outlier clip (k_clip.hip) of n finished frame blocks of `cap` rows on c->stream, between the frame stage and the
+// scores.  frame_clip_covers: what the stage takes - the entry points ask in front of their first launch
+bool frame_clip_covers(int cap);
+int frame_blocks_clip(km_ctx *c, char *const *d_blocks, int n, int cap);
 
 // ---- api_auto.hip: the arena of the kernel-size search, offsets from a 256-byte aligned base
 struct km_auto_arena {

@@ -1,8 +1,10 @@
 // Scoring entry points: ZNCCService.compute_zncc / _zncc2 (zncc_service.py:45-238), the mutual-information scores
 // (mutual_info_service.py:73-130, zncc_service.py:240-287), the DN-value filter of the key points (core.py:650-737) and
-// KariosAPI.analyze_accuracy (core.py:268-328): the valid-pixel count and GeometricStat (accuracy_statistics.py).
+// KariosAPI.analyze_accuracy (core.py:268-328): the valid-pixel count and GeometricStat (accuracy_statistics.py); the tracker's outlier clip
+// (klt.py:52-71) on resident columns.
 #include "api_internal.hpp"
 #include "k_accuracy.hpp"
+#include "k_clip.hpp"
 
 #include <cstring>
 #include <vector>
@@ -251,6 +253,35 @@ int km_accuracy_stats(km_ctx *c, const float *dx, const float *dy, const float *
     const float *src[3] = {dx, dy, score};
     for (int i = 0; i < 3 && n > 0; i++) { const int rch = h2d_now(c, in + (size_t)i * cap, src[i], (size_t)n * sizeof(float)); if (rch) return rch; }
     return accuracy_stats_dev(c, in, in + cap, in + 2 * (size_t)cap, n, thr, carto, factor, n_percent, percents, out);
+}
+
+// the tracker's outlier clip on resident columns (include/karios_hip.h): every check in front of the launch, a refused call queues nothing
+int km_sigma_clip_dev(km_ctx *c, const float *const *d_dx, const float *const *d_dy, const int *n, int n_units, int32_t *const *d_keep_index,
+                      km_clip_result *d_result)
+{
+    int rc;
+    if ((rc = begin_call(c))) return rc;
+    if (!d_dx || !d_dy || !n || !d_keep_index || !d_result) return km_fail(c, KM_E_ARG, "sigma_clip: null argument");
+    if (n_units < 1 || n_units > KC_UNITS_MAX) return km_fail(c, KM_E_ARG, "sigma_clip: %d units (1 .. %d per call)", n_units, KC_UNITS_MAX);
+    int n_max = 0;
+    for (int k = 0; k < n_units; k++) {
+        if (n[k] < 0 || (n[k] > 0 && (!d_dx[k] || !d_dy[k] || !d_keep_index[k]))) return km_fail(c, KM_E_ARG, "sigma_clip: bad columns of unit %d", k);
+        if (n[k] > cl::MAX_ROWS) return km_fail(c, KM_E_UNSUPPORTED, "sigma_clip: unit %d has %d rows (at most %d)", k, n[k], (int)cl::MAX_ROWS);
+        n_max = n[k] > n_max ? n[k] : n_max;
+    }
+    const size_t rows = kc_ws_rows(n_max);
+    float *ws = (float *)km_ws(c, WS_CL_COLS, rows * 4 * sizeof(float) * (size_t)n_units);
+    if (!ws) return KM_E_NOMEM;
+    kc_units A;
+    for (int k = 0; k < n_units; k++) {
+        kc_unit &u = A.u[k];
+        u = kc_unit();
+        float *base = ws + rows * 4 * (size_t)k;
+        u.dx = d_dx[k]; u.dy = d_dy[k]; u.n = n[k]; u.keep_index = d_keep_index[k];
+        u.u = base; u.v = base + rows; u.idx = (int32_t *)(base + 2 * rows); u.lab = (int32_t *)(base + 3 * rows);
+        u.rec = d_result + k;
+    }
+    return kc_clip_units(c, A, n_units);
 }
 
 }  // extern "C"

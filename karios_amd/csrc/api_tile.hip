@@ -549,6 +549,8 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
     if ((rc = check_dtype(c, "klt_tile_frame_dev", dtype)) || (rc = check_frame_width(c, "klt_tile_frame_dev", "tile", W))) return rc;
     if ((!host_out && !slot) || cap <= 0) return km_fail(c, KM_E_ARG, "klt_tile_frame_dev: null output");
     if ((rc = check_capacity(c, prm, cap))) return rc;
+    const bool with_clip = c->opt_frame_clip;
+    if (with_clip && !frame_clip_covers(cap)) return km_fail(c, KM_E_UNSUPPORTED, "klt_tile_frame_dev: the outlier clip holds at most 32768 rows (capacity %d)", cap);
     memset(&c->stats, 0, sizeof c->stats);
     c->evs_used[c->ev_cur][ST_ZNCC] = false; c->evs_used[c->ev_cur][ST_MI] = false;
     km_scalars *sc = scalars(c);
@@ -573,6 +575,7 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
         {
             km_stage_timer t(c, ST_FRAME);
             if ((rc = kf_frame(c, d_p0, d_p1, d_p0r, &sc->n_corners, n_max, cap, 0.1f, x_off, y_off, d_out, m.spec_used ? sc : nullptr, W))) return rc;
+            if (with_clip && (rc = frame_blocks_clip(c, &d_out, 1, cap))) return rc;      // ("frame_clip": the scores are the survivors')
         }
         if (with_zncc && (rc = tile_frame_scores(c, L, d_out, d_ref_full, d_mon_full, dtype, Hf, Wf, sref_f, smon_f, n_max, zncc_threshold, with_mi))) return rc;
         if ((rc = frame_sink_check(c, 0, 1, ob))) return rc;      // (a single block ignores the sink's pitch)

@@ -35,7 +35,7 @@ struct km_units_tail {
     km_units U;
     km_klt_params prm;
     int n = 0, n_max = 0, cap = 0, dtype = 0;
-    bool with_zncc = false, with_mi = false, piped = false, profile_skip = false;
+    bool with_zncc = false, with_mi = false, with_clip = false, piped = false, profile_skip = false;
     double zncc_threshold = 0.0;
     km_frame_layout L;
     char *d_out = nullptr;
@@ -79,6 +79,7 @@ static int units_tail(km_ctx *c, km_units_tail &T)
     {
         km_stage_timer t(c, ST_FRAME);
         if ((rc = kf_frame_units(c, U, T.n_max, T.cap, 0.1f))) return rc;
+        if (T.with_clip && (rc = frame_blocks_clip(c, U.frame, n, T.cap))) return rc;     // ("frame_clip" as it was when THIS submission was made)
     }
     if (T.with_zncc) {
         km_score_units S;
@@ -207,6 +208,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     const bool with_zncc = units[0].d_ref_full != nullptr;
     const bool user_mask = units[0].d_mask != nullptr;
     const bool with_mi = with_zncc && c->opt_frame_mi;
+    const bool with_clip = c->opt_frame_clip;      // (units_check_args refused cap > 32768, which is also what the clip takes)
     if (!c->utail) c->utail.reset(new km_units_tail);
     std::lock_guard<std::mutex> enqueue_lock(c->enqueue_mu);
     km_units_tail &old_tail = *c->utail;
@@ -359,7 +361,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     // ---- the tail: LK, frame stage, scores, copy-out - now, or with the next submission
     km_units_tail &T = *c->utail;
     T.lane = lane; T.slot = k; T.U = U; T.prm = *prm; T.n = n; T.n_max = n_max; T.cap = cap; T.dtype = dtype;
-    T.with_zncc = with_zncc; T.with_mi = with_mi; T.piped = piped; T.zncc_threshold = zncc_threshold; T.profile_skip = c->profile_skip;
+    T.with_zncc = with_zncc; T.with_mi = with_mi; T.with_clip = with_clip; T.piped = piped; T.zncc_threshold = zncc_threshold; T.profile_skip = c->profile_skip;
     T.L = L; T.d_out = d_out;
     T.sink = c->frame_sink; T.sink_pitch = c->frame_sink_pitch;
     slot->sunk_valid = false;

@@ -196,6 +196,7 @@ enum km_slot {
     WS_AC_SCAN,     //   tile sums of that scan
     WS_AC_KEYS0,    //   order keys of the four columns
     WS_AC_KEYS1,    //   ... the sort's second buffer
+    WS_CL_COLS,     // k_clip.hip: the working columns dx | dy | row name | new label of every unit of a clip launch
     WS_COUNT
 };
 
@@ -357,6 +358,7 @@ struct km_ctx {
     bool opt_lk2 = true;           // "lk2" 1 (default): LK on four resident patches per key point (two-level pyramids); 0: the first form
     bool opt_mm_early = true;      // "mm_early" 0: min / max of a submitted unit on the main stream behind the previous unit's tail (round-2 order)
     bool opt_frame_mi = false;     // "frame_mi" 1: frames scored by the tile entry points (ZNCC of the rows with score >= threshold) also carry the two mutual-information scores of those rows (core.py:894-907): two more float64 columns behind zncc
+    bool opt_frame_clip = false;   // "frame_clip" 1: the entry points that produce a frame block apply the tracker's outlier clip (klt.py:52-71, k_clip.hip) between the frame stage and the scores; read when the call is made
     int opt_ransac_first_batch = 0;   // "ransac_first_batch": iterations of the first batch of km_find_homography_ransac* (0: chosen from n and the chip)
     bool opt_no_defer = false; // "defer" 0: the deferred pyramid jobs run after the read-back waits instead of under them
     // stage-timer events: set 0 serves the synchronous calls, sets 1..KM_FRAME_SLOTS the frames in flight of

@@ -5,9 +5,9 @@ forward-backward distance `d = max(|p0 - p0r|)` per point in float32, keep `d < 
 `score = 1 - d / 0.1`, `dx, dy = p1 - p0`, optionally an iterative sigma clip, the tile offset added to `x0, y0`, rows
 ordered by `(x0, y0)` with the labels pandas' in-place sort leaves behind (the row's position before the sort).
 
-On the fixed-parameter path all of this happens on the device (k_frame.hip) and only `block_to_frame` runs here; the
-functions below serve the host-buffer entry points (`klt_tracker`) and the sigma-clip variant, whose float32 means and
-standard deviations must be numpy's.
+On the fixed-parameter path all of this happens on the device (k_frame.hip; the sigma clip in k_clip.hip, with numpy's float32
+means and standard deviations bit for bit) and only `block_to_frame` runs here; the functions below serve the host-buffer entry
+points (`klt_tracker`), frames of more rows than the device clip holds, and the tests' comparison.
 """
 from __future__ import annotations
 

@@ -219,13 +219,16 @@ class KLT:
 
     # ------------------------------------------------------------------ rasters that already live in HBM
     def _rasters_in_hbm(self, mon_img, ref_img, mask) -> bool:
-        """Both rasters are `DeviceRasterImage`s of one pixel type the kernels read, the run uses fixed parameters and neither the
-        sigma clip nor the Laplacian dump: the tiles are boxes of ONE resident pair - nothing is read, copied or uploaded."""
+        """Both rasters are `DeviceRasterImage`s of one pixel type the kernels read, the run uses fixed parameters and no Laplacian
+        dump: the tiles are boxes of ONE resident pair - nothing is read, copied or uploaded.  The sigma clip runs on the device
+        too, on frames of at most 32768 rows (a bounded maxCorners)."""
         from ..core.image import DeviceRasterImage
+        from .._lib import CLIP_MAX_ROWS
         conf = self._conf
+        clip_fits = not getattr(conf, "outliers_filtering", False) or 0 < conf.maxCorners <= CLIP_MAX_ROWS
         return (isinstance(mon_img, DeviceRasterImage) and isinstance(ref_img, DeviceRasterImage) and (mask is None or isinstance(mask, DeviceRasterImage))
                 and mon_img.dtype == ref_img.dtype and mon_img.dtype.type in _DEVICE_DTYPES and conf.laplacian_kernel_size != "auto"
-                and conf.laplacian_invert_polarity != "auto" and not getattr(conf, "outliers_filtering", False) and not self._gen_laplacian
+                and conf.laplacian_invert_polarity != "auto" and clip_fits and not self._gen_laplacian
                 and mon_img.tensor.is_contiguous() and ref_img.tensor.is_contiguous() and (mask is None or mask.tensor.is_contiguous())
                 and mon_img.tensor.shape == ref_img.tensor.shape)
 

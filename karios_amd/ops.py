@@ -935,3 +935,107 @@ def accuracy_statistics(dx, dy, score, confidence, carto: bool = False, factor=1
         # the interpolation of accuracy_statistics.py:237 on the two float32 order statistics (the fraction is a Python float)
         ce.append(None if r is None else order[2 * k] + (order[2 * k + 1] - order[2 * k]) * r[2])
     return AccuracyStatistics(sample, 0, stats, tuple(ce), "device")
+
+
+# ---- the tracker's outlier clip (csrc/api_score.hip km_sigma_clip_dev, k_clip.hip) --------------------------------------------------
+CLIP_MAX_ROWS = _lib.CLIP_MAX_ROWS
+
+
+def _sigma_clip_host(dx, dy):
+    """`frames.sigma_clip` with the number of rounds: numpy's own expressions on host arrays of any dtype and length."""
+    dx, dy = np.asarray(dx), np.asarray(dy)
+    alive, rounds = np.arange(len(dx)), 0
+    with np.errstate(all="ignore"):
+        while len(alive):
+            u, v = dx[alive], dy[alive]
+            off_u, off_v = np.abs(u - u.mean()), np.abs(v - v.mean())
+            ok = (off_u < 3.0 * u.std()) & (off_v < 3.0 * v.std()) & (off_u < 20.0) & (off_v < 20.0)
+            rounds += 1
+            if ok.all():
+                break
+            alive = alive[ok]
+    return alive, rounds
+
+
+def sigma_clip_batch(units, ctx: Context | None = None):
+    """The reference's iterative 3-sigma / 20-px outlier clip (klt.py:52-71, `frames.sigma_clip`) for up to 16 independent
+    (dx, dy) column pairs in ONE device launch -> [(indices of the survivors in row order, rounds computed), ...].  Every pair is two
+    float32 numpy arrays (indices come back as an int64 array) or two contiguous float32 torch tensors on the context's device (an
+    int64 tensor on that device).  The means and standard deviations are numpy's float32 ones bit for bit, so the indices are
+    `frames.sigma_clip`'s.  numpy on the host takes a numpy pair the device form does not hold: another dtype, more than 32768 rows."""
+    units = [(dx, dy) for dx, dy in units]
+    if not 1 <= len(units) <= _lib.UNITS_PER_SUBMISSION:
+        raise ValueError(f"sigma_clip_batch: 1 .. {_lib.UNITS_PER_SUBMISSION} column pairs per call")
+    dev = _on_device(units[0][0])
+    if any(_on_device(a) != dev for pair in units for a in pair):
+        raise ValueError("sigma_clip_batch: all columns must be numpy arrays or all be device tensors")
+    k = len(units)
+    tab = lambda: (C.c_void_p * k)()
+    t_dx, t_dy, t_keep, ns = tab(), tab(), tab(), (C.c_int * k)()
+    res = np.zeros((k, 2), np.int32)
+    if dev:
+        import torch
+        for dx, dy in units:
+            if any(a.dtype != torch.float32 or a.dim() != 1 or not a.is_contiguous() for a in (dx, dy)) or dx.shape != dy.shape:
+                raise ValueError("sigma_clip_batch: expected two contiguous 1-D float32 tensors of equal length")
+            if dx.shape[0] > CLIP_MAX_ROWS:
+                raise KariosHipError(f"sigma_clip_batch: {dx.shape[0]} rows (the device form holds {CLIP_MAX_ROWS})")
+        device = units[0][0].device
+        keeps = [torch.empty(max(int(dx.shape[0]), 1), dtype=torch.int32, device=device) for dx, _ in units]
+        d_res = torch.zeros((k, 2), dtype=torch.int32, device=device)
+        for i, (dx, dy) in enumerate(units):
+            ns[i] = int(dx.shape[0])
+            t_dx[i], t_dy[i], t_keep[i] = dx.data_ptr(), dy.data_ptr(), keeps[i].data_ptr()
+        c = _ctx(ctx)
+        torch.cuda.synchronize(device)                       # the library runs on its own stream
+        c.check(c.lib.km_sigma_clip_dev(c.handle, t_dx, t_dy, ns, k, t_keep, C.c_void_p(d_res.data_ptr())), "km_sigma_clip_dev")
+        c.sync()
+        res = d_res.cpu().numpy()
+        return [(keeps[i][:int(res[i, 0])].to(torch.int64), int(res[i, 1])) for i in range(k)]
+    cols = [(np.asarray(dx), np.asarray(dy)) for dx, dy in units]
+    for dx, dy in cols:
+        if dx.ndim != 1 or dx.shape != dy.shape:
+            raise ValueError("sigma_clip_batch: expected two 1-D arrays of equal length")
+    on_host = [dx.dtype != np.float32 or dy.dtype != np.float32 or len(dx) > CLIP_MAX_ROWS for dx, dy in cols]
+    if all(on_host):
+        return [_sigma_clip_host(dx, dy) for dx, dy in cols]
+    if any(on_host):
+        out = iter(sigma_clip_batch([p for p, h in zip(cols, on_host) if not h], ctx))
+        return [_sigma_clip_host(*p) if h else next(out) for p, h in zip(cols, on_host)]
+    c = _ctx(ctx)
+    up = lambda n: (max(n, 1) * 4 + 255) & ~255
+    total = sum(3 * up(len(dx)) for dx, _ in cols) + 256
+    base, cap = c.dev_alloc(total)
+    try:
+        at = base
+        keep_at = []
+        for i, (dx, dy) in enumerate(cols):
+            n = len(dx)
+            ns[i] = n
+            for tbl, a in ((t_dx, dx), (t_dy, dy)):
+                tbl[i] = at
+                if n:
+                    a = np.ascontiguousarray(a)
+                    c.check(c.lib.km_h2d(c.handle, C.c_void_p(at), ptr(a), n * 4), "km_h2d")
+                at += up(n)
+            t_keep[i] = at
+            keep_at.append(at)
+            at += up(n)
+        c.check(c.lib.km_sigma_clip_dev(c.handle, t_dx, t_dy, ns, k, t_keep, C.c_void_p(at)), "km_sigma_clip_dev")
+        c.check(c.lib.km_d2h(c.handle, ptr(res), C.c_void_p(at), res.nbytes), "km_d2h")
+        out = []
+        for i in range(k):
+            keep = np.empty(int(res[i, 0]), np.int32)
+            if keep.size:
+                c.check(c.lib.km_d2h(c.handle, ptr(keep), C.c_void_p(keep_at[i]), keep.nbytes), "km_d2h")
+            out.append((keep.astype(np.int64), int(res[i, 1])))
+        return out
+    finally:
+        c.dev_release(base, cap)
+
+
+def sigma_clip(dx, dy, ctx: Context | None = None, return_rounds: bool = False):
+    """`frames.sigma_clip(dx, dy)` on the device: the indices of the displacements that survive the reference's outlier loop
+    (klt.py:52-71).  numpy in / numpy out, or device tensors in / a device tensor out; `return_rounds`: (indices, rounds)."""
+    keep, rounds = sigma_clip_batch([(dx, dy)], ctx)[0]
+    return (keep, rounds) if return_rounds else keep

@@ -476,7 +476,7 @@ def match_distributed(bands: dict, n_bands: int, x_size: int, y_size: int, conf,
     (rows with score >= confidence_threshold), `radial error` and `angle` like `_handle_klt_results` (core.py:872-893).
     Returns the frames in reference order on every rank."""
     import torch
-    from ._lib import default_context
+    from ._lib import CLIP_MAX_ROWS, default_context
     ws, rank = _world()
     ctx = ctx if ctx is not None else default_context()
     units = enumerate_units(n_bands, x_size, y_size, conf)
@@ -492,8 +492,9 @@ def match_distributed(bands: dict, n_bands: int, x_size: int, y_size: int, conf,
     for slot, u in enumerate(mine):
         src = bands[u.band]
         ru = ResidentUnit.load(u, src[0], src[1], src[2] if len(src) > 2 else None, halo=halo, ctx=ctx)
-        if on_gpu and not getattr(conf, "outliers_filtering", False):
-            # the device pipeline drops the unit's block straight into the send buffer (km_set_frame_sink)
+        if on_gpu and (not getattr(conf, "outliers_filtering", False) or cap <= CLIP_MAX_ROWS):
+            # the device pipeline drops the unit's block straight into the send buffer (km_set_frame_sink) - with the outlier filter
+            # on, the block the device clipped (frames of more than 32768 rows are clipped on the host: packed below)
             ctx.set_frame_sink(send[slot, 1:].data_ptr(), L * 4)
             try:
                 ru.match(conf, thr)

@@ -187,10 +187,11 @@ def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False) ->
     dense kernel, the corner-selection chain, LK, the frame stage and the scores are launched ONCE for all units
     (csrc/api_units.hip); the frames are the unit-by-unit frames bit for bit.  Returns None when the batch form does not cover the
     case (the library answers KM_E_UNSUPPORTED: maxCorners 0, a unit narrower than 512 columns ...) or the
-    units do not share a context / pixel type, or only some carry a user mask - submit them one by one then."""
+    units do not share a context / pixel type, or only some carry a user mask - submit them one by one then.  With
+    `conf.outliers_filtering` every unit's frame is clipped on the device (km_set_option "frame_clip") in front of its scores."""
     if not units or len(units) > _lib.UNITS_PER_SUBMISSION:
         return None
-    if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto" or getattr(conf, "outliers_filtering", False) or conf.maxCorners <= 0:
+    if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto" or conf.maxCorners <= 0:
         return None
     first = units[0][0]
     c = first.ctx
@@ -234,12 +235,17 @@ def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False) ->
     nr = C.byref(C.c_double(float(first.no_data_ref))) if first.no_data_ref is not None else None
     nm = C.byref(C.c_double(float(first.no_data_mon))) if first.no_data_mon is not None else None
     ticket = C.c_int(-1)
-    with first._frame_mi(n_scores == 3):
+    with first._frame_mi(n_scores == 3), first._frame_clip(_clips(conf)):
         rc = c.lib.km_klt_units_frame_submit(c.handle, arr, len(units), first.code, nr, nm, C.byref(prm), float(zncc_threshold or 0.0), cap, C.byref(ticket))
     if rc == _lib.E_UNSUPPORTED:
         return None
     c.check(rc, "km_klt_units_frame_submit")
     return PendingBatch(c, ticket.value, cap, n_scores, redos)
+
+
+def _clips(conf) -> bool:
+    """The configuration asks for the tracker's outlier clip (klt.py:52-71)."""
+    return bool(getattr(conf, "outliers_filtering", False))
 
 
 class ResidentPair:
@@ -425,24 +431,52 @@ class ResidentPair:
         if ksizes is None and conf.laplacian_kernel_size == "auto" or invert_mon is None and conf.laplacian_invert_polarity == "auto":
             raise KariosHipError("ResidentPair.match_tile: 'auto' modes are resolved by karios_amd.matcher.KLT")
         x_off, y_off = origin if origin is not None else ((box[0], box[1]) if box is not None else (0, 0))
-        if getattr(conf, "outliers_filtering", False):
-            # the iterative sigma clip (klt.py:52-71) needs numpy's float32 statistics: FB test and ordering on the host
-            mon_k, ref_k = ksizes if ksizes is not None else tiling.kernel_sizes(conf.laplacian_kernel_size)
-            invert = bool(conf.laplacian_invert_polarity) if invert_mon is None else bool(invert_mon)
-            status, tracks = self.track_tile(conf, box, mon_k, ref_k, invert)
-            if status != "ok":
-                return None
-            cols, n_init = frames.track_columns(*tracks)
-            points = frames.assemble(cols, x_off, y_off, clip_outliers=True)
-            points.attrs["Ninit"] = n_init
-            if zncc_threshold is not None:
-                keep = points["score"].to_numpy() >= zncc_threshold
-                z = np.full(len(points), np.nan)
-                if keep.any():
-                    z[keep] = self.zncc(*(points[c].to_numpy()[keep] for c in ("x0", "y0", "dx", "dy")))
-                points["zncc_score"] = z
-            return points
+        if _clips(conf) and self._frame_capacity(conf, box) > _lib.CLIP_MAX_ROWS:
+            # more rows than the device clip holds (maxCorners 0 on a large tile): FB test, clip and ordering on the host
+            return self._match_tile_host_clip(conf, box, x_off, y_off, zncc_threshold, ksizes, invert_mon)
         return self._match_tile_device_frame(conf, box, x_off, y_off, zncc_threshold, ksizes=ksizes, invert_mon=invert_mon, mutual_info=mutual_info)
+
+    def _frame_capacity(self, conf, box) -> int:
+        """Rows the frame block of a tile holds: maxCorners, or a quarter of the box's pixels without a limit."""
+        bx, by = (box[2], box[3]) if box is not None else (self.x_size, self.y_size)
+        return conf.maxCorners if conf.maxCorners > 0 else max(1, (bx * by) // 4)
+
+    def _match_tile_host_clip(self, conf, box, x_off, y_off, zncc_threshold=None, ksizes=None, invert_mon=None) -> DataFrame | None:
+        """`match_tile` with the outlier filter on the host: the tracks come back as three point lists, FB test, `frames.sigma_clip`
+        (numpy) and the ordering run here, a second device call scores the survivors.  The path of a frame of more than 32768 rows,
+        and the tests' second opinion on the device clip."""
+        mon_k, ref_k = ksizes if ksizes is not None else tiling.kernel_sizes(conf.laplacian_kernel_size)
+        invert = bool(conf.laplacian_invert_polarity) if invert_mon is None else bool(invert_mon)
+        status, tracks = self.track_tile(conf, box, mon_k, ref_k, invert)
+        if status != "ok":
+            return None
+        cols, n_init = frames.track_columns(*tracks)
+        points = frames.assemble(cols, x_off, y_off, clip_outliers=True)
+        points.attrs["Ninit"] = n_init
+        if zncc_threshold is not None:
+            keep = points["score"].to_numpy() >= zncc_threshold
+            z = np.full(len(points), np.nan)
+            if keep.any():
+                z[keep] = self.zncc(*(points[c].to_numpy()[keep] for c in ("x0", "y0", "dx", "dy")))
+            points["zncc_score"] = z
+        return points
+
+    def _frame_clip(self, on: bool):
+        """Context manager: frames produced inside are clipped by the tracker's outlier filter on the device, in front of their
+        scores (km_set_option "frame_clip").  The library reads the value when the call is made, so a pipelined submission keeps it."""
+        from contextlib import contextmanager
+
+        @contextmanager
+        def scope():
+            if not on:
+                yield
+                return
+            self.ctx.set_option("frame_clip", 1)
+            try:
+                yield
+            finally:
+                self.ctx.set_option("frame_clip", 0)
+        return scope()
 
     def _frame_mi(self, on: bool):
         """Context manager: frames scored inside also carry `mutual_info_score` / `mi_score` (km_set_option "frame_mi")."""
@@ -462,8 +496,8 @@ class ResidentPair:
 
     def _match_tile_device_frame(self, conf, box, x_off, y_off, zncc_threshold=None, build_frame=True, ksizes=None,
                                  invert_mon=None, mutual_info: bool = False) -> DataFrame | None:
-        """Tile pipeline + FB test + score + (x0, y0) ordering (+ ZNCC [+ MI / NMI] of the confident rows) on the device, one D2H
-        copy of the finished frame."""
+        """Tile pipeline + FB test + score + (x0, y0) ordering (+ the outlier clip of `conf.outliers_filtering`) (+ ZNCC [+ MI / NMI] of
+        the confident rows) on the device, one D2H copy of the finished frame."""
         c = self.ctx
         n_scores = 0 if zncc_threshold is None else (3 if mutual_info else 1)
         _, _, bx, by, off = self._box(box)
@@ -474,11 +508,12 @@ class ResidentPair:
         buf = self._host_frame
         ref, mon, mask, nr, nm = self._image_args(off)
         if zncc_threshold is None:
-            c.check(c.lib.km_klt_tile_frame_dev(c.handle, ref, mon, self.code, by, bx, self.x_size, self.x_size, mask, self.x_size, nr, nm,
-                                                C.byref(prm), float(x_off), float(y_off), buf.ctypes.data_as(C.c_void_p), cap),
-                    "km_klt_tile_frame_dev")
+            with self._frame_clip(_clips(conf)):
+                c.check(c.lib.km_klt_tile_frame_dev(c.handle, ref, mon, self.code, by, bx, self.x_size, self.x_size, mask, self.x_size, nr, nm,
+                                                    C.byref(prm), float(x_off), float(y_off), buf.ctypes.data_as(C.c_void_p), cap),
+                        "km_klt_tile_frame_dev")
         else:
-            with self._windowed(), self._frame_mi(n_scores == 3):
+            with self._windowed(), self._frame_mi(n_scores == 3), self._frame_clip(_clips(conf)):
                 c.check(c.lib.km_klt_tile_frame_zncc_dev(c.handle, ref, mon, self.code, by, bx, self.x_size, self.x_size, mask, self.x_size, nr, nm,
                                                          C.byref(prm), float(x_off), float(y_off), C.c_void_p(self.ref_ptr),
                                                          C.c_void_p(self.mon_ptr), self.y_size, self.x_size, self.x_size, self.x_size,
@@ -522,9 +557,12 @@ class ResidentPair:
     def match_tile_raw(self, conf, box=None, zncc_threshold=None, origin=None, mutual_info: bool = False) -> "RawFrame":
         """GPU half of `match_tile`: runs the device pipeline and returns the raw frame block (a private copy), leaving
         the pandas half to `RawFrame.to_frame()` - which may run in another thread while this thread already drives the
-        next tile (ctypes releases the GIL inside the library).  Fixed kernel size / polarity, no outlier filtering."""
-        if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto" or getattr(conf, "outliers_filtering", False):
-            raise KariosHipError("ResidentPair.match_tile_raw: 'auto' modes and outlier filtering need ResidentPair.match_tile / matcher.KLT")
+        next tile (ctypes releases the GIL inside the library).  Fixed kernel size / polarity; the outlier filter on the device, for
+        frames of at most 32768 rows."""
+        if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto":
+            raise KariosHipError("ResidentPair.match_tile_raw: 'auto' modes need ResidentPair.match_tile / matcher.KLT")
+        if _clips(conf) and self._frame_capacity(conf, box) > _lib.CLIP_MAX_ROWS:
+            raise KariosHipError("ResidentPair.match_tile_raw: outlier filtering of more than 32768 rows needs ResidentPair.match_tile")
         x_off, y_off = origin if origin is not None else ((box[0], box[1]) if box is not None else (0, 0))
         with_zncc = 0 if zncc_threshold is None else (3 if mutual_info else 1)
         # host blocks rotate through a ring of three: the previous block may still be read by the host half of the pipeline
@@ -542,8 +580,10 @@ class ResidentPair:
         """Asynchronous `match_tile_raw` (km_klt_tile_frame_submit): returns when the tile's last kernel and the copy of
         its frame block are enqueued, so the next `submit_tile` queues its dense stages right behind them - no GPU idle
         time between tiles.  Up to three tiles may be pending; `PendingFrame.wait()` may run in another thread."""
-        if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto" or getattr(conf, "outliers_filtering", False):
-            raise KariosHipError("ResidentPair.submit_tile: 'auto' modes and outlier filtering need ResidentPair.match_tile / matcher.KLT")
+        if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto":
+            raise KariosHipError("ResidentPair.submit_tile: 'auto' modes need ResidentPair.match_tile / matcher.KLT")
+        if _clips(conf) and self._frame_capacity(conf, box) > _lib.CLIP_MAX_ROWS:
+            raise KariosHipError("ResidentPair.submit_tile: outlier filtering of more than 32768 rows needs ResidentPair.match_tile")
         c = self.ctx
         bx_off, by_off, bx, by, off = self._box(box)
         prm = self._params(conf)
@@ -553,7 +593,7 @@ class ResidentPair:
         n_scores = 0 if not with_zncc else (3 if mutual_info else 1)
         ticket = C.c_int(-1)
         x_off, y_off = origin if origin is not None else (bx_off, by_off)
-        with self._windowed(), self._frame_mi(n_scores == 3):
+        with self._windowed(), self._frame_mi(n_scores == 3), self._frame_clip(_clips(conf)):
             c.check(c.lib.km_klt_tile_frame_submit(c.handle, ref, mon, self.code, by, bx, self.x_size, self.x_size, mask, self.x_size, nr, nm,
                                                    C.byref(prm), float(x_off), float(y_off),
                                                    C.c_void_p(self.ref_ptr) if with_zncc else None, C.c_void_p(self.mon_ptr) if with_zncc else None,
