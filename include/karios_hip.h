@@ -668,6 +668,46 @@ typedef struct km_clip_result {
 int km_sigma_clip_dev(km_ctx *ctx, const float *const *d_dx, const float *const *d_dy, const int *n, int n_units, int32_t *const *d_keep_index,
                       km_clip_result *d_result);
 
+/* ---- ChipService.generate_chips (karios/report/chip_service.py) on resident data ------------------------------------------------
+ * The arithmetic is restated in tests/chips_restatement.py (the definition the library is held to, bit for bit).
+ *
+ * CenterAndQuarterCellPointSelector.select_points (:46-306) for the float32 columns x0, y0, score of n rows (n <= 2^24, finite
+ * coordinates) on a width x height image under a grid of grid_rows x grid_cols cells (1 .. KM_CHIP_MAX_GRID each).  Rows pass with
+ * (double)score >= thr, where thr is `threshold` itself (threshold_f64 != 0: an np.float64 threshold compares in float64) or
+ * (double)(float)threshold (a Python float compares in float32).  cell = clip(floor(x0 / (float)(width / cols))) ...; per cell,
+ * in cell order: the row nearest to the cell's centre, then for each quarter 0 .. 3 the row (the centre row apart) whose distance
+ * is nearest to the quarter's median distance; ties go to the larger score, then to the first row.  Every float32 operation is a
+ * rounding of its own.  out_index receives at most KM_CHIP_PICKS * grid_rows * grid_cols row indices in the reference's output
+ * order (empty cells and quarters left out), *out_count their number.  Both forms write *out_count to host memory; the device form
+ * reads the columns from the device and writes out_index there. */
+#define KM_CHIP_SIZE 57
+#define KM_CHIP_MAX_GRID 16
+#define KM_CHIP_PICKS 5
+int km_chip_select(km_ctx *ctx, const float *x0, const float *y0, const float *score, int n, int width, int height, double threshold,
+                   int threshold_f64, int grid_rows, int grid_cols, int32_t *out_index, int32_t *out_count);
+int km_chip_select_dev(km_ctx *ctx, const float *d_x0, const float *d_y0, const float *d_score, int n, int width, int height, double threshold,
+                       int threshold_f64, int grid_rows, int grid_cols, int32_t *d_out_index, int32_t *out_count);
+/* _to_chips_gdal_dataset (:544-648) for n rows (0 .. 2^20) of float32 columns x0, y0, dx, dy on two rasters of one pixel type (KM_U8,
+ * KM_U16, KM_I16, KM_F32), each at least 57 x 57 with its own shape and row stride in elements.  Window centres: ref (int)x0,
+ * (int)y0; mon round(x0 + dx), round(y0 + dy) - the float64 sum, half to even.  ok[i] is 0 when either 57 x 57 window leaves its
+ * raster, or a centre is not finite or beyond 2^30 (reported as 0).  Per row i, at [i][57][57]: the raw chips in the rasters' type,
+ * their uint8 stretch by the chip's own minimum and maximum (_to_uint8: NaN ignored for the range and mapped to 0, a flat or
+ * all-NaN chip gives zeros) and, for ksize != 0 (1, 3, 5, 7, 9 or 11; ref_lap / mon_lap may be NULL for 0), cv2.Laplacian(u8,
+ * CV_8U, ksize) with the border reflected at the chip's own edge.  windows[i] = {X0, Y0, X1, Y1}.  A row with ok == 0 has zeros in
+ * every image.  The host form takes and fills host memory; the device form device memory, asynchronously on the context stream. */
+typedef struct km_chip_outputs {
+    void *ref_raw, *mon_raw;                   /* n x 57 x 57 of the rasters' type */
+    uint8_t *ref_u8, *mon_u8;                  /* n x 57 x 57 */
+    uint8_t *ref_lap, *mon_lap;                /* n x 57 x 57, NULL with ksize 0 */
+    uint8_t *ok;                               /* n */
+    int32_t *windows;                          /* n x 4 */
+} km_chip_outputs;
+int km_chips(km_ctx *ctx, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref, ptrdiff_t smon,
+             const float *x0, const float *y0, const float *dx, const float *dy, int n, int ksize_ref, int ksize_mon, const km_chip_outputs *out);
+int km_chips_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref,
+                 ptrdiff_t smon, const float *d_x0, const float *d_y0, const float *d_dx, const float *d_dy, int n, int ksize_ref, int ksize_mon,
+                 const km_chip_outputs *d_out);
+
 #ifdef __cplusplus
 }
 #endif

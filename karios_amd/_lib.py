@@ -67,6 +67,14 @@ class ClipResult(C.Structure):
     _fields_ = [("count", C.c_int32), ("rounds", C.c_int32)]
 
 
+class ChipOutputs(C.Structure):
+    """km_chip_outputs of include/karios_hip.h."""
+    _fields_ = [("ref_raw", C.c_void_p), ("mon_raw", C.c_void_p), ("ref_u8", C.c_void_p), ("mon_u8", C.c_void_p), ("ref_lap", C.c_void_p),
+                ("mon_lap", C.c_void_p), ("ok", C.c_void_p), ("windows", C.c_void_p)]
+
+
+CHIP_SIZE, CHIP_MAX_GRID, CHIP_PICKS = 57, 16, 5      # KM_CHIP_SIZE, KM_CHIP_MAX_GRID, KM_CHIP_PICKS
+CHIP_SELECT_MAX_ROWS, CHIP_MAX_ROWS = 1 << 24, 1 << 20
 CLIP_MAX_ROWS = 32768          # rows one unit of km_sigma_clip_dev / the "frame_clip" stage holds
 UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
 E_ARG = -1                     # KM_E_ARG
@@ -182,6 +190,10 @@ SIGNATURES = {
     "km_accuracy_stats": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _d, _i, _pd, C.POINTER(AccuracyResult)]),
     "km_accuracy_stats_dev": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _d, _i, _pd, C.POINTER(AccuracyResult)]),
     "km_sigma_clip_dev": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _pi, _i, C.POINTER(_vp), _vp]),
+    "km_chip_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _vp, C.POINTER(C.c_int32)]),
+    "km_chip_select_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _vp, C.POINTER(C.c_int32)]),
+    "km_chips": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(ChipOutputs)]),
+    "km_chips_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(ChipOutputs)]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
-// Device-side pixel helpers shared by the dense kernel files that came out of one (k_raster.hip, k_lap.hip): pixel-type traits,
-// wave reductions, the exact uint8 stretch and the valid-pixel rule of the automatic mask.  Device inline code only; included by
-// those files and nothing else.
+// Device-side pixel helpers shared by the dense kernel files that came out of one (k_raster.hip, k_lap.hip) and by the key-point chips
+// (k_chips.hip): pixel-type traits, wave reductions, the exact uint8 stretch and the valid-pixel rule of the automatic mask.  Device
+// inline code only; included by those files and nothing else.
 #pragma once
 #include "common.hpp"
 

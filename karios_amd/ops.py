@@ -937,6 +937,144 @@ def accuracy_statistics(dx, dy, score, confidence, carto: bool = False, factor=1
     return AccuracyStatistics(sample, 0, stats, tuple(ce), "device")
 
 
+# ---- ChipService.generate_chips (csrc/api_score.hip km_chip_select / km_chips, k_chips.hip) ----------------------------------------
+CHIP_SIZE = _lib.CHIP_SIZE
+CHIP_KSIZES = (1, 3, 5, 7, 9, 11)
+
+
+def _torch_np_dtype(t):
+    return np.dtype(str(t.dtype).replace("torch.", ""))
+
+
+def _f32_columns(cols, what, names):
+    """The columns of one call, all numpy or all device tensors -> (on device, columns as the library reads them, rows)."""
+    dev = _on_device(cols[0])
+    if any(_on_device(a) != dev for a in cols):
+        raise ValueError(f"{what}: {names} must all be numpy arrays or all be device tensors")
+    if dev:
+        import torch
+        if any(a.dtype != torch.float32 or a.dim() != 1 or not a.is_contiguous() for a in cols):
+            raise ValueError(f"{what}: {names} must be contiguous 1-D float32 tensors")
+    else:
+        cols = tuple(np.asarray(a) for a in cols)
+        if any(a.dtype != np.float32 or a.ndim != 1 for a in cols):
+            raise ValueError(f"{what}: {names} must be 1-D float32 arrays")
+        cols = tuple(np.ascontiguousarray(a) for a in cols)
+    n = int(cols[0].shape[0])
+    if any(int(a.shape[0]) != n for a in cols):
+        raise ValueError(f"{what}: {names} differ in length")
+    return dev, cols, n
+
+
+def _col_args(dev, cols, n):
+    if not n:
+        return [None] * len(cols)
+    return [C.c_void_p(a.data_ptr()) for a in cols] if dev else [ptr(a) for a in cols]
+
+
+def select_chip_points(x0, y0, score, width, height, threshold, grid=(5, 5), ctx: Context | None = None):
+    """CenterAndQuarterCellPointSelector.select_points (report/chip_service.py:46-306) on the rows with score >= threshold, for
+    float32 columns: the row indices (int32) in the reference's output order - per cell of the `grid` (rows, cols) over a
+    width x height image the row nearest to the centre, then one row per quarter.  A Python-float threshold compares in float32
+    like the reference's frame does, an np.float64 in float64.  numpy columns give a numpy array, device tensors a device tensor."""
+    dev, cols, n = _f32_columns((x0, y0, score), "select_chip_points", "x0, y0 and score")
+    rows, ncols = (int(v) for v in grid)
+    if not (1 <= rows <= _lib.CHIP_MAX_GRID and 1 <= ncols <= _lib.CHIP_MAX_GRID):
+        raise ValueError(f"select_chip_points: grid {grid} (1 .. {_lib.CHIP_MAX_GRID} cells per axis)")
+    if n > _lib.CHIP_SELECT_MAX_ROWS:
+        raise ValueError(f"select_chip_points: {n} rows (at most 2^24)")
+    c = _ctx(ctx)
+    cap = rows * ncols * _lib.CHIP_PICKS
+    count = C.c_int32()
+    tail = (n, int(width), int(height), float(threshold), int(isinstance(threshold, np.float64)), rows, ncols)
+    if dev:
+        import torch
+        torch.cuda.synchronize(cols[0].device)
+        out = torch.empty(cap, dtype=torch.int32, device=cols[0].device)
+        c.check(c.lib.km_chip_select_dev(c.handle, *_col_args(dev, cols, n), *tail, C.c_void_p(out.data_ptr()), C.byref(count)), "km_chip_select_dev")
+    else:
+        out = np.empty(cap, np.int32)
+        c.check(c.lib.km_chip_select(c.handle, *_col_args(dev, cols, n), *tail, ptr(out), C.byref(count)), "km_chip_select")
+    return out[:count.value]
+
+
+class ChipImages:
+    """Result of `extract_chips` for n rows: `ok` (n, bool), `windows` (n, 4: X0, Y0 of ref and X1, Y1 of mon, the chip centres),
+    `ref_raw` / `mon_raw` (n, 57, 57 in the rasters' type), `ref_u8` / `mon_u8`, `ref_lap` / `mon_lap` (uint8; None without a
+    kernel size).  Rows that are not ok are zero in every image."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def chip_ksize(k):
+    """Kernel size argument of the library: None -> 0 (no Laplacian), else one of CHIP_KSIZES."""
+    if k is None:
+        return 0
+    if int(k) != k or int(k) not in CHIP_KSIZES:
+        raise ValueError(f"Laplacian kernel size {k} (one of {CHIP_KSIZES} or None)")
+    return int(k)
+
+
+def extract_chips(ref, mon, x0, y0, dx, dy, ksize_ref=None, ksize_mon=None, ctx: Context | None = None) -> ChipImages:
+    """The chips of `_to_chips_gdal_dataset` (report/chip_service.py:544-648) for the rows x0, y0, dx, dy (float32): the 57 x 57
+    windows of `ref` around (int(x0), int(y0)) and of `mon` around (round(x0 + dx), round(y0 + dy)), their uint8 stretch by each
+    chip's own minimum and maximum and, with a kernel size, cv2.Laplacian(u8, CV_8U, ksize) of each chip.  Rasters: 2-D uint8 /
+    uint16 / int16 / float32 of one type, each at least 57 x 57 (windows of wider buffers are fine); numpy in gives numpy out,
+    device tensors in give device tensors out."""
+    kr, km = chip_ksize(ksize_ref), chip_ksize(ksize_mon)
+    dev, cols, n = _f32_columns((x0, y0, dx, dy), "extract_chips", "x0, y0, dx and dy")
+    if dev != _on_device(ref) or dev != _on_device(mon):
+        raise ValueError("extract_chips: rasters and columns must all be numpy arrays or all be device tensors")
+    if n > _lib.CHIP_MAX_ROWS:
+        raise ValueError(f"extract_chips: {n} rows (at most 2^20)")
+    if dev:
+        import torch
+        if any(a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1) for a in (ref, mon)):
+            raise ValueError("extract_chips: expected 2-D tensors with contiguous rows")
+        dt, dt_m = _torch_np_dtype(ref), _torch_np_dtype(mon)
+        shapes = [(int(a.shape[0]), int(a.shape[1])) for a in (ref, mon)]
+        strides = [int(a.stride(0)) if a.shape[0] > 1 else int(a.shape[1]) for a in (ref, mon)]
+        img_args = [C.c_void_p(ref.data_ptr()), C.c_void_p(mon.data_ptr())]
+
+        def empty(shape, dtype):
+            return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=ref.device)
+
+        def address(a):
+            return a.data_ptr()
+    else:
+        ref, mon = as_image(ref), as_image(mon)
+        dt, dt_m = ref.dtype, mon.dtype
+        shapes = [ref.shape, mon.shape]
+        strides = [row_stride(ref), row_stride(mon)]
+        img_args = [ptr(ref), ptr(mon)]
+        empty = np.empty
+
+        def address(a):
+            return a.ctypes.data
+    if dt != dt_m or dt not in PREP_DTYPES:
+        raise KariosHipError(f"extract_chips: rasters of {dt} and {dt_m} (one of uint8, uint16, int16, float32 for both)")
+    if min(shapes[0] + shapes[1]) < CHIP_SIZE:
+        raise ValueError(f"extract_chips: rasters of {shapes[0]} and {shapes[1]} (at least {CHIP_SIZE} x {CHIP_SIZE})")
+    shape = (n, CHIP_SIZE, CHIP_SIZE)
+    res = ChipImages(ok=empty((n,), np.uint8), windows=empty((n, 4), np.int32), ref_raw=empty(shape, dt), mon_raw=empty(shape, dt),
+                     ref_u8=empty(shape, np.uint8), mon_u8=empty(shape, np.uint8), ref_lap=empty(shape, np.uint8) if kr else None,
+                     mon_lap=empty(shape, np.uint8) if km else None)
+    if n:
+        c = _ctx(ctx)
+        if dev:
+            torch.cuda.synchronize(ref.device)
+        out = _lib.ChipOutputs(*(address(getattr(res, k)) if getattr(res, k) is not None else None
+                                 for k in ("ref_raw", "mon_raw", "ref_u8", "mon_u8", "ref_lap", "mon_lap", "ok", "windows")))
+        what = "km_chips_dev" if dev else "km_chips"
+        c.check(getattr(c.lib, what)(c.handle, *img_args, _lib._DTYPES[dt], shapes[0][0], shapes[0][1], shapes[1][0], shapes[1][1], strides[0], strides[1],
+                                     *_col_args(dev, cols, n), n, kr, km, C.byref(out)), what)
+        if dev:
+            c.sync()
+    res.ok = res.ok != 0
+    return res
+
+
 # ---- the tracker's outlier clip (csrc/api_score.hip km_sigma_clip_dev, k_clip.hip) --------------------------------------------------
 CLIP_MAX_ROWS = _lib.CLIP_MAX_ROWS
 

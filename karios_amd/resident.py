@@ -737,6 +737,15 @@ class ResidentPair:
             frame["mi_score"] = nmi
         return frame
 
+    # ------------------------------------------------------------------ key-point chips
+    def chips(self, points, confidence_threshold: float = 0.4, laplacian_ksize=None):
+        """`ChipService.generate_chips` on the resident rasters (report/chip_service.py:397-493): the key points with
+        score >= confidence_threshold, per cell of a 5 x 5 grid the centre point and one per quarter, and their 57 x 57 chips of
+        both images - raw, stretched to uint8 and, with `laplacian_ksize` (an int or {"mon": k, "ref": k}), their Laplacian.
+        `points`: a DataFrame or a mapping of float32 device columns.  -> `karios_amd.report.Chips`, None when no row passes."""
+        from .report.chip_service import pair_chips
+        return pair_chips(self, points, confidence_threshold, laplacian_ksize)
+
     # ------------------------------------------------------------------ large offset
     def phase_offset(self) -> np.ndarray:
         """LargeOffsetMatcher.match() on resident data (large_offset.py:39): [row, col]."""
