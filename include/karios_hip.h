@@ -104,6 +104,8 @@ int km_set_profiling(km_ctx *ctx, int enable);
  *                  2-pixels-per-lane kernel (k_eig2.hip).  Initial value from KARIOS_HIP_EIG3
  *   "lk2"          1 (default): LK on four resident patches per key point (two-level pyramids); 0: the first form (one patch per
  *                  direction and level), which also serves deeper pyramids and row bands
+ *   "lk_reuse"     1 (default): an LK iteration of the "lk2" form reads the search patch (LDS) and cuts its byte pairs again only when
+ *                  the window's integer position moved since the previous iteration; 0: every iteration does (same integers either way)
  *   "speculative"  1 (default): the tile entry points detect corners without a host synchronisation and without sorts (fixed
  *                  capacities, k_select2.hip); a tile that does not fit is flagged (frame header word 2) and repeated through the exact
  *                  path - inside the call for the blocking entry points, by the caller of km_frame_wait for submitted frames

@@ -162,6 +162,7 @@ int km_set_option(km_ctx *c, const char *name, int value)
     if (strcmp(name, "fused_eig") == 0) { c->fused_eig = value != 0; return KM_OK; }
     if (strcmp(name, "eig3") == 0) { c->opt_eig3 = value != 0; return KM_OK; }
     if (strcmp(name, "lk2") == 0) { c->opt_lk2 = value != 0; return KM_OK; }
+    if (strcmp(name, "lk_reuse") == 0) { c->opt_lk_reuse = value != 0; return KM_OK; }
     if (strcmp(name, "speculative") == 0) { c->opt_speculative = value != 0; return KM_OK; }
     if (strcmp(name, "aux_pyramid") == 0) { c->opt_aux_pyramid = value != 0; return KM_OK; }
     if (strcmp(name, "mm_early") == 0) { c->opt_mm_early = value != 0; return KM_OK; }

@@ -356,6 +356,7 @@ struct km_ctx {
     bool opt_fft61 = true;         // "fft61" 1 (default): rows of length 61 M through the wave-local form (k_fft.hip, second form); 0: the Stockham kernel
     bool opt_phase_fp64 = false;   // "phase_fp64" 1: phase correlation always in double precision, k_fft64.hip (the reference's precision)
     bool opt_lk2 = true;           // "lk2" 1 (default): LK on four resident patches per key point (two-level pyramids); 0: the first form
+    bool opt_lk_reuse = true;      // "lk_reuse" 1 (default): the lk2 form reads a run's search-patch bytes again only when the integer position moved; 0: every iteration
     bool opt_mm_early = true;      // "mm_early" 0: min / max of a submitted unit on the main stream behind the previous unit's tail (round-2 order)
     bool opt_frame_mi = false;     // "frame_mi" 1: frames scored by the tile entry points (ZNCC of the rows with score >= threshold) also carry the two mutual-information scores of those rows (core.py:894-907): two more float64 columns behind zncc
     bool opt_frame_clip = false;   // "frame_clip" 1: the entry points that produce a frame block apply the tracker's outlier clip (klt.py:52-71, k_clip.hip) between the frame stage and the scores; read when the call is made

@@ -30,6 +30,7 @@ struct lk_args {
     const int *d_n;
     int n_max, win, max_count, backward;
     int general_templates;   // (development build, KARIOS_HIP_LK_GENERAL: every template through the general two-row form - A/B of the degenerate-weight forms)
+    int lk_reuse;            // "lk_reuse" option: 1 = the second form keeps a run's byte pairs while the integer position stands, 0 = cuts them every iteration
     double epsilon;
     float *p1, *p0r;
     int *left_band;   // row-band mode: raised when a point's window needs rows outside the resident band
@@ -413,7 +414,9 @@ __global__ __launch_bounds__(64 * LK_WPB) KM_LK_OCC void lk_kernel(lk_args g, in
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = blockIdx.x * LK_WPB + wv;
-    const int n = g.d_n ? min(*g.d_n, g.n_max) : g.n_max;
+    // (what a wave reads through a pointer that itself came from the unit table arrives in vector registers: the corner count and the key
+    // point are the same in every lane, and saying so keeps the per-level geometry and every test on it in scalar registers)
+    const int n = __builtin_amdgcn_readfirstlane(g.d_n ? min(*g.d_n, g.n_max) : g.n_max);
     if (p >= n) return;                                  // (no workgroup barrier anywhere: waves are independent)
     unsigned char *smem = smem_all + (size_t)wv * sm_per_wave;
     const int win = g.win;
@@ -493,9 +496,10 @@ __device__ __forceinline__ int lk_dot2_k(lk_s2 a, lk_s2 b, int k)
 
 template <int NR, int WIN, int MAXIT>
 __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, uint8_t *pJ, int (&oI)[2][2], int (&oJ)[2][2], float px, float py,
-                                const lk2_geo<WIN> &geo, int max_count, double epsilon, const int (&run_desc)[NR], float &outx, float &outy, int general_templates)
+                                const lk2_geo<WIN> &geo, int max_count, double epsilon, const int (&run_desc)[NR], float &outx, float &outy, int general_templates, int lk_reuse)
 {
     const int win = geo.win;
+    const int always_cut = lk_reuse ? 0 : 1;   // ("lk_reuse" 0: every iteration cuts its byte pairs out of LDS again)
     const float half = (float)(win - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
     const int PP = geo.pp(), PB = geo.bytes();
@@ -666,6 +670,12 @@ __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, u
         nx -= half; ny -= half;
         float pdx = 0.f, pdy = 0.f;
         int jx0 = oJ[level][0], jy0 = oJ[level][1];
+        // The search patch's bytes under the window depend on the INTEGER position (inx, iny) and the patch origin only, and from the
+        // second iteration on a step is a fraction of a pixel: the vertical byte pairs of every run stay in registers (KV) and are cut
+        // out of LDS again only when the integer position moved (always on a pass's first iteration; a restage implies a move).  The
+        // position is the same in every lane, so the test is a scalar branch.  The integers are the same either way.
+        uint32_t KV[NR][LK_RUN + 1];
+        int kinx = LK2_INVALID, kiny = LK2_INVALID;
         for (int j = 0; j < max_count; j++) {
             const int inx = (int)floorf(nx), iny = (int)floorf(ny);
             if (inx < -win || inx >= JW || iny < -win || iny >= JH) break;
@@ -675,31 +685,38 @@ __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, u
                 jx0 = inx - LK2_M; jy0 = iny - LK2_M;
                 lk2_restage<MAXIT>(J.img[level], JW, JH, jx0, jy0, geo, Y);
                 LK_WAVE_SYNC();
+                kinx = LK2_INVALID;
             }
             a = nx - (float)inx; b = ny - (float)iny;
             lk_weights(a, b, w00, w01, w10, w11);
             const lk_s2 wc0 = lk_as_s2(lk_pack16(w00, w10)), wc1 = lk_as_s2(lk_pack16(w01, w11));   // (column k, column k + 1); signed: w11 may be -1
-            const uint8_t *jb = Y + (iny - jy0) * PP + (inx - jx0);
+            const int sinx = __builtin_amdgcn_readfirstlane(inx), siny = __builtin_amdgcn_readfirstlane(iny);
+            if (((sinx ^ kinx) | (siny ^ kiny) | always_cut) != 0) {
+                kinx = sinx; kiny = siny;
+                const uint8_t *jb = Y + (iny - jy0) * PP + (inx - jx0);
+#pragma unroll
+                for (int t = 0; t < NR; t++) {
+                    const int y = run_desc[t] & 0xff, x0 = (run_desc[t] >> 8) & 0xff;
+                    const uint8_t *p0 = jb + y * PP + x0;
+                    const unsigned jsh = lk_lds_shift(p0);
+                    const uint2 r0 = lk_lds_read8(p0, jsh), r1 = lk_lds_read8(p0 + PP, jsh);   // bytes x0 .. x0+7 of the two patch rows
+                    // VERTICAL byte pairs (row y, row y + 1) of columns 0 .. 5: six v_perm serve the five interpolated values (the horizontal
+                    // pairs (k, k + 1) of either row took ten); the integer sum w00 p(k) + w10 q(k) + w01 p(k+1) + w11 q(k+1) is the same
+#pragma unroll
+                    for (int k = 0; k <= LK_RUN; k++) {
+                        const uint32_t sel = 0x0c000c00u | (uint32_t)(k & 3) | ((uint32_t)(4 + (k & 3)) << 16);
+                        KV[t][k] = k < 4 ? __builtin_amdgcn_perm(r1.x, r0.x, sel) : __builtin_amdgcn_perm(r1.y, r0.y, sel);
+                    }
+                }
+            }
             int sb1 = -cI1, sb2 = -cI2;
 #pragma unroll
             for (int t = 0; t < NR; t++) {
-                const int y = run_desc[t] & 0xff, x0 = (run_desc[t] >> 8) & 0xff;
-                const uint8_t *p0 = jb + y * PP + x0;
-                const unsigned jsh = lk_lds_shift(p0);
-                const uint2 r0 = lk_lds_read8(p0, jsh), r1 = lk_lds_read8(p0 + PP, jsh);   // bytes x0 .. x0+7 of the two patch rows
                 int val[LK_RUN + 1];
                 val[LK_RUN] = 0;
-                // VERTICAL byte pairs (row y, row y + 1) of columns 0 .. 5: six v_perm serve the five interpolated values (the horizontal
-                // pairs (k, k + 1) of either row took ten); the integer sum w00 p(k) + w10 q(k) + w01 p(k+1) + w11 q(k+1) is the same
-                lk_s2 V[LK_RUN + 1];
-#pragma unroll
-                for (int k = 0; k <= LK_RUN; k++) {
-                    const uint32_t sel = 0x0c000c00u | (uint32_t)(k & 3) | ((uint32_t)(4 + (k & 3)) << 16);
-                    V[k] = lk_as_s2(k < 4 ? __builtin_amdgcn_perm(r1.x, r0.x, sel) : __builtin_amdgcn_perm(r1.y, r0.y, sel));
-                }
 #pragma unroll
                 for (int k = 0; k < LK_RUN; k++)
-                    val[k] = __builtin_amdgcn_sdot2(V[k], wc0, lk_dot2_k(V[k + 1], wc1, k_half9), false) >> (14 - 5);
+                    val[k] = __builtin_amdgcn_sdot2(lk_as_s2(KV[t][k]), wc0, lk_dot2_k(lk_as_s2(KV[t][k + 1]), wc1, k_half9), false) >> (14 - 5);
 #pragma unroll
                 for (int q2 = 0; q2 < 3; q2++) {
                     const lk_s2 jv = lk_as_s2(lk_pack16(val[2 * q2], val[2 * q2 + 1]));      // (positions beyond the run meet a zero Ix / Iy)
@@ -725,11 +742,15 @@ __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, u
     outx = resx; outy = resy;
 }
 
+__device__ __forceinline__ float lk_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+
 template <int NR, int WIN, int MAXIT>
 __device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict__ order)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    const int n = g.d_n ? min(*g.d_n, g.n_max) : g.n_max;
+    // (what a wave reads through a pointer that itself came from the unit table arrives in vector registers: the corner count and the key
+    // point are the same in every lane, and saying so keeps the per-level geometry and every test on it in scalar registers)
+    const int n = __builtin_amdgcn_readfirstlane(g.d_n ? min(*g.d_n, g.n_max) : g.n_max);
     // workgroup w runs on XCD w % 8: every XCD takes one contiguous eighth of the (spatially ordered) point list
     const unsigned per = ((unsigned)n + KM_XCDS - 1) / KM_XCDS, slot = (blockIdx.x % KM_XCDS) * per + blockIdx.x / KM_XCDS;
     if (blockIdx.x / KM_XCDS >= per || slot >= (unsigned)n) return;
@@ -745,7 +766,7 @@ __device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict
         const int y = r / rpr, x0 = (r - y * rpr) * LK_RUN;
         run_desc[t] = r < total ? (y | (x0 << 8) | (min(LK_RUN, win - x0) << 16)) : 0;
     }
-    const float px = g.pts_in[2 * p], py = g.pts_in[2 * p + 1];
+    const float px = lk_uniform(g.pts_in[2 * p]), py = lk_uniform(g.pts_in[2 * p + 1]);
     const float half = (float)(win - 1) * 0.5f;
     // one neighbourhood per image and level, centred on the key point's window: all loads of the key point in flight together
     int oA[2][2], oB[2][2];
@@ -779,11 +800,11 @@ __device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict
     }
     LK_WAVE_SYNC();
     float fx, fy;
-    lk2_track_point<NR, WIN, MAXIT>(g.A, g.B, pA, pB, oA, oB, px, py, geo, g.max_count, g.epsilon, run_desc, fx, fy, g.general_templates);
+    lk2_track_point<NR, WIN, MAXIT>(g.A, g.B, pA, pB, oA, oB, px, py, geo, g.max_count, g.epsilon, run_desc, fx, fy, g.general_templates, g.lk_reuse);
     if ((threadIdx.x & 63) == 0) { g.p1[2 * p] = fx; g.p1[2 * p + 1] = fy; }
     if (g.backward) {
         float rx, ry;
-        lk2_track_point<NR, WIN, MAXIT>(g.B, g.A, pB, pA, oB, oA, fx, fy, geo, g.max_count, g.epsilon, run_desc, rx, ry, g.general_templates);
+        lk2_track_point<NR, WIN, MAXIT>(g.B, g.A, pB, pA, oB, oA, fx, fy, geo, g.max_count, g.epsilon, run_desc, rx, ry, g.general_templates, g.lk_reuse);
         if ((threadIdx.x & 63) == 0) { g.p0r[2 * p] = rx; g.p0r[2 * p + 1] = ry; }
     }
 }
@@ -797,7 +818,7 @@ __global__ __launch_bounds__(64) KM_LK_OCC void lk2_kernel(lk_args g, const int 
 // the reference's window (matching_winsize 25, processing_configuration.json:14) with every size a compile-time constant.
 // 6 waves per SIMD: the register allocator would take 82 VGPRs (5 waves) for two fewer copies.
 #ifndef LK2_25_WAVES
-#define LK2_25_WAVES 6
+#define LK2_25_WAVES 5
 #endif
 #if LK2_25_WAVES
 #define LK2_25_OCC __attribute__((amdgpu_waves_per_eu(LK2_25_WAVES, LK2_25_WAVES)))
@@ -842,6 +863,7 @@ int kl_units_prepare(km_ctx *c, const km_units &U, int n_max, int win, int max_c
         g.max_count = max_count < 0 ? 0 : max_count > 100 ? 100 : max_count;
         g.backward = 1; g.epsilon = e * e; g.p1 = U.p1[u]; g.p0r = U.p0r[u]; g.left_band = nullptr;
         g.general_templates = km_dev_env("KARIOS_HIP_LK_GENERAL") ? 1 : 0;
+    g.lk_reuse = c->opt_lk_reuse ? 1 : 0;
     }
     lk_args *table = (lk_args *)km_ws(c, WS_UNITS_LK, sizeof(lk_args) * KM_UNITS_MAX);
     if (!table) return KM_E_NOMEM;
@@ -885,6 +907,7 @@ int kl_jobs_launch(km_ctx *c, const km_lk_job *jobs, int n_jobs, int n_max, int 
         g.max_count = max_count < 0 ? 0 : max_count > 100 ? 100 : max_count;
         g.backward = 1; g.epsilon = e * e; g.p1 = jobs[j].p1; g.p0r = jobs[j].p0r; g.left_band = nullptr;
         g.general_templates = km_dev_env("KARIOS_HIP_LK_GENERAL") ? 1 : 0;
+    g.lk_reuse = c->opt_lk_reuse ? 1 : 0;
     }
     lk_args *table = (lk_args *)km_ws(c, WS_UNITS_LK, sizeof(lk_args) * KM_LK_JOBS_MAX);
     if (!table) return KM_E_NOMEM;
@@ -903,6 +926,7 @@ int kl_track(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_pts_in,
     g.max_count = max_count < 0 ? 0 : max_count > 100 ? 100 : max_count;
     g.backward = backward_too ? 1 : 0;
     g.general_templates = km_dev_env("KARIOS_HIP_LK_GENERAL") ? 1 : 0;
+    g.lk_reuse = c->opt_lk_reuse ? 1 : 0;
     double e = epsilon < 0 ? 0 : epsilon > 10 ? 10 : epsilon;
     g.epsilon = e * e;
     g.p1 = d_p1; g.p0r = d_p0r; g.left_band = d_left_band;

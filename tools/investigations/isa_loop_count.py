@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Instruction mix of the hot loop of a kernel from the compiler's assembly (`hipcc -save-temps`): the innermost backward-branch loop
-that contains a marker instruction.  python tools/investigations/isa_loop_count.py <file.s> <kernel-symbol-substring> <marker-instruction> [rows per trip]"""
+that contains the marker instructions.  Several markers, separated by commas (e.g. v_floor_f32,v_add_u32_dpp for the LK iteration loop,
+whose level loop holds more v_floor_f32 than the iteration loop itself): the innermost loop that holds ALL of them.
+python tools/investigations/isa_loop_count.py <file.s> <kernel-symbol-substring> <marker-instruction>[,<marker> ...] [rows per trip]"""
 import collections
 import re
 import sys
@@ -17,9 +19,17 @@ for i, l in enumerate(body):
     m = re.search(r"s_c?branch\w*\s+(\.LBB\d+_\d+)", l)
     if m and m.group(1) in labels and labels[m.group(1)] < i:
         loops.append((labels[m.group(1)], i))
-# the loop with the most markers; among those the shortest (innermost)
-cands = sorted((-sum(marker in l for l in body[a:b]), b - a, a, b) for a, b in loops)
-_, _, a, b = cands[0]
+markers = marker.split(",")
+if len(markers) > 1:
+    # the shortest (innermost) loop that holds every marker
+    cands = sorted((b - a, a, b) for a, b in loops if all(any(m in l for l in body[a:b]) for m in markers))
+    if not cands:
+        sys.exit(f"{sym}: no loop holds all of {markers}")
+    _, a, b = cands[0]
+else:
+    # the loop with the most markers; among those the shortest (innermost)
+    cands = sorted((-sum(marker in l for l in body[a:b]), b - a, a, b) for a, b in loops)
+    _, _, a, b = cands[0]
 ins = [l.split()[0] for l in body[a:b + 1] if l.startswith("\t") and not l.strip().startswith((".", ";"))]
 c = collections.Counter(ins)
 valu = sum(v for k, v in c.items() if k.startswith("v_"))
