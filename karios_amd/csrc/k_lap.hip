@@ -390,10 +390,19 @@ __device__ __forceinline__ unsigned opaque_lane_offset(unsigned x)
     asm volatile("" : "+v"(x));
     return x;
 }
+// The same in place, for a loop: the old value dies in the asm, so no copy of the offset is made per use (the by-value form keeps its
+// argument alive and costs a v_mov each time).
+__device__ __forceinline__ void reopaque_lane_offset(unsigned &x) { asm volatile("" : "+v"(x)); }
+// f(0_c) .. f((N-1)_c): a fully unrolled loop whose index is a compile-time constant
+template <class F, int... I> __device__ __forceinline__ void lapm_for_impl(F &&f, std::integer_sequence<int, I...>)
+{
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void lapm_for(F &&f) { lapm_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 #define LAPM_VALID_OF(R) ((R) == 5 ? 240 : 248)      // output columns of a strip: 64 lanes x 4 columns less the halo lanes (two either side for radius 5)
 #ifndef LAPM_PF
-#define LAPM_PF 3      // source rows in flight per wave
+#define LAPM_PF 3      // source rows in flight per wave (interior trips: really so; 2, 3 and 4 measure the same - profiles/lap_march_rows_kernel_stats.md)
 #endif
 
 template <int R, typename T, bool MASK>
@@ -534,29 +543,31 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
         for (int k = 0; k < NR; k++)
 #pragma unroll
             for (int j = 0; j < 4; j++) ring[i][k][j] = 0;
-    // raw rows travel LAPM_PF rows ahead of their use (a short register FIFO; the copies disappear in the unrolled body)
-    T nxt[LAPM_PF][2][4];
-#pragma unroll
-    for (int f = 0; f < LAPM_PF; f++) load_raw(min(y0 - R + f, y1 + R - 1), nxt[f]);
-    for (int mbase = y0 - R; mbase < y1 + R; mbase += NR) {
-#pragma unroll
-        for (int k = 0; k < NR; k++) {
-            const int m = mbase + k;                 // source row of this step (may lie outside: mirrored)
-            if (m >= y1 + R) continue;               // (no break: ring indices must stay compile-time constants)
-            T v[2][4];
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    v[i][j] = nxt[0][i][j];
-#pragma unroll
-                    for (int f = 0; f + 1 < LAPM_PF; f++) nxt[f][i][j] = nxt[f + 1][i][j];
-                }
-            if (m + LAPM_PF < y1 + R) load_raw(m + LAPM_PF, nxt[LAPM_PF - 1]);
+    // The stores of an interior trip (below) go through buffer descriptors: one per plane, its base the plane's row of the trip's
+    // first step (mask: source row m; outputs: row m - R, at radius 5 the binomial's row m - RH - 1, the same), its size the rows
+    // these trips write, the row a scalar offset that advances by W per step.  Every lane stores, unconditionally - a lane that
+    // produces no output (halo lanes, lanes right of the image) carries an offset beyond any size (2^31) and the hardware drops its
+    // store.  No exec mask, no branch round a store: the compiler's wait-count bookkeeping merges the two sides of such a branch to
+    // "no store issued" and then waits for more than the row a step consumes.
+    __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void *)nullptr, 0, 0, 0x00020000), rs_o0 = rs_m, rs_o1 = rs_m;
+    unsigned srow = 0;                                                    // byte offset of the current step's row behind the bases
+    const unsigned ux = out_lane ? ugx : 0x80000000u;
+    const uint32_t cnt_mask_in = out_lane ? cnt_mask : 0u;
+    (void)srow; (void)ux; (void)cnt_mask_in;
+    // ---- one row step: source row m (ring slot k, a compile-time constant), raw pixels v.  IN: a step of an interior trip.  What IN
+    // replaces, everywhere below:
+    //   the tests on m (mask row: y0 <= m < y1; output row: m - R >= y0)  ->  nothing, they hold for every row of an interior trip
+    //   `out_lane` round a store                                           ->  every lane stores, `ux` is out of range where !out_lane
+    //   `out_lane` round the count of valid pixels, `cnt_mask`             ->  `cnt_mask_in`, zero where !out_lane
+    //   row pointers computed from m, global stores                        ->  descriptor + `srow`
+    // (IN implies FAST; the general step keeps the parent's text, its per-lane fallbacks included)
+    auto row_step = [&](auto k_tag, auto in_tag, int m, const T (&v)[2][4]) {
+            constexpr int k = decltype(k_tag)::value;
+            constexpr bool IN = decltype(in_tag)::value;
             // ---- auto mask of source row m (it is an output row when y0 <= m < y1)
             if constexpr (MASK && FAST && sizeof(T) == 2) {
                 // packed form: a pixel pair is valid iff min(mon, ref, mon ^ nodata_mon, ref ^ nodata_ref) != 0 (unsigned)
-                if (m >= y0 && m < y1 && out_lane) {
+                if (IN || (m >= y0 && m < y1 && out_lane)) {
                     uint2 qm, qr;
                     __builtin_memcpy(&qm, v[1], 8); __builtin_memcpy(&qr, v[0], 8);
                     auto nz2 = [&](uint32_t a, uint32_t b) {
@@ -567,20 +578,29 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                         return __builtin_bit_cast(uint32_t, mn2);
                     };
                     const uint32_t mp = __builtin_amdgcn_perm(nz2(qm.y, qr.y), nz2(qm.x, qr.x), 0x06040200u);
-                    cnt += (unsigned)__popc(mp & cnt_mask);
-                    __builtin_memcpy((mask_out + (size_t)m * W) + opaque_lane_offset(ugx), &mp, 4);
+                    if constexpr (IN) {
+                        cnt += (unsigned)__popc(mp & cnt_mask_in);
+                        __builtin_amdgcn_raw_buffer_store_b32(mp, rs_m, ux, srow, 0);
+                    } else {
+                        cnt += (unsigned)__popc(mp & cnt_mask);
+                        __builtin_memcpy((mask_out + (size_t)m * W) + opaque_lane_offset(ugx), &mp, 4);
+                    }
                 }
             } else if constexpr (MASK) {
-                if (m >= y0 && m < y1 && out_lane) {
+                if (IN || (m >= y0 && m < y1 && out_lane)) {
                     uint32_t mp = 0;
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         const bool ok = (gx0 + j < W) && px_valid<T>(v[1][j], v[0][j], nd);
                         mp |= (ok ? 1u : 0u) << (8 * j);
-                        cnt += ok && gx0 + j >= cnt_from;
+                        if constexpr (!IN) cnt += ok && gx0 + j >= cnt_from;
                     }
                     const size_t o = (size_t)m * W + gx0;
-                    if (FAST) __builtin_memcpy(mask_out + o, &mp, 4);
+                    (void)o;
+                    if constexpr (IN) {
+                        cnt += (unsigned)__popc(mp & cnt_mask_in);       // (cnt_mask keeps the bytes of the columns from cnt_from on)
+                        __builtin_amdgcn_raw_buffer_store_b32(mp, rs_m, ux, srow, 0);
+                    } else if (FAST) __builtin_memcpy(mask_out + o, &mp, 4);
                     else if (gx0 + 3 < W && (o & 3) == 0) *(uint32_t *)(mask_out + o) = mp;
                     else {
                         for (int j = 0; j < 4 && gx0 + j < W; j++) mask_out[o + j] = (uint8_t)((mp >> (8 * j)) & 1u);
@@ -595,8 +615,10 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 for (int j = 0; j < 4; j++) cw |= st[i](v[i][j], nullptr) << (8 * j);
                 cw ^= (i == 1 && invert1) ? 0x7f7f7f7fu : 0x80808080u;   // (255 - u) - 128 == u ^ 0x7f
                 if constexpr (FAST) cw = __builtin_amdgcn_perm(cw, cw, edge_sel);                    // border lanes: mirrored columns
-                const uint32_t lw = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cw, 0x138, 0xf, 0xf, false);   // lane-1
-                const uint32_t rw = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cw, 0x130, 0xf, 0xf, false);   // lane+1
+                // (bound_ctrl: the lane without a neighbour reads 0, and the move needs no `old` value - an update_dpp(0, ..) costs a
+                //  v_mov_b32 v, 0 to seed each of the two)
+                const uint32_t lw = (uint32_t)__builtin_amdgcn_mov_dpp((int)cw, 0x138, 0xf, 0xf, true);   // lane-1
+                const uint32_t rw = (uint32_t)__builtin_amdgcn_mov_dpp((int)cw, 0x130, 0xf, 0xf, true);   // lane+1
                 // ---- horizontal kd / ks passes: bytes [4+o-R, 4+o-R+8) of (lw | cw | rw)
 #pragma unroll
                 for (int o = 0; o < 4; o++) {
@@ -632,7 +654,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 // horizontal [1 2 1], then the vertical [1 2 1] over the rows yy - 2 .. yy: output row yo = yy - 1.  An image whose kernel is
                 // smaller (b3 = 0) passes its 9-tap-padded row through unchanged, one row late like the other.
                 const int yy = m - RH, yo = yy - 1;
-                if (yy >= y0 - 1) {
+                if (IN || yy >= y0 - 1) {
 #pragma unroll
                     for (int i = 0; i < 2; i++) {
                         int a[4], h[4];
@@ -647,8 +669,8 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                         }
                         uint32_t packed = 0;
                         if (cf.b3[i]) {
-                            const int al = __builtin_amdgcn_update_dpp(0, a[3], 0x138, 0xf, 0xf, false);      // lane - 1: the column left of this lane's
-                            const int ar = __builtin_amdgcn_update_dpp(0, a[0], 0x130, 0xf, 0xf, false);      // lane + 1
+                            const int al = __builtin_amdgcn_mov_dpp(a[3], 0x138, 0xf, 0xf, true);      // lane - 1: the column left of this lane's
+                            const int ar = __builtin_amdgcn_mov_dpp(a[0], 0x130, 0xf, 0xf, true);      // lane + 1
 #pragma unroll
                             for (int o = 0; o < 4; o++) h[o] = (o == 0 ? al : a[o - 1]) + 2 * a[o] + (o == 3 ? ar : a[o + 1]);
 #pragma unroll
@@ -659,9 +681,11 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                         }
 #pragma unroll
                         for (int o = 0; o < 4; o++) { hp[i][1][o] = hp[i][0][o]; hp[i][0][o] = h[o]; }
-                        if (yo >= y0 && out_lane) {
+                        if (IN || (yo >= y0 && out_lane)) {
                             const size_t off = (size_t)yo * W + gx0;
-                            if (FAST) __builtin_memcpy((outs[i] + (size_t)yo * W) + opaque_lane_offset(ugx), &packed, 4);
+                            (void)off;
+                            if constexpr (IN) __builtin_amdgcn_raw_buffer_store_b32(packed, i == 0 ? rs_o0 : rs_o1, ux, srow, 0);
+                            else if (FAST) __builtin_memcpy((outs[i] + (size_t)yo * W) + opaque_lane_offset(ugx), &packed, 4);
                             else if (gx0 + 3 < W && (off & 3) == 0) *(uint32_t *)(outs[i] + off) = packed;
                             else {
                                 for (int j = 0; j < 4 && gx0 + j < W; j++) outs[i][off + j] = (uint8_t)(packed >> (8 * j));
@@ -671,7 +695,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 }
             } else {
             const int y = m - R;
-            if (y >= y0 && out_lane) {
+            if (IN || (y >= y0 && out_lane)) {
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     uint32_t packed = 0;
@@ -685,7 +709,9 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                         packed |= (uint32_t)min(max(acc, 0), 255) << (8 * o);
                     }
                     const size_t off = (size_t)y * W + gx0;
-                    if (FAST) __builtin_memcpy((outs[i] + (size_t)y * W) + opaque_lane_offset(ugx), &packed, 4);
+                    (void)off;
+                    if constexpr (IN) __builtin_amdgcn_raw_buffer_store_b32(packed, i == 0 ? rs_o0 : rs_o1, ux, srow, 0);
+                    else if (FAST) __builtin_memcpy((outs[i] + (size_t)y * W) + opaque_lane_offset(ugx), &packed, 4);
                     else if (gx0 + 3 < W && (off & 3) == 0) *(uint32_t *)(outs[i] + off) = packed;
                     else {
                         for (int j = 0; j < 4 && gx0 + j < W; j++) outs[i][off + j] = (uint8_t)(packed >> (8 * j));
@@ -693,7 +719,87 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
                 }
             }
             }
+    };  // row_step
+
+    // An item's march: GENERAL trips (the warm-up that fills the ring, the rows that mirror at the top or bottom of the image, the tail
+    // of the item) and INTERIOR trips in between.  Both run whole trips of NR row steps from the item's first source row y0 - R on, so
+    // the ring slot of a row stays the compile-time constant k of its step.
+    //  general:  the guarded form - every condition on m tested, rows mirrored, the row in flight LAPM_PF steps ahead kept in a short
+    //            register FIFO that is SHIFTED every step: the shift reads the newest slot, so a general step waits for the loads of
+    //            the step before (and, vmcnt counting stores in order with loads, for that step's stores)
+    //  interior: trips whose NR rows m all are mask rows and output rows (y0 + R <= m < y1) with the rows m .. m + PF inside the image
+    //            and inside [y0 - R, y1 + R).  No guard, no conditional load, no mirror; row bases advance by the stride.  The raw rows
+    //            sit in NR STATIC slots - step k consumes slot k and loads the row of step k + PF into slot (k + PF) % NR - of which
+    //            the live ranges keep PF + 1 in registers; nothing is copied, and a step waits only for the row it consumes.
+    // A switch between the two forms hands no row in flight over: the last general steps of the warm-up still fill their FIFO, the
+    // interior trips load those rows again into their slots, and the tail's FIFO reloads what the last trip prefetched - 2 PF row
+    // loads per item that hit the cache (of the 40 - 170 rows of an item), for two forms that share no register state.
+    // rows in flight: LAPM_PF, but two for float32 at radius 5 - a raw row is 8 registers there, and the third row ahead takes that
+    // kernel from 165 to 174 registers: past 168, from three waves per SIMD to two (in the general steps' FIFO as in the slots)
+    constexpr int DEPTH = (R == 5 && sizeof(T) == 4 && LAPM_PF > 2) ? 2 : LAPM_PF;
+    constexpr int PF = DEPTH < NR ? DEPTH : NR - 1;         // (radius 1: three slots, so at most two rows ahead)
+    constexpr int WARM = (2 * R + NR - 1) / NR * NR;        // whole trips until every step writes an output row: NR (radius 5: 2 NR)
+    const int m_end = y1 + R;                               // one past the item's last source row
+    int mbase = y0 - R;
+    int n_in = 0;                                           // interior trips
+    if constexpr (FAST) n_in = (min(y1, min(H, m_end) - PF) - (mbase + WARM)) / NR;
+    int m_stop = n_in > 0 ? mbase + WARM : m_end;
+    for (;;) {
+        {
+            T nxt[DEPTH][2][4];
+#pragma unroll
+            for (int f = 0; f < DEPTH; f++) load_raw(min(mbase + f, m_end - 1), nxt[f]);
+            for (; mbase < m_stop; mbase += NR) {
+                lapm_for<NR>([&](auto k_tag) {
+                    const int m = mbase + decltype(k_tag)::value;      // source row of this step (may lie outside: mirrored)
+                    if (m >= m_end) return;                  // (no break: ring indices must stay compile-time constants)
+                    T v[2][4];
+#pragma unroll
+                    for (int i = 0; i < 2; i++)
+#pragma unroll
+                        for (int j = 0; j < 4; j++) {
+                            v[i][j] = nxt[0][i][j];
+#pragma unroll
+                            for (int f = 0; f + 1 < DEPTH; f++) nxt[f][i][j] = nxt[f + 1][i][j];
+                        }
+                    if (m + DEPTH < m_end) load_raw(m + DEPTH, nxt[DEPTH - 1]);
+                    row_step(k_tag, std::false_type{}, m, v);
+                });
+            }
         }
+        if (mbase >= m_end) break;
+        if constexpr (FAST) {
+            const ptrdiff_t sb0 = stride0 * (ptrdiff_t)sizeof(T), sb1 = stride1 * (ptrdiff_t)sizeof(T);
+            const char *p0 = (const char *)img0 + (ptrdiff_t)mbase * sb0, *p1 = (const char *)img1 + (ptrdiff_t)mbase * sb1;   // the next row to load
+            unsigned lx = ugx_load * (unsigned)sizeof(T);    // byte offset of the lane's first column, opaque in place (see opaque_lane_offset)
+            auto load_next = [&](T (&v)[2][4]) {
+                reopaque_lane_offset(lx);
+                __builtin_memcpy(v[0], p0 + lx, 4 * sizeof(T));
+                __builtin_memcpy(v[1], p1 + lx, 4 * sizeof(T));
+                p0 += sb0; p1 += sb1;
+            };
+            T slot[NR][2][4];
+#pragma unroll
+            for (int f = 0; f < PF; f++) load_next(slot[f]);
+            const int span = n_in * NR * W;                  // the rows these trips write (an item has at most 4096 rows: far below 2^31 bytes)
+            if constexpr (MASK) rs_m = __builtin_amdgcn_make_buffer_rsrc((void *)(mask_out + (size_t)mbase * W), 0, span, 0x00020000);
+            rs_o0 = __builtin_amdgcn_make_buffer_rsrc((void *)(out0 + (size_t)(mbase - R) * W), 0, span, 0x00020000);
+            rs_o1 = __builtin_amdgcn_make_buffer_rsrc((void *)(out1 + (size_t)(mbase - R) * W), 0, span, 0x00020000);
+            srow = 0;
+            for (int t = 0; t < n_in; t++) {
+                lapm_for<NR>([&](auto k_tag) {
+                    constexpr int k = decltype(k_tag)::value;
+                    load_next(slot[(k + PF) % NR]);
+                    row_step(k_tag, std::true_type{}, mbase + k, slot[k]);
+                    srow += (unsigned)W;
+                    // (a trip is one basic block: without a fence between the steps the scheduler interleaves the seven rows - a
+                    //  fifth more registers, a wave per SIMD less - and moves the loads away from the step that issues them)
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                mbase += NR;
+            }
+        }
+        m_stop = m_end;
     }
     };  // march
     // FAST: every lane of the item either lies inside the image with its 4 columns or is a whole-lane mirror of its in-image neighbour
