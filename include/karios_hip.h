@@ -710,6 +710,49 @@ int km_chips_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, i
                  ptrdiff_t smon, const float *d_x0, const float *d_y0, const float *d_dx, const float *d_dy, int n, int ksize_ref, int ksize_mon,
                  const km_chip_outputs *d_out);
 
+/* ---- the report's numbers on resident data (karios/report/overview_plot.py:134-194, karios/report/commons.py:49-71);
+ * tests/report_restatement.py is the definition.
+ *
+ * Display range of one raster (KM_U8, KM_U16, KM_I16, KM_F32; H x W, row stride in elements).  A pixel is INVALID when its byte of
+ * the optional uint8 mask (own row stride, NULL: no mask) is 0, when it equals one of the n_no_values (0 .. KM_DISPLAY_MAX_NO_VALUES)
+ * DN values, or when it equals *nodata (NULL: none).  Comparisons are by value, (double)pixel == v: a value the pixel type cannot
+ * hold and a NaN match nothing, 0 matches -0.0.  A pixel is VALID when it is finite, not zero and not invalid.  Results, in host
+ * memory in both forms: out->n_valid; out->n_invalid (counted whatever the pixel's value); out->raster_min / raster_max, the
+ * minimum and maximum of every pixel that is not NaN (a zero as +0.0; NaN when there is none); and per quantile q[j] in [0, 1]
+ * of the valid pixels v0 / v1 / vi with the meaning km_order_statistics gives them (untouched when n_valid is 0, which is no error);
+ * for a KM_F32 raster vi = float32(n_valid - 1) * float32(q[j]), the float32 product np.percentile forms for a float32 array.
+ * Exact (a radix select under the predicate, integer counters): two calls give the same bits.  Every argument error is KM_E_ARG
+ * before anything is launched.  The device form reads device memory and completes the context stream before it returns. */
+#define KM_DISPLAY_MAX_NO_VALUES 16
+typedef struct km_display_range_result {
+    int64_t n_valid, n_invalid;
+    double raster_min, raster_max;
+} km_display_range_result;
+int km_display_range(km_ctx *ctx, const void *img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *mask, ptrdiff_t mask_stride,
+                     const double *nodata, const double *no_values, int n_no_values, int n_q, const double *q, km_display_range_result *out,
+                     double *v0, double *v1, double *vi);
+int km_display_range_dev(km_ctx *ctx, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *d_mask, ptrdiff_t mask_stride,
+                         const double *nodata, const double *no_values, int n_no_values, int n_q, const double *q, km_display_range_result *out,
+                         double *v0, double *v1, double *vi);
+/* mean_profile (commons.py:49-71) of n_prof (1 .. KM_PROFILE_MAX) profiles over the same n rows (0 .. 2^20): per profile float32
+ * columns `values` and `positions` and a bin size (1 .. 2^24).  Rows are grouped by np.floor_divide(positions, float32(bin_size))
+ * (numpy's divmod rule; a NaN key - NaN or infinite position - drops the row; -0.0 and 0.0 are one group), the groups ascending.
+ * Per group g, into outputs of capacity n: key[g]; position[g] = int32(float32(float32(key * bin) + float32(bin / 2))); count[g] =
+ * the rows whose value is not NaN; mean[g] = pandas' Kahan sum in float32 over those rows in row order / float32(count), NaN for
+ * count 0; std[g] = float32(sqrt(M2 / (count - 1))) of pandas' Welford recurrence in float64, NaN for count < 2.  n_groups[p] and
+ * n_out_of_range[p] (groups whose float32 position int32 cannot hold; their position[g] is 0) are host memory in both forms; the
+ * columns and outputs are host memory in the host form, device memory in the device form, which completes the context stream. */
+#define KM_PROFILE_MAX 8
+typedef struct km_profile {
+    const float *values, *positions;           /* n each */
+    float *key;                                /* outputs, n each */
+    int32_t *position, *count;
+    float *mean, *std;
+    int32_t bin_size;
+} km_profile;
+int km_mean_profiles(km_ctx *ctx, int n, int n_prof, const km_profile *prof, int32_t *n_groups, int32_t *n_out_of_range);
+int km_mean_profiles_dev(km_ctx *ctx, int n, int n_prof, const km_profile *d_prof, int32_t *n_groups, int32_t *n_out_of_range);
+
 #ifdef __cplusplus
 }
 #endif

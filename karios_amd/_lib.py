@@ -73,6 +73,19 @@ class ChipOutputs(C.Structure):
                 ("mon_lap", C.c_void_p), ("ok", C.c_void_p), ("windows", C.c_void_p)]
 
 
+class DisplayRangeResult(C.Structure):
+    """km_display_range_result of include/karios_hip.h."""
+    _fields_ = [("n_valid", C.c_int64), ("n_invalid", C.c_int64), ("raster_min", C.c_double), ("raster_max", C.c_double)]
+
+
+class Profile(C.Structure):
+    """km_profile of include/karios_hip.h."""
+    _fields_ = [("values", C.c_void_p), ("positions", C.c_void_p), ("key", C.c_void_p), ("position", C.c_void_p), ("count", C.c_void_p),
+                ("mean", C.c_void_p), ("std", C.c_void_p), ("bin_size", C.c_int32)]
+
+
+DISPLAY_MAX_NO_VALUES = 16     # KM_DISPLAY_MAX_NO_VALUES
+PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = 8, 1 << 20, 1 << 24   # KM_PROFILE_MAX; rows and bin size km_mean_profiles takes
 CHIP_SIZE, CHIP_MAX_GRID, CHIP_PICKS = 57, 16, 5      # KM_CHIP_SIZE, KM_CHIP_MAX_GRID, KM_CHIP_PICKS
 CHIP_SELECT_MAX_ROWS, CHIP_MAX_ROWS = 1 << 24, 1 << 20
 CLIP_MAX_ROWS = 32768          # rows one unit of km_sigma_clip_dev / the "frame_clip" stage holds
@@ -194,6 +207,10 @@ SIGNATURES = {
     "km_chip_select_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _d, _i, _i, _i, _vp, C.POINTER(C.c_int32)]),
     "km_chips": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(ChipOutputs)]),
     "km_chips_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(ChipOutputs)]),
+    "km_display_range": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, _pd, _pd, _i, _i, _pd, C.POINTER(DisplayRangeResult), _pd, _pd, _pd]),
+    "km_display_range_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, _pd, _pd, _i, _i, _pd, C.POINTER(DisplayRangeResult), _pd, _pd, _pd]),
+    "km_mean_profiles": (_i, [_vp, _i, _i, C.POINTER(Profile), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "km_mean_profiles_dev": (_i, [_vp, _i, _i, C.POINTER(Profile), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -2,8 +2,11 @@
 // percentiles of the quality check (karios/api/core.py:491-506): exact order statistics of a raster, the percentile stretch to uint8
 // and CLAHE.  The kernels live in k_prep.hip.  The interpolation between the two order statistics of a percentile is numpy's and stays
 // with the caller (karios_amd/ops.py): it is arithmetic of the SOURCE dtype there, wrap-around of int16 included.
+// Also the display range of the report's overview figure (karios/report/overview_plot.py:134-194): the same select under the
+// reference's invalid-pixel rule; kernels in k_report.hip.
 #include "api_internal.hpp"
 #include "k_prep.hpp"
+#include "k_report.hpp"
 
 #include <stddef.h>
 #include <string.h>
@@ -55,6 +58,71 @@ int stats_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t s
     return KM_OK;
 }
 
+// ---- the display range of the report's overview (karios/report/overview_plot.py:134-194)
+struct range_args {
+    const void *img;
+    int dtype, H, W;
+    ptrdiff_t stride;
+    const uint8_t *mask;
+    ptrdiff_t mask_stride;
+    const double *nodata, *no_values;
+    int n_no_values, n_q;
+    const double *q;
+    km_display_range_result *out;
+    double *v0, *v1, *vi;
+};
+
+int range_check(km_ctx *c, const range_args &a)
+{
+    int rc;
+    if ((rc = check_image(c, a.img, a.H, a.W, a.stride, "display_range"))) return rc;
+    if (!prep_dtype(a.dtype)) return km_fail(c, KM_E_ARG, "display_range: dtype %d (uint8, uint16, int16 and float32 only)", a.dtype);
+    if (a.mask && a.mask_stride < a.W) return km_fail(c, KM_E_ARG, "display_range: mask stride %td < width %d", a.mask_stride, a.W);
+    if (a.n_no_values < 0 || (a.n_no_values > 0 && !a.no_values)) return km_fail(c, KM_E_ARG, "display_range: bad DN value list");
+    if (a.n_no_values > KM_DISPLAY_MAX_NO_VALUES)
+        return km_fail(c, KM_E_ARG, "display_range: %d DN values (at most %d)", a.n_no_values, KM_DISPLAY_MAX_NO_VALUES);
+    if (a.n_q < 0 || !a.out || (a.n_q && (!a.q || !a.v0 || !a.v1 || !a.vi))) return km_fail(c, KM_E_ARG, "display_range: bad arguments");
+    for (int j = 0; j < a.n_q; j++)
+        if (!(a.q[j] >= 0.0 && a.q[j] <= 1.0)) return km_fail(c, KM_E_ARG, "display_range: quantile %d = %g outside [0, 1]", j, a.q[j]);
+    if ((unsigned long long)a.H * (unsigned long long)a.W >= (1ull << 42))
+        return km_fail(c, KM_E_ARG, "display_range: %d x %d raster", a.H, a.W);
+    return KM_OK;
+}
+
+// the DN values and the no-data value as pixels of the raster's type: what no pixel can equal is left out
+rp::tests range_tests(const range_args &a)
+{
+    rp::tests t = kr_no_tests();
+    for (int k = 0; k < a.n_no_values; k++) kr_add_test(t, a.dtype, a.no_values[k]);
+    if (a.nodata) kr_add_test(t, a.dtype, *a.nodata);
+    return t;
+}
+
+// the quantiles go through the select KR_MAX_Q at a time, like stats_dev; the counts and the extremes come with every group
+int range_dev(km_ctx *c, const range_args &a, const void *d_img, ptrdiff_t stride, const uint8_t *d_mask, ptrdiff_t mask_stride)
+{
+    const size_t ws_bytes = up256(kr_range_ws_bytes());
+    char *ws = (char *)km_ws(c, WS_RP_STATE, ws_bytes + sizeof(kr_range_result));
+    if (!ws) return KM_E_NOMEM;
+    kr_range_result *d_res = (kr_range_result *)(ws + ws_bytes);
+    const rp::tests t = range_tests(a);
+    kr_range_result res;
+    int j0 = 0;
+    do {
+        const int m = a.n_q - j0 < KR_MAX_Q ? a.n_q - j0 : KR_MAX_Q;
+        int rc;
+        if ((rc = kr_display_range(c, d_img, a.dtype, a.H, a.W, stride, d_mask, mask_stride, t, m, a.q + j0, ws, d_res))) return rc;
+        KM_D2H(c, &res, d_res, sizeof res);
+        KM_FLUSH(c);
+        a.out->n_valid = (int64_t)res.n_valid; a.out->n_invalid = (int64_t)res.n_invalid;
+        a.out->raster_min = res.raster_min; a.out->raster_max = res.raster_max;
+        if (res.n_valid > 0)
+            for (int j = 0; j < m; j++) { a.vi[j0 + j] = res.vi[j]; a.v0[j0 + j] = res.v0[j]; a.v1[j0 + j] = res.v1[j]; }
+        j0 += m;
+    } while (j0 < a.n_q);
+    return KM_OK;
+}
+
 int stretch_args(km_ctx *c, const void *img, int dtype, int H, int W, ptrdiff_t stride, const void *out, ptrdiff_t ostride)
 {
     int rc;
@@ -101,6 +169,29 @@ int km_order_statistics(km_ctx *c, const void *img, int dtype, int H, int W, ptr
     void *d_img;
     if ((rc = upload_image(c, WS_RAW_A, img, km_dtype_size(dtype), H, W, stride, &d_img))) return rc;
     return stats_dev(c, d_img, dtype, H, W, W, exclude, n_q, q, n_out, v0, v1, vi);
+}
+
+int km_display_range_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *d_mask, ptrdiff_t mask_stride,
+                         const double *nodata, const double *no_values, int n_no_values, int n_q, const double *q, km_display_range_result *out,
+                         double *v0, double *v1, double *vi)
+{
+    const range_args a = {d_img, dtype, H, W, stride, d_mask, mask_stride, nodata, no_values, n_no_values, n_q, q, out, v0, v1, vi};
+    int rc;
+    if ((rc = begin_call(c)) || (rc = range_check(c, a))) return rc;
+    return range_dev(c, a, d_img, stride, d_mask, mask_stride);
+}
+
+int km_display_range(km_ctx *c, const void *img, int dtype, int H, int W, ptrdiff_t stride, const uint8_t *mask, ptrdiff_t mask_stride,
+                     const double *nodata, const double *no_values, int n_no_values, int n_q, const double *q, km_display_range_result *out,
+                     double *v0, double *v1, double *vi)
+{
+    const range_args a = {img, dtype, H, W, stride, mask, mask_stride, nodata, no_values, n_no_values, n_q, q, out, v0, v1, vi};
+    int rc;
+    if ((rc = begin_call(c)) || (rc = range_check(c, a))) return rc;
+    void *d_img, *d_mask = nullptr;
+    if ((rc = upload_image(c, WS_RAW_A, img, km_dtype_size(dtype), H, W, stride, &d_img))) return rc;
+    if (mask && (rc = upload_image(c, WS_MASK_IN, mask, 1, H, W, mask_stride, &d_mask))) return rc;
+    return range_dev(c, a, d_img, W, (const uint8_t *)d_mask, W);
 }
 
 int km_stretch_percentile_u8_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, double lo, double hi, uint8_t *d_out,

@@ -1,11 +1,13 @@
 // Scoring entry points: ZNCCService.compute_zncc / _zncc2 (zncc_service.py:45-238), the mutual-information scores
 // (mutual_info_service.py:73-130, zncc_service.py:240-287), the DN-value filter of the key points (core.py:650-737) and
 // KariosAPI.analyze_accuracy (core.py:268-328): the valid-pixel count and GeometricStat (accuracy_statistics.py); the tracker's outlier clip
-// (klt.py:52-71) on resident columns; ChipService.generate_chips (report/chip_service.py): the key-point selection and the chips.
+// (klt.py:52-71) on resident columns; ChipService.generate_chips (report/chip_service.py): the key-point selection and the chips;
+// mean_profile of the report's figures (report/commons.py:49-71).
 #include "api_internal.hpp"
 #include "k_accuracy.hpp"
 #include "k_chips.hpp"
 #include "k_clip.hpp"
+#include "k_report.hpp"
 
 #include <cstring>
 #include <vector>
@@ -432,6 +434,97 @@ int km_chips(km_ctx *c, const void *ref, const void *mon, int dtype, int Href, i
     KM_D2H(c, out->windows, d.windows, (size_t)n * 4 * sizeof(int32_t));
     KM_D2H(c, out->ok, d.ok, (size_t)n);
     KM_FLUSH(c);
+    return KM_OK;
+}
+
+}  // extern "C"
+
+// ---- mean_profile of the report's figures (karios/report/commons.py:49-71): every check in front of the first launch or copy
+namespace {
+
+int check_profiles_args(km_ctx *c, int n, int n_prof, const km_profile *prof, const int32_t *n_groups, const int32_t *n_out_of_range)
+{
+    if (n < 0 || n > rp::MAX_ROWS) return km_fail(c, KM_E_ARG, "mean_profiles: %d rows (0 .. 2^20)", n);
+    if (n_prof < 1 || n_prof > KM_PROFILE_MAX) return km_fail(c, KM_E_ARG, "mean_profiles: %d profiles (1 .. %d per call)", n_prof, KM_PROFILE_MAX);
+    if (!prof || !n_groups || !n_out_of_range) return km_fail(c, KM_E_ARG, "mean_profiles: null argument");
+    for (int k = 0; k < n_prof; k++) {
+        const km_profile &p = prof[k];
+        if (p.bin_size < 1 || p.bin_size > rp::MAX_BIN) return km_fail(c, KM_E_ARG, "mean_profiles: bin size %d of profile %d (1 .. 2^24)", p.bin_size, k);
+        if (n > 0 && (!p.values || !p.positions || !p.key || !p.position || !p.count || !p.mean || !p.std))
+            return km_fail(c, KM_E_ARG, "mean_profiles: null column or output of profile %d", k);
+    }
+    return KM_OK;
+}
+
+// the profiles one after the other on the context stream; their counts come back in one copy
+int mean_profiles_dev(km_ctx *c, int n, int n_prof, const km_profile *d_prof, int32_t *n_groups, int32_t *n_out_of_range)
+{
+    const size_t cap = n > 0 ? (size_t)n : 1;
+    kr_profile_ws ws;
+    ws.keys_a = (unsigned long long *)km_ws(c, WS_RP_KEYS0, cap * sizeof(unsigned long long));
+    ws.keys_b = (unsigned long long *)km_ws(c, WS_RP_KEYS1, cap * sizeof(unsigned long long));
+    char *fl = (char *)km_ws(c, WS_RP_FLAG, up256(cap * sizeof(unsigned)) + KM_PROFILE_MAX * KR_COUNTS * sizeof(int32_t));
+    if (!ws.keys_a || !ws.keys_b || !fl) return KM_E_NOMEM;
+    ws.flags = (unsigned *)fl;
+    int32_t *d_counts = (int32_t *)(fl + up256(cap * sizeof(unsigned)));
+    for (int k = 0; k < n_prof; k++) {
+        const km_profile &q = d_prof[k];
+        const kr_profile p = {q.values, q.positions, q.bin_size, q.key, q.position, q.count, q.mean, q.std};
+        const int rc = kr_mean_profile(c, p, n, ws, d_counts + (size_t)k * KR_COUNTS);
+        if (rc) return rc;
+    }
+    int32_t counts[KM_PROFILE_MAX * KR_COUNTS];
+    KM_D2H(c, counts, d_counts, (size_t)n_prof * KR_COUNTS * sizeof(int32_t));
+    KM_FLUSH(c);
+    for (int k = 0; k < n_prof; k++) { n_groups[k] = counts[k * KR_COUNTS + KR_GROUPS]; n_out_of_range[k] = counts[k * KR_COUNTS + KR_OUT_OF_RANGE]; }
+    return KM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int km_mean_profiles_dev(km_ctx *c, int n, int n_prof, const km_profile *d_prof, int32_t *n_groups, int32_t *n_out_of_range)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_profiles_args(c, n, n_prof, d_prof, n_groups, n_out_of_range))) return rc;
+    return mean_profiles_dev(c, n, n_prof, d_prof, n_groups, n_out_of_range);
+}
+
+int km_mean_profiles(km_ctx *c, int n, int n_prof, const km_profile *prof, int32_t *n_groups, int32_t *n_out_of_range)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_profiles_args(c, n, n_prof, prof, n_groups, n_out_of_range))) return rc;
+    // WS_RP_IO: per profile values | positions | key | position | count | mean | std, n words each
+    const size_t cap = n > 0 ? (size_t)n : 1;
+    uint32_t *io = (uint32_t *)km_ws(c, WS_RP_IO, (size_t)n_prof * 7 * cap * sizeof(uint32_t));
+    if (!io) return KM_E_NOMEM;
+    km_profile d[KM_PROFILE_MAX];
+    for (int k = 0; k < n_prof; k++) {
+        uint32_t *b = io + (size_t)k * 7 * cap;
+        d[k].values = (const float *)b; d[k].positions = (const float *)(b + cap);
+        d[k].key = (float *)(b + 2 * cap); d[k].position = (int32_t *)(b + 3 * cap); d[k].count = (int32_t *)(b + 4 * cap);
+        d[k].mean = (float *)(b + 5 * cap); d[k].std = (float *)(b + 6 * cap);
+        d[k].bin_size = prof[k].bin_size;
+        if (n > 0) {
+            int rch;
+            if ((rch = h2d_now(c, b, prof[k].values, (size_t)n * sizeof(float))) || (rch = h2d_now(c, b + cap, prof[k].positions, (size_t)n * sizeof(float))))
+                return rch;
+        }
+    }
+    if ((rc = mean_profiles_dev(c, n, n_prof, d, n_groups, n_out_of_range))) return rc;
+    bool any = false;
+    for (int k = 0; k < n_prof; k++) {
+        const size_t bytes = (size_t)n_groups[k] * sizeof(uint32_t);
+        if (!bytes) continue;
+        KM_D2H(c, prof[k].key, d[k].key, bytes);
+        KM_D2H(c, prof[k].position, d[k].position, bytes);
+        KM_D2H(c, prof[k].count, d[k].count, bytes);
+        KM_D2H(c, prof[k].mean, d[k].mean, bytes);
+        KM_D2H(c, prof[k].std, d[k].std, bytes);
+        any = true;
+    }
+    if (any) KM_FLUSH(c);
     return KM_OK;
 }
 

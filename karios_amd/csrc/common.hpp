@@ -197,6 +197,12 @@ enum km_slot {
     WS_AC_KEYS0,    //   order keys of the four columns
     WS_AC_KEYS1,    //   ... the sort's second buffer
     WS_CL_COLS,     // k_clip.hip: the working columns dx | dy | row name | new label of every unit of a clip launch
+    WS_RP_STATE,    // api_prep.hip (display range): the select's state (k_report.hip) and the result block
+    WS_RP_KEYS0,    // api_score.hip (mean profiles): (group key << 32 | row) of one profile
+    WS_RP_KEYS1,    //   ... the sort's second buffer, then the gathered values and the group heads
+    WS_RP_FLAG,     //   head flags and their exclusive scan; the counts of every profile of the call
+    WS_RP_SCAN,     //   tile sums of that scan
+    WS_RP_IO,       //   columns and outputs of the host-API form
     WS_COUNT
 };
 

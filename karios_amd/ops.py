@@ -1177,3 +1177,167 @@ def sigma_clip(dx, dy, ctx: Context | None = None, return_rounds: bool = False):
     (klt.py:52-71).  numpy in / numpy out, or device tensors in / a device tensor out; `return_rounds`: (indices, rounds)."""
     keep, rounds = sigma_clip_batch([(dx, dy)], ctx)[0]
     return (keep, rounds) if return_rounds else keep
+
+
+# ---- the report's numbers (csrc/api_prep.hip km_display_range, csrc/api_score.hip km_mean_profiles, k_report.hip) -------------------
+DISPLAY_MAX_NO_VALUES = _lib.DISPLAY_MAX_NO_VALUES
+PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = _lib.PROFILE_MAX, _lib.PROFILE_MAX_ROWS, _lib.PROFILE_MAX_BIN
+
+
+class DisplayRange:
+    """Result of `display_range`: `values` one per percent (`v_min` the first, `v_max` the last) with the value and type
+    np.percentile returns - or, when no pixel is valid, np.nanmin / np.nanmax of the raster; `n_valid`, `n_invalid`; `raster_min` /
+    `raster_max` in the raster's type (a zero as +0.0, NaN for a raster of nothing but NaN)."""
+
+    def __init__(self, values, n_valid, n_invalid, raster_min, raster_max):
+        self.values, self.n_valid, self.n_invalid, self.raster_min, self.raster_max = values, n_valid, n_invalid, raster_min, raster_max
+        self.v_min, self.v_max = (values[0], values[-1]) if len(values) else (None, None)
+
+
+def _lerp_as_numpy(v0, v1, vi, n, dtype):
+    """np.percentile's interpolation between its two neighbours -> one scalar per quantile, as numpy returns them: float64 through
+    `lerp_linear` for the integer types; for float32 every step in float32, the virtual index included."""
+    if np.dtype(dtype) != np.float32:
+        return list(lerp_linear(v0, v1, vi, n, dtype))
+    f32 = np.float32
+    out = []
+    with np.errstate(all="ignore"):
+        for a, b, v in zip(np.asarray(v0, np.float64).astype(f32), np.asarray(v1, np.float64).astype(f32), np.asarray(vi, np.float64).astype(f32)):
+            prev = f32(-1) if v >= n - 1 else np.floor(v)
+            gamma = f32(v - prev)
+            diff = f32(b - a)
+            out.append(f32(b - f32(diff * f32(f32(1) - gamma))) if gamma >= 0.5 else f32(a + f32(diff * gamma)))
+    return out
+
+
+def _display_range_lists(no_values, percents):
+    values = [] if no_values is None else [float(v) for v in no_values]
+    if len(values) > DISPLAY_MAX_NO_VALUES:
+        raise ValueError(f"display_range: {len(values)} DN values (at most {DISPLAY_MAX_NO_VALUES})")
+    pp = [float(p) for p in percents]
+    if any(not 0 <= p <= 100 for p in pp):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    return values, pp
+
+
+def display_range(arr, mask=None, no_values=None, nodata=None, percents=(0.5, 99.5), ctx: Context | None = None) -> DisplayRange:
+    """The display range of OverviewPlot._plot_image (report/overview_plot.py:134-194) of a 2-D uint8 / uint16 / int16 / float32
+    raster: np.percentile(valid, p) for every p of `percents`, valid = the pixels that are finite, not zero and not invalid;
+    invalid = `mask == 0` (optional uint8 mask of the raster's shape) | np.isin(arr, no_values) (at most 16 DN values) |
+    arr == nodata.  Without a valid pixel the range is np.nanmin / np.nanmax of the raster (two percents).  Raster and mask are both
+    numpy arrays or both torch tensors on the context's device (rows contiguous; windows of wider buffers are fine, each with its own
+    pitch).  A Python-number `nodata` compares with a float32 raster in float32 as numpy's does, an np.float64 in float64."""
+    values, pp = _display_range_lists(no_values, percents)
+    if _on_device(arr):
+        import torch
+        if arr.dim() != 2 or (arr.shape[1] > 1 and arr.stride(1) != 1):
+            raise ValueError("display_range: expected a 2-D tensor with contiguous rows")
+        dt = _torch_np_dtype(arr)
+        H, W = int(arr.shape[0]), int(arr.shape[1])
+        stride = int(arr.stride(0)) if H > 1 else W
+        img_arg, mask_arg, mstride = C.c_void_p(arr.data_ptr()), None, 0
+        if mask is not None:
+            if not _on_device(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or (W > 1 and mask.stride(1) != 1):
+                raise ValueError("display_range: the mask must be a uint8 tensor of the raster's shape with contiguous rows")
+            mask_arg, mstride = C.c_void_p(mask.data_ptr()), (int(mask.stride(0)) if H > 1 else W)
+        what = "km_display_range_dev"
+    else:
+        a = as_image(arr)
+        dt = a.dtype
+        H, W = a.shape
+        stride = row_stride(a)
+        img_arg, mask_arg, mstride = ptr(a), None, 0
+        if mask is not None:
+            m = np.asarray(mask)
+            if m.shape != a.shape:
+                raise ValueError("display_range: mask shape differs from the raster's")
+            m = as_image(m if m.dtype == np.uint8 else (m != 0).astype(np.uint8))
+            mask_arg, mstride = ptr(m), row_stride(m)
+        what = "km_display_range"
+    if dt not in PREP_DTYPES:
+        raise KariosHipError(f"display_range: unsupported pixel type {dt} (uint8, uint16, int16, float32)")
+    if H < 1 or W < 1:
+        raise ValueError("display_range: empty raster")
+    c = _ctx(ctx)
+    if _on_device(arr):
+        import torch
+        torch.cuda.synchronize(arr.device)
+    return _display_range_call(c, what, img_arg, dt, H, W, stride, mask_arg, mstride, values, nodata, pp)
+
+
+def _display_range_call(c, what, img_arg, dt, H, W, stride, mask_arg, mstride, values, nodata, pp):
+    """The library call behind `display_range` and `ResidentPair.display_ranges`: checked arguments in, a `DisplayRange` out."""
+    if nodata is not None:
+        with np.errstate(over="ignore"):
+            nodata = float(np.float32(nodata)) if dt == np.float32 and type(nodata) in (int, float) else float(nodata)
+    # the quantile as np.percentile forms it: in float32 for a float32 raster
+    with np.errstate(all="ignore"):
+        q = np.array([float(np.true_divide(p, np.float32(100) if dt == np.float32 else 100)) for p in pp], np.float64)
+    res = _lib.DisplayRangeResult()
+    v0, v1, vi = np.full(q.size, np.nan), np.full(q.size, np.nan), np.full(q.size, np.nan)
+    nv = np.array(values, np.float64)
+    pd = C.POINTER(C.c_double)
+    c.check(getattr(c.lib, what)(c.handle, img_arg, _lib._DTYPES[dt], H, W, stride, mask_arg, mstride,
+                                 C.byref(C.c_double(nodata)) if nodata is not None else None, nv.ctypes.data_as(pd) if nv.size else None, nv.size,
+                                 q.size, q.ctypes.data_as(pd), C.byref(res), v0.ctypes.data_as(pd), v1.ctypes.data_as(pd), vi.ctypes.data_as(pd)), what)
+    with np.errstate(all="ignore"):
+        rmin, rmax = dt.type(res.raster_min), dt.type(res.raster_max)
+    n = int(res.n_valid)
+    if n > 0:
+        out = _lerp_as_numpy(v0, v1, vi, n, dt)
+    else:
+        out = [rmin, rmax] if q.size == 2 else [dt.type(np.nan) if dt.kind == "f" else None] * q.size
+    return DisplayRange(out, n, int(res.n_invalid), rmin, rmax)
+
+
+class ProfileColumns:
+    """One profile of `mean_profiles`: `key` (float32, the groups' np.floor_divide(positions, bin_size), ascending), `position`
+    (int32, the reference's groups_positions), `count` (int32 rows whose value is not NaN), `mean` and `std` (float32); numpy arrays,
+    or device tensors for device input."""
+
+    def __init__(self, key, position, count, mean, std):
+        self.key, self.position, self.count, self.mean, self.std = key, position, count, mean, std
+
+
+def mean_profiles(profiles, ctx: Context | None = None):
+    """`mean_profile` (report/commons.py:49-71) of 1 .. 8 profiles in one call: `profiles` is a sequence of (values, positions,
+    bin_size) with float32 columns of one length (at most 2^20 rows; all numpy or all device tensors) and 1 <= bin_size <= 2^24
+    -> a list of `ProfileColumns`.  ValueError when a group's position lies outside int32, where numpy's cast is not defined."""
+    profiles = [tuple(p) for p in profiles]
+    if not 1 <= len(profiles) <= PROFILE_MAX:
+        raise ValueError(f"mean_profiles: {len(profiles)} profiles (1 .. {PROFILE_MAX} per call)")
+    cols = []
+    for values, positions, _bin in profiles:
+        cols += [values, positions]
+    dev, cols, n = _f32_columns(tuple(cols), "mean_profiles", "values and positions")
+    if n > PROFILE_MAX_ROWS:
+        raise ValueError(f"mean_profiles: {n} rows (at most 2^20)")
+    bins = []
+    for _v, _p, b in profiles:
+        if int(b) != b or not 1 <= int(b) <= PROFILE_MAX_BIN:
+            raise ValueError(f"mean_profiles: bin size {b} (an integer, 1 .. 2^24)")
+        bins.append(int(b))
+    c = _ctx(ctx)
+    k = len(profiles)
+    recs = (_lib.Profile * k)()
+    outs = []
+    if dev:
+        import torch
+        torch.cuda.synchronize(cols[0].device)
+    for i in range(k):
+        if dev:
+            import torch
+            o = [torch.empty(n, dtype=t, device=cols[0].device) for t in (torch.float32, torch.int32, torch.int32, torch.float32, torch.float32)]
+        else:
+            o = [np.empty(n, t) for t in (np.float32, np.int32, np.int32, np.float32, np.float32)]
+        outs.append(o)
+        args = _col_args(dev, (cols[2 * i], cols[2 * i + 1]) + tuple(o), n)
+        r = recs[i]
+        r.values, r.positions, r.key, r.position, r.count, r.mean, r.std = [C.cast(a, C.c_void_p).value if a is not None else None for a in args]
+        r.bin_size = bins[i]
+    groups, oor = (C.c_int32 * k)(), (C.c_int32 * k)()
+    what = "km_mean_profiles_dev" if dev else "km_mean_profiles"
+    c.check(getattr(c.lib, what)(c.handle, n, k, recs, groups, oor), what)
+    if any(oor):
+        raise ValueError(f"mean_profiles: {sum(oor)} group position(s) outside int32")
+    return [ProfileColumns(*(a[:groups[i]] for a in outs[i])) for i in range(k)]
