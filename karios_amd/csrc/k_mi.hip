@@ -8,6 +8,7 @@
 // maximum folded into the last bin.  One wavefront per key point; the joint histogram lives in LDS (ds atomics).
 // Key-point rounding / bounds rules are those of the ZNCC kernel (`_compute_mutual_info` = `_compute_zncc`).
 #include "common.hpp"
+#include "mi_math.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -98,17 +99,23 @@ __global__ __launch_bounds__(256) void mi_kernel(const T *__restrict__ ref, cons
     // chips -> registers, per-chip min / max
     double va[MI_PER_LANE], vb[MI_PER_LANE];
     double mn1 = INFINITY, mx1 = -INFINITY, mn2 = INFINITY, mx2 = -INFINITY;
+    float poison = 0.0f;
 #pragma unroll
     for (int i = 0; i < MI_PER_LANE; i++) {
         const int idx = i * 64 + lane;
         va[i] = 0; vb[i] = 0;
         if (idx < MI_NPX) {
             const int r = idx / MI_CHIP, cx = idx - r * MI_CHIP;
-            va[i] = (double)ref[(size_t)(Y0 - MI_MARGIN + r) * sref + (X0 - MI_MARGIN + cx)];
-            vb[i] = (double)mon[(size_t)(Y1 - MI_MARGIN + r) * smon + (X1 - MI_MARGIN + cx)];
+            const float pa = (float)ref[(size_t)(Y0 - MI_MARGIN + r) * sref + (X0 - MI_MARGIN + cx)];
+            const float pb = (float)mon[(size_t)(Y1 - MI_MARGIN + r) * smon + (X1 - MI_MARGIN + cx)];
+            va[i] = (double)pa; vb[i] = (double)pb;
             mn1 = fmin(mn1, va[i]); mx1 = fmax(mx1, va[i]); mn2 = fmin(mn2, vb[i]); mx2 = fmax(mx2, vb[i]);
+            poison = __fmaf_rn(pa, 0.0f, __fmaf_rn(pb, 0.0f, poison));   // 0 x (NaN or an infinity) = NaN, and it stays: one float32 FMA per pixel
         }
     }
+    // a NaN or an infinity in either chip: np.histogram2d raises ("autodetected range ... is not finite"), the reference catches it and
+    // scores the key point NaN (mutual_info_service.py:126-130, zncc_service.py:283-287) - fmin / fmax would drop a NaN silently
+    if (!__all(poison == poison)) { give_up(); return; }
     mn1 = mi_wave_min(mn1); mx1 = mi_wave_max(mx1); mn2 = mi_wave_min(mn2); mx2 = mi_wave_max(mx2);
     if (mn1 == mx1) { mn1 -= 0.5; mx1 += 0.5; }   // numpy _get_outer_edges for a constant sample
     if (mn2 == mx2) { mn2 -= 0.5; mx2 += 0.5; }
@@ -241,28 +248,17 @@ __device__ __forceinline__ void mi_int_item(const T *__restrict__ ref, const T *
         mn2 = min(mn2, __shfl_xor(mn2, o)); mx2 = max(mx2, __shfl_xor(mx2, o));
     }
     const int R1 = mx1 - mn1, R2 = mx2 - mn2;
-    // floor(32 d / R) for 0 <= d <= R < 2^16 by ONE multiplication: with L = ceil(log2 R), s = 21 + L and M = ceil(2^s / R),
-    // M R = 2^s + e with 0 <= e < R <= 2^L, hence 32 d M / 2^s = 32 d / R + 32 d e / (R 2^s) and the excess is below
-    // 2^21 2^L / (R 2^s) = 1 / R: it cannot carry a quotient with fractional part <= (R - 1) / R over the next integer.  M <= 2^22, the
-    // product d M < 2^38: a 64-bit multiply-add and a 64-bit shift by s - 5.  (M from a float64 division: 2^s / R is an integer only
-    // for R a power of two, where the division is exact; otherwise it lies >= 1 / R from the integers, far beyond its 2^-31 error.)
-    auto magic = [](int R, unsigned &M, int &sh) {
-        const int L = R > 1 ? 32 - __clz(R - 1) : 0;
-        M = R ? (unsigned)ceil(ldexp(1.0, 21 + L) / (double)R) : 0u;
-        sh = 21 + L - 5;
-    };
+    // floor(32 d / R) for 0 <= d <= R < 2^16 by ONE multiplication with a per-chip constant: mi_math.hpp (the CPU suite walks every (R, d))
     unsigned M1, M2;
     int sh1, sh2;
-    magic(R1, M1, sh1); magic(R2, M2, sh2);
+    mi::magic(R1, M1, sh1); mi::magic(R2, M2, sh2);
     LK_LIKE_SYNC();
     if (col_on) {
 #pragma unroll
         for (int i = 0; i < MI_CHIP; i++) {
             const unsigned d1 = (pk[i] & 0xffffu) - (unsigned)mn1, d2 = (pk[i] >> 16) - (unsigned)mn2;
-            const int q1 = (int)(unsigned)(((unsigned long long)d1 * M1) >> sh1), q2 = (int)(unsigned)(((unsigned long long)d2 * M2) >> sh2);
-            // the maximum folds into the last bin (numpy's on_edge rule); a constant chip: numpy widens the range to [v - 0.5, v + 0.5],
-            // the samples sit in the middle bin 16
-            const int b1 = R1 ? min(q1, MI_BINS - 1) : MI_BINS / 2, b2 = R2 ? min(q2, MI_BINS - 1) : MI_BINS / 2;
+            // (the maximum folds into the last bin, a constant chip sits in bin 16: mi::bin_of)
+            const int b1 = mi::bin_of(mi::quotient(d1, M1, sh1), R1), b2 = mi::bin_of(mi::quotient(d2, M2, sh2), R2);
             atomicAdd(&hist[b1 * MI_BINS + b2], 1u);
         }
     }
