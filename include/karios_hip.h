@@ -481,6 +481,14 @@ int km_find_transform_ecc_dev(km_ctx *ctx, const void *d_template_image, const v
                               ptrdiff_t template_stride, int hd, int wd, ptrdiff_t input_stride, const uint8_t *d_mask,
                               ptrdiff_t mask_stride, float map[9], int max_iter, double eps, int gauss_filt_size, double *cc,
                               int *iterations);
+/* For tests: the intermediates of km_find_transform_ecc at one map (host pointers only).  Runs the same set-up on the same image
+ * arguments, then the kernels of one iteration at map (float32 3 x 3, read only), and copies out: t_blur = the blurred template,
+ * hs x ws float32; plane = hd x wd x 4 float32 {blurred input, gx * pre-mask, gy * pre-mask, pre-mask}; sums = the 66 fp64 sums the
+ * iteration's host algebra works on: N, S(mI), S(mI^2), S(mT), S(mT^2), S(mTI), the 36 Hessian terms (upper triangle, row by
+ * row), S(J_k I), S(J_k m), S(J_k m T), k = 0 .. 7.  Bitwise identical from call to call. */
+int km_ecc_stages(km_ctx *ctx, const void *template_image, const void *input_image, int dtype, int hs, int ws,
+                  ptrdiff_t template_stride, int hd, int wd, ptrdiff_t input_stride, const uint8_t *mask, ptrdiff_t mask_stride,
+                  const float map[9], float *t_blur, float *plane, double *sums);
 /* _refine_with_ecc for n initial 3 x 3 fp64 matrices (mon -> ref) on uint8 mon (hm x wm) / ref (hr x wr): mon pre-warped onto ref's
  * canvas with (float)init, candidates with fewer than 1000 non-zero pixels skipped, ECC on the Sobel magnitudes (the template's
  * computed once) from the identity with mask = pre-warped mon > 0.  Per candidate (host arrays): final = residual @ init (fp64,

@@ -180,6 +180,7 @@ SIGNATURES = {
     "km_sobel_magnitude_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp]),
     "km_find_transform_ecc": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _sz, _vp, _sz, _vp, _i, _d, _i, _pd, _pi]),
     "km_find_transform_ecc_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _sz, _vp, _sz, _vp, _i, _d, _i, _pd, _pi]),
+    "km_ecc_stages": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _i, _i, _sz, _vp, _sz, _vp, _vp, _vp, _pd]),
     "km_refine_ecc_candidates": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "km_refine_ecc_candidates_dev": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _sz, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "km_order_statistics": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _i, _pd, C.POINTER(C.c_int64), _pd, _pd, _pd]),

@@ -360,6 +360,36 @@ int km_find_transform_ecc(km_ctx *c, const void *tmpl, const void *in, int dtype
     return ecc_loop(c, d_t, hs, ws, d_plane, hd, wd, map, max_iter, eps, cc, iters);
 }
 
+// For tests: what km_find_transform_ecc's first iteration at `map` works on.  The same ecc_prepare, one ka_ecc_sums, three copies out.
+int km_ecc_stages(km_ctx *c, const void *tmpl, const void *in, int dtype, int hs, int ws, ptrdiff_t st, int hd, int wd, ptrdiff_t si,
+                  const uint8_t *mask, ptrdiff_t sm, const float map[9], float *t_blur, float *plane, double *sums)
+{
+    int rc, no_iters = 0;
+    double no_cc = 0.0;
+    if ((rc = begin_call(c)) || (rc = ecc_args(c, dtype, hs, ws, hd, wd, 0, 5, map, &no_cc, &no_iters)) ||
+        (rc = check_image(c, tmpl, hs, ws, st, "ecc_stages")) || (rc = check_image(c, in, hd, wd, si, "ecc_stages")) ||
+        (mask && (rc = check_image(c, mask, hd, wd, sm, "ecc_stages mask"))))
+        return rc;
+    if (!t_blur || !plane || !sums) return km_fail(c, KM_E_ARG, "ecc_stages: null output");
+    const size_t es = km_dtype_size(dtype);
+    void *d_t_raw, *d_i_raw, *d_m = nullptr;
+    if ((rc = upload_image(c, WS_RAW_A, tmpl, es, hs, ws, st, &d_t_raw)) || (rc = upload_image(c, WS_RAW_B, in, es, hd, wd, si, &d_i_raw)) ||
+        (mask && (rc = upload_image(c, WS_MASK_IN, mask, 1, hd, wd, sm, &d_m))))
+        return rc;
+    float *d_t;
+    float4 *d_plane;
+    if ((rc = ecc_prepare(c, d_t_raw, d_i_raw, dtype, hs, ws, ws, hd, wd, wd, (const uint8_t *)d_m, wd, &d_t, &d_plane))) return rc;
+    double *d_part = (double *)km_ws(c, WS_AL_PART, ((size_t)KA_ECC_MAX_BLOCKS + 1) * KA_NSUM * sizeof(double));
+    if (!d_part) return KM_E_NOMEM;
+    double *d_sums = d_part + (size_t)KA_ECC_MAX_BLOCKS * KA_NSUM;
+    if ((rc = ka_ecc_sums(c, d_t, hs, ws, d_plane, hd, wd, map, d_part, d_sums))) return rc;
+    KM_D2H(c, t_blur, d_t, (size_t)hs * ws * sizeof(float));
+    KM_D2H(c, plane, d_plane, (size_t)hd * wd * sizeof(float4));
+    KM_D2H(c, sums, d_sums, KA_NSUM * sizeof(double));
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
 int km_refine_ecc_candidates_dev(km_ctx *c, const uint8_t *d_mon, int hm, int wm, ptrdiff_t smon, const uint8_t *d_ref, int hr, int wr,
                                  ptrdiff_t sref, int n, const double *inits, int max_iter, double eps, double *final_out, float *residual_out,
                                  double *cc_out, int *iters_out, int64_t *valid_out, int *status_out)

@@ -2,7 +2,8 @@
 // cv2.findTransformECC(MOTION_HOMOGRAPHY).  The arithmetic is restated in numpy in tests/align_restatement.py, which is the
 // definition these kernels are held to bit for bit (warps, Sobel) or to fp64 summation order
 // (the 66 sums of an ECC iteration; every per-pixel product is exact in fp64, only the order of the additions differs).  The
-// Gaussian, gradient and pre-mask kernels follow the restatement's operation order too; the tests reach them through ECC only.
+// Gaussian, gradient and pre-mask kernels follow the restatement's operation order too and are held to it bit for bit through
+// km_ecc_stages (tests/test_gpu_align_stages.py).
 #include "k_align.hpp"
 
 #include <math.h>

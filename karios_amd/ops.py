@@ -355,21 +355,40 @@ def find_transform_ecc(template, image, warp, criteria, input_mask=None, gauss_f
     """cv2.findTransformECC(template, image, warp, MOTION_HOMOGRAPHY, criteria, inputMask, gaussFiltSize) -> (cc, warp float32).
     Raises KariosHipError with code E_NO_CONVERGENCE where OpenCV raises StsNoConv."""
     c = _ctx(ctx)
+    images, mp = _ecc_images(template, image, warp, input_mask, "find_transform_ecc")
+    n_it, eps = _criteria(criteria)
+    cc, it = C.c_double(), C.c_int()
+    c.check(c.lib.km_find_transform_ecc(c.handle, *images, ptr(mp), n_it, eps, int(gauss_filt_size), C.byref(cc), C.byref(it)),
+            "km_find_transform_ecc")
+    return (cc.value, mp, it.value) if return_iterations else (cc.value, mp)
+
+
+def _ecc_images(template, image, warp, input_mask, who):
+    """-> (the image arguments km_find_transform_ecc and km_ecc_stages share, the float32 map)"""
     t, a = as_image(template), as_image(image)
     if t.dtype != a.dtype or t.dtype not in (np.uint8, np.float32):
-        raise KariosHipError("find_transform_ecc: both images uint8 or both float32")
+        raise KariosHipError(f"{who}: both images uint8 or both float32")
     mp = np.array(np.asarray(warp).reshape(3, 3), np.float32)
     m = None
     if input_mask is not None:
         m = as_image(np.asarray(input_mask).astype(np.uint8, copy=False))
         if m.shape != a.shape:
-            raise KariosHipError("find_transform_ecc: mask shape differs from the input's")
-    n_it, eps = _criteria(criteria)
-    cc, it = C.c_double(), C.c_int()
-    c.check(c.lib.km_find_transform_ecc(c.handle, ptr(t), ptr(a), dtype_code(t), t.shape[0], t.shape[1], row_stride(t), a.shape[0], a.shape[1],
-                                        row_stride(a), ptr(m) if m is not None else None, row_stride(m) if m is not None else 0, ptr(mp),
-                                        n_it, eps, int(gauss_filt_size), C.byref(cc), C.byref(it)), "km_find_transform_ecc")
-    return (cc.value, mp, it.value) if return_iterations else (cc.value, mp)
+            raise KariosHipError(f"{who}: mask shape differs from the input's")
+    # (ndarray.ctypes.data_as keeps its array alive: the pointers outlive this function's locals)
+    return (ptr(t), ptr(a), dtype_code(t), t.shape[0], t.shape[1], row_stride(t), a.shape[0], a.shape[1], row_stride(a),
+            ptr(m), row_stride(m) if m is not None else 0), mp
+
+
+def ecc_stages(template, image, warp, input_mask=None, ctx: Context | None = None):
+    """For tests: the intermediates of find_transform_ecc at the map `warp` -> (t_blur float32 [hs, ws], plane float32 [hd, wd, 4] =
+    {blurred input, gx * pre-mask, gy * pre-mask, pre-mask}, sums float64 [66], the sums one iteration's host algebra works on)."""
+    c = _ctx(ctx)
+    images, mp = _ecc_images(template, image, warp, input_mask, "ecc_stages")
+    hs, ws, hd, wd = images[3], images[4], images[6], images[7]
+    t_blur, plane, sums = np.empty((hs, ws), np.float32), np.empty((hd, wd, 4), np.float32), np.empty(66, np.float64)
+    c.check(c.lib.km_ecc_stages(c.handle, *images, ptr(mp), ptr(t_blur), ptr(plane), sums.ctypes.data_as(C.POINTER(C.c_double))),
+            "km_ecc_stages")
+    return t_blur, plane, sums
 
 
 def refine_ecc_candidates(mon_u8, ref_u8, inits, max_iters=200, eps=1e-6, ctx: Context | None = None):

@@ -230,9 +230,10 @@ def ecc_jacobian(gxw, gyw, hs, ws, mp):
     return [g1 * X, g2 * X, temp * X, g1 * Y, g2 * Y, temp * Y, g1, g2]
 
 
-def ecc_sums(t, img, gx, gy, pm, mp):
-    """The 66 fp64 sums of one iteration: N, S(mI), S(mI^2), S(mT), S(mT^2), S(mTI), the 36 Hessian terms (upper triangle,
-    row by row), S(J_k I), S(J_k m), S(J_k m T).  Every per-pixel product is exact in fp64."""
+def ecc_terms(t, img, gx, gy, pm, mp):
+    """The per-pixel terms (66 fp64 hs x ws arrays) of the sums of one iteration: m, mI, mI^2, mT, mT^2, mTI, the 36 Hessian
+    terms J_k J_l (upper triangle, row by row), J_k I, J_k m, J_k m T.  Every product is exact in fp64: m is 0 or 1, the rest
+    are products of two float32 values."""
     hs, ws = t.shape
     M = np.asarray(mp, np.float32).astype(np.float64)
     dsz = (ws, hs)
@@ -242,14 +243,19 @@ def ecc_sums(t, img, gx, gy, pm, mp):
     m = warp_perspective(pm, M, dsz, INTER_NEAREST | WARP_INVERSE_MAP, 0.0).astype(np.float64)
     J = [j.astype(np.float64) for j in ecc_jacobian(gxw, gyw, hs, ws, np.asarray(mp, np.float32))]
     T = t.astype(np.float64)
-    s = [m.sum(), (m * Iw).sum(), (m * Iw * Iw).sum(), (m * T).sum(), (m * T * T).sum(), (m * T * Iw).sum()]
+    s = [m, m * Iw, m * Iw * Iw, m * T, m * T * T, m * T * Iw]
     for k in range(8):
         for l in range(k, 8):
-            s.append((J[k] * J[l]).sum())
-    s += [(J[k] * Iw).sum() for k in range(8)]
-    s += [(J[k] * m).sum() for k in range(8)]
-    s += [(J[k] * m * T).sum() for k in range(8)]
-    return np.array(s, np.float64)
+            s.append(J[k] * J[l])
+    s += [J[k] * Iw for k in range(8)]
+    s += [J[k] * m for k in range(8)]
+    s += [J[k] * m * T for k in range(8)]
+    return s
+
+
+def ecc_sums(t, img, gx, gy, pm, mp):
+    """The 66 fp64 sums of one iteration (numpy's summation order), in ecc_terms' order."""
+    return np.array([term.sum() for term in ecc_terms(t, img, gx, gy, pm, mp)], np.float64)
 
 
 def lu_inv_f32(A):

@@ -202,3 +202,164 @@ def test_prior_from_georefs():
     assert _prior_from_georefs(Img("x", SR(False), 10, -10, 0, 0), ref) is None
     assert _prior_from_georefs(Img("x", SR(None), 10, -10, 0, 0), ref) is None
 
+
+
+# ---- the inputs of the stage and degenerate-warp GPU tests (tests/align_cases.py) do what they are there for ------------------------
+import align_cases as A  # noqa: E402
+
+
+@pytest.mark.parametrize("name", list(A.warp_cases()))
+def test_warp_case_reaches_the_rule_it_is_listed_for(name):
+    A.check_warp_case(name)
+
+
+def test_special_float_source_holds_every_special_value():
+    a = A.warp_source((33, 41), np.float32, "special")
+    tiny = np.finfo(np.float32).tiny
+    assert np.isnan(a).any() and (a == np.inf).any() and (a == -np.inf).any() and (a == A.FLT_MAX).any() and (a == -A.FLT_MAX).any()
+    assert ((a != 0) & (np.abs(a) < tiny)).any() and (np.signbit(a) & (a == 0)).any() and a.strides[0] > a.shape[1] * 4
+
+
+@pytest.mark.parametrize("shapes", [s for s in A.STAGE_SHAPES if min(s[1]) >= A.EDGE_MASK_MIN], ids=str)
+def test_stage_mask_hits_both_sides_of_the_premask_rounding(shapes):
+    m = A.stage_mask(shapes[1])
+    valid = m[m > 0]
+    assert (m == 0).any() and not m[0].any() and not m[:, :2].any() and ((valid != 255).any() and len(np.unique(valid)) > 2)
+    blur = R.gauss5((m > 0).astype(np.float32))
+    pm = R.ecc_premask(m, m.shape)
+    one, zero = A.edge_sites(shapes[1])
+    assert blur[one] == np.float32(244 / 256) and pm[one] == 1 and blur[zero] == np.float32(243 / 256) and pm[zero] == 0
+    k = np.float32(0.5 / 0.95)
+    assert np.float32(243 / 256) * k < 0.5 < np.float32(244 / 256) * k       # no value of the n / 256 grid lies between them
+    assert pm.min() == 0 and pm.max() == 1 and pm.dtype == np.uint8
+
+
+@pytest.mark.parametrize("shapes", A.LOOP_SHAPES, ids=str)
+def test_loop_cases_converge_inside_the_iteration_cap(shapes):
+    cc, mp, it = A.loop_reference(shapes)
+    assert 1 < it < 200 and cc > 0.9
+
+
+def test_step_cases_are_what_they_are_named():
+    for name, (t, i, mask, mp) in A.step_cases().items():
+        s = R.ecc_sums(*R.ecc_prepare(t, i, mask), mp)
+        H = np.zeros((8, 8), np.float32)
+        H[np.triu_indices(8)] = s[6:42]
+        H = H + np.triu(H, 1).T
+        singular = not R.lu_inv_f32(H).any()
+        if name in ("anticorrelated", "flat"):
+            with pytest.raises(R.EccNoConvergence, match="minimized" if name == "anticorrelated" else "NaN"):
+                R.ecc_step(s, mp)
+        else:
+            rho, new = R.ecc_step(s, mp)
+            assert 0.5 < rho < 1 and np.array_equal(new, np.asarray(mp, np.float32)) == (name == "stripes")
+        assert singular == (name in ("flat", "stripes")), name
+
+
+SUMS_HOST_SHAPES = [A.STAGE_SHAPES[6], A.STAGE_SHAPES[7]]
+
+
+@pytest.mark.parametrize("name", ["identity", "subpixel", "outside", "den_sign"])
+@pytest.mark.parametrize("shapes", SUMS_HOST_SHAPES, ids=str)
+def test_numpy_order_sums_lie_inside_the_exact_sum_bound_and_one_pixel_does_not(shapes, name):
+    exact, bound, numpy_order = A.exact_sums(shapes, name)
+    assert np.isfinite(exact).all() and (np.abs(numpy_order - exact) <= bound).all()
+    assert (np.abs(numpy_order - exact) <= 0.05 * bound).all()               # far inside: the bound is no tight fit to one order
+    terms = R.ecc_terms(*A.prepared(shapes, "float32", True), A.sums_maps(shapes)[name])
+    n_valid = int(exact[0])
+    (hs, ws), (hd, wd) = shapes
+    assert n_valid == terms[0].sum()
+    assert 0 < n_valid < 40 if name == "outside" else n_valid > (100 if name == "den_sign" else hs * ws // 4)
+    if name == "den_sign":
+        den = A.jacobian_den(shapes, A.sums_maps(shapes)[name])
+        assert (den > 0).any() and (den < 0).any() and (den != 0).all()
+    for k in range(66):                                                        # leaving one median pixel out is far outside the bound
+        mag = np.abs(terms[k][terms[k] != 0])
+        assert mag.size and np.median(mag) > 1e4 * bound[k], (k, np.median(mag), bound[k])
+
+
+def test_wide_input_sums_case_counts_pixels_at_the_saturated_position():
+    shapes = A.WIDE_INPUT_SHAPE
+    (hs, ws), (hd, wd) = shapes
+    mp = A.sums_maps(shapes)["sat_short"]
+    sx, sy, fx, fy = R.warp_taps(mp.astype(np.float64), hs, ws, True)
+    nx, ny = R.warp_taps(mp.astype(np.float64), hs, ws, False)
+    assert wd > 32768 and (sx == 32767).sum() == (nx == 32767).sum() == hs * (ws - 34) and (sx == -32768).any()
+    exact, bound, numpy_order = A.exact_sums(shapes, "sat_short")
+    assert exact[0] == (sx >= 0).sum() == hs * (ws - 33) and (np.abs(numpy_order - exact) <= bound).all()    # N: column 33 and the saturated ones
+    terms = R.ecc_terms(*A.prepared(shapes, "float32", False), mp)
+    assert (terms[1][sx == 32767] != 0).all()                                 # ... each with the image's value at column 32767
+
+
+def test_ecc_sums_is_the_numpy_sum_of_ecc_terms():
+    shapes = A.STAGE_SHAPES[5]
+    parts = A.prepared(shapes, "float32", True)
+    mp = A.sums_maps(shapes)["subpixel"]
+    terms = R.ecc_terms(*parts, mp)
+    assert len(terms) == 66 and all(t.shape == shapes[0] and t.dtype == np.float64 for t in terms)
+    np.testing.assert_array_equal(R.ecc_sums(*parts, mp), [t.sum() for t in terms])
+    m, T = terms[0], parts[0].astype(np.float64)
+    assert set(np.unique(m)) <= {0.0, 1.0}
+    np.testing.assert_array_equal(terms[3], m * T)
+    np.testing.assert_array_equal(terms[4], m * T * T)
+
+
+def _pad101(a, r):
+    for axis in (0, 1):
+        pad = [(0, 0), (0, 0)]
+        pad[axis] = (r, r)
+        a = np.pad(a, pad, mode="reflect" if a.shape[axis] > 1 else "edge")
+    return a
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 9), (9, 1), (2, 2), (3, 2), (5, 67), (13, 29)])
+def test_gauss5_is_the_5x5_binomial_correlation_with_reflect_101(shape):
+    """on integer images every float32 step of R.gauss5 is exact, so it must equal the plain fp64 correlation"""
+    a = np.random.default_rng(shape[0] * 100 + shape[1]).integers(0, 256, shape).astype(np.float64)
+    k = np.array([1, 4, 6, 4, 1], np.float64) / 16
+    p = _pad101(a, 2)
+    exp = np.zeros(shape)
+    for dy in range(5):
+        for dx in range(5):
+            exp += k[dy] * k[dx] * p[dy:dy + shape[0], dx:dx + shape[1]]
+    got = R.gauss5(a.astype(np.float32))
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got.astype(np.float64), exp)
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (1, 9), (9, 1), (2, 2), (3, 2), (13, 29)])
+def test_ecc_gradients_are_plain_central_differences_times_the_premask(shape):
+    rng = np.random.default_rng(shape[0] * 10 + shape[1])
+    a = (rng.random(shape) * 255).astype(np.float32)
+    pm = (rng.random(shape) < 0.7).astype(np.uint8)
+    p = _pad101(a.astype(np.float64), 1)
+    H, W = shape
+    ex = (p[1:1 + H, 2:2 + W] - p[1:1 + H, 0:W]) / 2 * pm        # exact in fp64, one rounding to float32
+    ey = (p[2:2 + H, 1:1 + W] - p[0:H, 1:1 + W]) / 2 * pm
+    gx, gy = R.ecc_gradients(a, pm)
+    assert gx.dtype == gy.dtype == np.float32
+    np.testing.assert_array_equal(gx, ex.astype(np.float32))
+    np.testing.assert_array_equal(gy, ey.astype(np.float32))
+
+
+def _plain_sobel_sq(img):
+    p = _pad101(np.asarray(img, np.int64), 1)
+    H, W = img.shape
+    s = lambda dy, dx: p[1 + dy:1 + dy + H, 1 + dx:1 + dx + W]   # noqa: E731
+    gx = (s(-1, 1) - s(-1, -1)) + 2 * (s(0, 1) - s(0, -1)) + (s(1, 1) - s(1, -1))
+    gy = (s(1, -1) - s(-1, -1)) + 2 * (s(1, 0) - s(-1, 0)) + (s(1, 1) - s(-1, 1))
+    return gx * gx + gy * gy
+
+
+def test_sobel_extreme_patterns_reach_the_largest_gradient_and_the_last_workgroup():
+    img, at = A.sobel_extreme()
+    sq = _plain_sobel_sq(img)
+    assert sq.max() == 1020 ** 2 + 510 ** 2 == sq[at] and set(np.unique(img)) == {0, 255}     # the largest gx^2 + gy^2 of 8-bit pixels
+    out = R.sobel_magnitude(img)
+    assert out[at] == 1.0 and out.max() == 1.0
+    np.testing.assert_array_equal(out, np.sqrt(sq.astype(np.float32)) / np.float32(np.sqrt(np.float32(sq.max()))))
+    last = A.sobel_last_pixel()
+    H, W = last.shape
+    sq = _plain_sobel_sq(last)
+    ys, xs = np.nonzero(sq)
+    assert ys.size and (ys >= (H - 1) // 4 * 4).all() and (xs >= (W - 1) // 64 * 64).all()     # only the last 4 x 64 workgroup sees it

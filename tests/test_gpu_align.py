@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import align_cases as A  # noqa: E402
 import align_restatement as R  # noqa: E402
 
 import ctypes as C  # noqa: E402
@@ -65,6 +66,51 @@ def test_warp_perspective_bit_identical(case, dtype):
                 _same(got, exp)
 
 
+def _same_but_nan(a, b):
+    """NaN at the same places (its payload and sign are not defined by IEEE arithmetic), every other element bitwise"""
+    assert a.dtype == b.dtype == np.float32 and a.shape == b.shape
+    np.testing.assert_array_equal(np.isnan(a), np.isnan(b))
+    ok = ~np.isnan(b)
+    np.testing.assert_array_equal(a.view(np.uint32)[ok], b.view(np.uint32)[ok])
+
+
+def _warp_both_ways(src, M, dsize, inverse_flags=(0, ops.WARP_INVERSE_MAP), same=_same):
+    for flags in (ops.INTER_LINEAR, ops.INTER_NEAREST):
+        for inv in inverse_flags:
+            for border in (0.0, 7.3, float("nan")):
+                got = ops.warp_perspective(src, M, dsize, flags | inv, border)
+                with np.errstate(all="ignore"):
+                    exp = R.warp_perspective(src, M, dsize, flags | inv, border)
+                (same if border == border or src.dtype == np.uint8 else _same_but_nan)(got, exp)
+
+
+@pytest.mark.parametrize("name", list(A.warp_cases()))
+@pytest.mark.parametrize("dtype", [np.uint8, np.float32])
+def test_warp_perspective_where_the_edge_rules_bite(name, dtype):
+    """W == 0 and W < 0, singular and all-zero matrices, positions beyond the int and the short range, non-finite entries, exact
+    ties on the 1/32 grid, taps astride the source's edges, tiny sources and destinations: tests/align_cases.py, each with the
+    condition it is there for (also asserted on the CPU in test_align_host.py)"""
+    A.check_warp_case(name)
+    (sH, sW), (dH, dW), M, inv, _ = A.warp_cases()[name]
+    _warp_both_ways(A.warp_source((sH, sW), dtype), M, (dW, dH), (inv,))
+
+
+@pytest.mark.parametrize("name", ["edges", "w_zero_row", "ties", "src_1x7"])
+def test_warp_perspective_float32_specials_and_uint8_full_scale(name):
+    (sH, sW), (dH, dW), M, inv, _ = A.warp_cases()[name]
+    _warp_both_ways(A.warp_source((sH, sW), np.float32, "special"), M, (dW, dH), (inv,), _same_but_nan)
+    _warp_both_ways(A.warp_source((sH, sW), np.uint8, "checker"), M, (dW, dH), (inv,))
+
+
+def test_warp_perspective_checkerboard_half_pixel_blend():
+    """0 / 255 at weights 16/32 x 16/32 and at every other fraction: the 8-bit blend's rounding at full scale"""
+    src = A.warp_source((40, 50), np.uint8, "checker")
+    for M in ([[1, 0, 0.5], [0, 1, 0.5], [0, 0, 1]], [[1 + 1 / 32, 0, -1.25], [0, 1 - 1 / 32, -0.75], [0, 0, 1]]):
+        exp = R.warp_perspective(src, np.array(M), (56, 44), R.INTER_LINEAR | R.WARP_INVERSE_MAP, 255.0)
+        assert (exp == 128).any() if M[0][0] == 1 else len(np.unique(exp)) > 30    # 127.5 rounds up; many fractions
+        _warp_both_ways(src, np.array(M, np.float64), (56, 44), (ops.WARP_INVERSE_MAP,))
+
+
 def test_warp_perspective_float32_matrix_and_dev_entry_point():
     import torch
     src = (np.random.default_rng(1).random((300, 400)) * 4000).astype(np.float32)
@@ -83,12 +129,23 @@ def test_warp_perspective_float32_matrix_and_dev_entry_point():
     _same(d_dst[:, :380].cpu().numpy().copy(), exp)
 
 
-@pytest.mark.parametrize("shape", [(64, 64), (129, 77), (1, 9), (512, 700)])
+@pytest.mark.parametrize("shape", [(64, 64), (129, 77), (1, 9), (512, 700), (9, 1), (1, 1), (2, 2), (4, 65)])
 def test_sobel_magnitude_bit_identical(shape):
     img = np.random.default_rng(shape[0]).integers(0, 256, shape, dtype=np.uint8)
     _same(ops.sobel_magnitude(img), R.sobel_magnitude(img))
     flat = np.full(shape, 7, np.uint8)
     _same(ops.sobel_magnitude(flat), R.sobel_magnitude(flat))
+
+
+def test_sobel_magnitude_largest_gradient_and_maximum_in_the_last_workgroup():
+    img, at = A.sobel_extreme()                  # gx^2 + gy^2 = 1020^2 + 510^2 at `at` (test_align_host.py)
+    got = ops.sobel_magnitude(img)
+    assert got[at] == 1.0
+    _same(got, R.sobel_magnitude(img))
+    last = A.sobel_last_pixel()
+    got = ops.sobel_magnitude(last)
+    assert got.max() == 1.0 and got[-1, -2] > 0
+    _same(got, R.sobel_magnitude(last))
 
 
 def _pair(n, A, pad=32, seed=20260101):
