@@ -761,6 +761,47 @@ typedef struct km_profile {
 int km_mean_profiles(km_ctx *ctx, int n, int n_prof, const km_profile *prof, int32_t *n_groups, int32_t *n_out_of_range);
 int km_mean_profiles_dev(km_ctx *ctx, int n, int n_prof, const km_profile *d_prof, int32_t *n_groups, int32_t *n_out_of_range);
 
+/* ---- the report's products and the altitude figure's numbers on resident data (karios/report/product_generator.py:138-218,
+ * karios/api/core.py:1049-1053, karios/report/shift_by_alt_plot.py:127-171); tests/products_restatement.py is the definition.
+ * In all three the host form reads and writes host memory, the device form device memory; the counts (n_out_of_range, n_groups) are
+ * host memory in both, and the device form completes the context stream before it returns.  Every argument error is KM_E_ARG before
+ * anything is launched.
+ *
+ * Point rasters of n (0 .. 2^20) key points on an H x W grid (fewer than 2^32 - 1 pixels): `mask` (NULL: none; row stride in bytes)
+ * becomes 0 with 1 at every key point, `delta` (NULL: none; band b, row y at delta + b * band_stride + y * row_stride, strides in
+ * floats) becomes two bands of NaN (bits 0x7FC00000) with dx / dy, copied by bits, at the key points.  Nothing outside the H x W
+ * windows is written.  The pixel of a row is (int)y0, (int)x0 - float32 truncated toward zero; a column in [-W, W), a negative one
+ * counted from the right edge as numpy's assignment into a row buffer does; a row in [0, H).  Several rows on one pixel: the last in
+ * input order.  A row with a NaN or infinite coordinate or outside those ranges stores nothing and is counted in *n_out_of_range
+ * (the reference raises IndexError there; the matcher produces no such row).  dx / dy are read only when there is a delta raster. */
+int km_point_rasters(km_ctx *ctx, int n, const float *x0, const float *y0, const float *dx, const float *dy, int H, int W, uint8_t *mask,
+                     ptrdiff_t mask_stride, float *delta, ptrdiff_t band_stride, ptrdiff_t row_stride, int32_t *n_out_of_range);
+int km_point_rasters_dev(km_ctx *ctx, int n, const float *d_x0, const float *d_y0, const float *d_dx, const float *d_dy, int H, int W,
+                         uint8_t *d_mask, ptrdiff_t mask_stride, float *d_delta, ptrdiff_t band_stride, ptrdiff_t row_stride,
+                         int32_t *n_out_of_range);
+/* out[i] = raster[(int)y0[i], (int)x0[i]] of a KM_U8 / KM_U16 / KM_I16 / KM_F32 raster (H x W, row stride in elements), in the
+ * raster's type, for n (0 .. 2^20) rows: numpy's fancy indexing - both indices truncated toward zero, [-size, size), a negative one
+ * counted from the end.  A row outside that, or with a NaN or infinite coordinate, reads as 0 and is counted in *n_out_of_range. */
+int km_sample_points(km_ctx *ctx, const void *raster, int dtype, int H, int W, ptrdiff_t stride, int n, const float *x0, const float *y0,
+                     void *out, int32_t *n_out_of_range);
+int km_sample_points_dev(km_ctx *ctx, const void *d_raster, int dtype, int H, int W, ptrdiff_t stride, int n, const float *d_x0,
+                         const float *d_y0, void *d_out, int32_t *n_out_of_range);
+/* matplotlib.cbook.boxplot_stats(x, whis=1.5) of every group of n (0 .. 2^20) rows, grouped as km_mean_profiles groups them
+ * (np.floor_divide(positions, float32(bin_size)), bin_size 1 .. 2^24, a NaN key drops the row, the groups ascending); x = the group's
+ * values in row order, NaN values included.  Per group g, into outputs of capacity n: key[g]; count[g] = len(x); mean[g] =
+ * np.mean(x) (numpy's pairwise float32 sum over blocks of 8192 / float32(count)); and KM_BOX_STATS float64 columns of n each in
+ * `stats`, column k at stats + k * n, in the order q1, med, q3 (np.percentile(x, [25, 50, 75]): float64 interpolation between float32
+ * order statistics whose difference is formed in float32), iqr = q3 - q1, cilo / cihi = med -/+ 1.57 * iqr / sqrt(count), whislo,
+ * whishi (the smallest x >= q1 - 1.5 iqr / the largest x <= q3 + 1.5 iqr, compared in float64; q1 / q3 when there is none or it lies
+ * inside the box).  Order statistics and whisker ends that are zero are +0.0.  A group holding a NaN value has NaN statistics.
+ * cls[i] per ROW: 0 inside the whiskers, 1 below whislo, 2 above whishi (matplotlib's fliers are the 1s in row order, then the 2s), -1
+ * for a dropped row.  *n_groups: the number of groups. */
+#define KM_BOX_STATS 8
+int km_box_stats(km_ctx *ctx, int n, const float *values, const float *positions, int bin_size, float *key, int32_t *count, float *mean,
+                 double *stats, int8_t *cls, int32_t *n_groups);
+int km_box_stats_dev(km_ctx *ctx, int n, const float *d_values, const float *d_positions, int bin_size, float *d_key, int32_t *d_count,
+                     float *d_mean, double *d_stats, int8_t *d_cls, int32_t *n_groups);
+
 #ifdef __cplusplus
 }
 #endif

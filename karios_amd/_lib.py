@@ -86,7 +86,8 @@ class Profile(C.Structure):
 
 DISPLAY_MAX_NO_VALUES = 16     # KM_DISPLAY_MAX_NO_VALUES
 PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = 8, 1 << 20, 1 << 24   # KM_PROFILE_MAX; rows and bin size km_mean_profiles takes
-CHIP_SIZE, CHIP_MAX_GRID, CHIP_PICKS = 57, 16, 5      # KM_CHIP_SIZE, KM_CHIP_MAX_GRID, KM_CHIP_PICKS
+BOX_STATS = 8                  # KM_BOX_STATS: q1, med, q3, iqr, cilo, cihi, whislo, whishi
+CHIP_SIZE, CHIP_MAX_GRID, CHIP_PICKS = 57, 16, 5     # KM_CHIP_SIZE, KM_CHIP_MAX_GRID, KM_CHIP_PICKS
 CHIP_SELECT_MAX_ROWS, CHIP_MAX_ROWS = 1 << 24, 1 << 20
 CLIP_MAX_ROWS = 32768          # rows one unit of km_sigma_clip_dev / the "frame_clip" stage holds
 UNITS_PER_SUBMISSION = 16      # KM_UNITS_PER_SUBMISSION
@@ -212,6 +213,12 @@ SIGNATURES = {
     "km_display_range_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, _pd, _pd, _i, _i, _pd, C.POINTER(DisplayRangeResult), _pd, _pd, _pd]),
     "km_mean_profiles": (_i, [_vp, _i, _i, C.POINTER(Profile), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "km_mean_profiles_dev": (_i, [_vp, _i, _i, C.POINTER(Profile), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "km_point_rasters": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _sz, C.POINTER(C.c_int32)]),
+    "km_point_rasters_dev": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _sz, C.POINTER(C.c_int32)]),
+    "km_sample_points": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "km_sample_points_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "km_box_stats": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "km_box_stats_dev": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -203,6 +203,7 @@ enum km_slot {
     WS_RP_FLAG,     //   head flags and their exclusive scan; the counts of every profile of the call
     WS_RP_SCAN,     //   tile sums of that scan
     WS_RP_IO,       //   columns and outputs of the host-API form
+    WS_PD_MISC,     // api_score.hip (box statistics; its keys, flags and scan use the WS_RP_* slots): gathered values, heads, group indices, block sums
     WS_COUNT
 };
 

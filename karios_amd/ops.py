@@ -1360,3 +1360,157 @@ def mean_profiles(profiles, ctx: Context | None = None):
     if any(oor):
         raise ValueError(f"mean_profiles: {sum(oor)} group position(s) outside int32")
     return [ProfileColumns(*(a[:groups[i]] for a in outs[i])) for i in range(k)]
+
+
+# ---- the report's products and the altitude figure's numbers (csrc/api_score.hip km_point_rasters, km_sample_points, km_box_stats,
+# k_products.hip) --------------------------------------------------------------------------------------------------------------------
+BOX_STAT_NAMES = ("q1", "med", "q3", "iqr", "cilo", "cihi", "whislo", "whishi")     # the columns of km_box_stats, in its order
+
+
+def _raster_shape(shape, what):
+    H, W = (int(v) for v in shape)
+    if H < 1 or W < 1 or H * W >= 2 ** 32 - 1:
+        raise ValueError(f"{what}: a raster of {H} x {W} (at least 1 x 1, fewer than 2^32 - 1 pixels)")
+    return H, W
+
+
+def _out_plane(out, shape, np_dtype, dev, device, what):
+    """The caller's buffer for one output - a window of a wider buffer is fine - or a fresh one."""
+    if out is None:
+        if dev:
+            import torch
+            return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=device)
+        return np.empty(shape, np_dtype)
+    if _on_device(out) != dev:
+        raise ValueError(f"{what}: the output must live where the columns live")
+    dt = _torch_np_dtype(out) if dev else out.dtype
+    strides = tuple(out.stride()) if dev else tuple(s // out.itemsize for s in out.strides)
+    if dt != np.dtype(np_dtype) or tuple(out.shape) != tuple(shape) or (shape[-1] > 1 and strides[-1] != 1) or (not dev and not out.flags.writeable):
+        raise ValueError(f"{what}: the output must be a writable {np.dtype(np_dtype).name} buffer of shape {tuple(shape)} with contiguous rows")
+    return out
+
+
+def point_rasters(x0, y0, dx=None, dy=None, shape=None, mask=True, delta=True, out_mask=None, out_delta=None, ctx: Context | None = None):
+    """ProductGenerator._create_mask / _create_intermediate_raster (report/product_generator.py:138-218) minus the file: for float32
+    key-point columns and a raster `shape` (H, W) -> (`mask`, `delta`): the uint8 H x W raster with 1 at every key point and the
+    float32 2 x H x W raster of NaN with dx / dy at the key points (None for the one not asked for; `dx = dy = None` gives the mask
+    alone).  Pixels are `x0.astype(int)`, `y0.astype(int)`; columns wrap as numpy's assignment into a row buffer does, rows do not;
+    of several rows on one pixel the last wins.  numpy columns give numpy rasters, device tensors device tensors; `out_mask` /
+    `out_delta` may name the buffers to fill (windows of wider buffers included).  IndexError, as from the reference, when a row lies
+    outside the raster or has a NaN or infinite coordinate."""
+    delta = bool(delta) and dx is not None
+    mask = bool(mask)
+    if (dx is None) != (dy is None):
+        raise ValueError("point_rasters: dx and dy come together")
+    if shape is None:
+        raise ValueError("point_rasters: the raster's shape is needed")
+    H, W = _raster_shape(shape, "point_rasters")
+    dev, cols, n = _f32_columns((x0, y0) + ((dx, dy) if delta else ()), "point_rasters", "x0, y0, dx and dy")
+    if n > PROFILE_MAX_ROWS:
+        raise ValueError(f"point_rasters: {n} rows (at most 2^20)")
+    device = cols[0].device if dev else None
+    m = _out_plane(out_mask, (H, W), np.uint8, dev, device, "point_rasters") if mask else None
+    d = _out_plane(out_delta, (2, H, W), np.float32, dev, device, "point_rasters") if delta else None
+    c = _ctx(ctx)
+    if dev:
+        import torch
+        torch.cuda.synchronize(device)
+    args = _col_args(dev, cols, n) + [None] * (4 - len(cols))
+
+    def plane(a):
+        return None if a is None else (C.c_void_p(a.data_ptr()) if dev else ptr(a))
+
+    def strides(a):
+        return tuple(int(s) for s in a.stride()) if dev else tuple(s // a.itemsize for s in a.strides)
+    ms = (strides(m)[0] if H > 1 else W) if mask else 0
+    bs, rs = ((strides(d)[0], strides(d)[1] if H > 1 else W) if delta else (0, 0))
+    bad = C.c_int32()
+    what = "km_point_rasters_dev" if dev else "km_point_rasters"
+    c.check(getattr(c.lib, what)(c.handle, n, *args, H, W, plane(m), ms, plane(d), bs, rs, C.byref(bad)), what)
+    if bad.value:
+        raise IndexError(f"point_rasters: {bad.value} row(s) out of bounds for a raster of {H} x {W}")
+    return m, d
+
+
+def sample_points(raster, x0, y0, dtype=None, ctx: Context | None = None):
+    """`raster[y0.astype(int), x0.astype(int)]` (the altitude column, api/core.py:1049-1053) of a 2-D uint8 / uint16 / int16 /
+    float32 raster for float32 columns: numpy's fancy indexing, negative indices counted from the end, in the raster's type.
+    Raster and columns are all numpy arrays or all tensors on the context's device (rows contiguous; a window of a wider buffer is
+    fine).  `dtype` names the pixel type of a tensor that only stores its bit pattern (uint16 in int16 storage); the result keeps
+    the storage type.  IndexError where numpy raises it, and for a NaN or infinite coordinate."""
+    dev, cols, n = _f32_columns((x0, y0), "sample_points", "x0 and y0")
+    if _on_device(raster) != dev:
+        raise ValueError("sample_points: raster and columns must all be numpy arrays or all be device tensors")
+    if dev:
+        if raster.dim() != 2 or (raster.shape[1] > 1 and raster.stride(1) != 1):
+            raise ValueError("sample_points: expected a 2-D tensor with contiguous rows")
+        dt = _torch_np_dtype(raster)
+        if dtype is not None:
+            if np.dtype(dtype).itemsize != dt.itemsize:
+                raise ValueError(f"sample_points: pixel type {np.dtype(dtype)} in {dt} storage")
+            dt = np.dtype(dtype)
+        H, W = int(raster.shape[0]), int(raster.shape[1])
+        stride = int(raster.stride(0)) if H > 1 else W
+        img_arg = C.c_void_p(raster.data_ptr())
+    else:
+        a = as_image(raster)
+        dt, (H, W), stride, img_arg = a.dtype, a.shape, row_stride(a), ptr(a)
+    if dt not in PREP_DTYPES:
+        raise KariosHipError(f"sample_points: unsupported pixel type {dt} (uint8, uint16, int16, float32)")
+    if H < 1 or W < 1:
+        raise ValueError("sample_points: empty raster")
+    if n > PROFILE_MAX_ROWS:
+        raise ValueError(f"sample_points: {n} rows (at most 2^20)")
+    c = _ctx(ctx)
+    if dev:
+        import torch
+        torch.cuda.synchronize(raster.device)
+        out = torch.empty(n, dtype=raster.dtype, device=raster.device)
+    else:
+        out = np.empty(n, dt)
+    bad = C.c_int32()
+    what = "km_sample_points_dev" if dev else "km_sample_points"
+    c.check(getattr(c.lib, what)(c.handle, img_arg, _lib._DTYPES[dt], H, W, stride, n, *_col_args(dev, cols + (out,), n), C.byref(bad)), what)
+    if bad.value:
+        raise IndexError(f"sample_points: {bad.value} row(s) out of bounds for a raster of {H} x {W}")
+    return out
+
+
+class BoxStats:
+    """Result of `box_stats`: per group `key` (float32, ascending), `count` (int32, NaN values included), `mean` (float32) and the
+    float64 columns `q1`, `med`, `q3`, `iqr`, `cilo`, `cihi`, `whislo`, `whishi`; `cls` (int8) per ROW: 0 inside the whiskers, 1
+    below, 2 above, -1 for a row without a group.  numpy arrays, or device tensors for device input."""
+
+    def __init__(self, key, count, mean, stats, cls):
+        self.key, self.count, self.mean, self.cls = key, count, mean, cls
+        for name, col in zip(BOX_STAT_NAMES, stats):
+            setattr(self, name, col)
+
+
+def box_stats(values, positions, bin_size, ctx: Context | None = None) -> BoxStats:
+    """matplotlib.cbook.boxplot_stats(x, whis=1.5) of every group of `mean_profile` (np.floor_divide(positions, bin_size), the
+    groups ascending), x the group's values in row order: float32 columns of one length (at most 2^20 rows; numpy or device
+    tensors), 1 <= bin_size <= 2^24 -> `BoxStats`.  The fliers of a group are its rows of class 1 in row order, then those of
+    class 2 (`box_fliers`)."""
+    dev, cols, n = _f32_columns((values, positions), "box_stats", "values and positions")
+    if n > PROFILE_MAX_ROWS:
+        raise ValueError(f"box_stats: {n} rows (at most 2^20)")
+    if int(bin_size) != bin_size or not 1 <= int(bin_size) <= PROFILE_MAX_BIN:
+        raise ValueError(f"box_stats: bin size {bin_size} (an integer, 1 .. 2^24)")
+    c = _ctx(ctx)
+    k = _lib.BOX_STATS
+    if dev:
+        import torch
+        device = cols[0].device
+        torch.cuda.synchronize(device)
+        key, count, mean = (torch.empty(n, dtype=t, device=device) for t in (torch.float32, torch.int32, torch.float32))
+        stats, cls = torch.empty((k, n), dtype=torch.float64, device=device), torch.empty(n, dtype=torch.int8, device=device)
+    else:
+        key, count, mean = (np.empty(n, t) for t in (np.float32, np.int32, np.float32))
+        stats, cls = np.empty((k, n), np.float64), np.empty(n, np.int8)
+    groups = C.c_int32()
+    a = _col_args(dev, cols + (key, count, mean, stats, cls), n)
+    what = "km_box_stats_dev" if dev else "km_box_stats"
+    c.check(getattr(c.lib, what)(c.handle, n, a[0], a[1], int(bin_size), *a[2:], C.byref(groups)), what)
+    g = groups.value
+    return BoxStats(key[:g], count[:g], mean[:g], [stats[j, :g] for j in range(k)], cls)

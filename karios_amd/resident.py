@@ -762,6 +762,17 @@ class ResidentPair:
         ref = ops._display_range_call(c, "km_display_range_dev", C.c_void_p(self.ref_ptr), self.dtype, H, W, W, None, 0, values, self.no_data_ref, pp)
         return mon, ref
 
+    # ------------------------------------------------------------------ the report's products
+    def point_rasters(self, points, mask: bool = True, delta: bool = True):
+        """The rasters behind `kp_mask.tif` and `kp_delta.tif` (report/product_generator.py:138-218) in the reference raster's shape
+        -> (mask, delta): uint8 y_size x x_size with 1 at every key point, float32 2 x y_size x x_size of NaN with dx / dy at the
+        key points; None for the one not asked for.  `points`: a DataFrame (numpy rasters) or a mapping of float32 device columns
+        (device tensors)."""
+        from . import ops
+        from .report.product_generator import point_columns
+        cols = point_columns(points, ("x0", "y0", "dx", "dy") if delta else ("x0", "y0"))
+        return ops.point_rasters(*cols, shape=(self.y_size, self.x_size), mask=mask, delta=delta, ctx=self.ctx)
+
     # ------------------------------------------------------------------ large offset
     def phase_offset(self) -> np.ndarray:
         """LargeOffsetMatcher.match() on resident data (large_offset.py:39): [row, col]."""
