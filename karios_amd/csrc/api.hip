@@ -83,7 +83,9 @@ static int join_uploads(km_ctx *c)
     if (c->copy_pending) {
         KM_HIP(c, hipEventRecord(c->ev_copy, c->copy_stream));
         KM_HIP(c, hipStreamWaitEvent(c->stream, c->ev_copy, 0));
-        if (c->aux_stream) KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_copy, 0));   // (the early min / max reads the rasters there)
+        // (the early min / max reads the rasters there.  No second stream yet: whoever creates it puts it behind the main stream before its first
+        // kernel - the fork of a tile's pyramids, the start of a batched pipeline, api_units.hip - and so behind the wait above)
+        if (c->aux_stream) KM_HIP(c, hipStreamWaitEvent(c->aux_stream, c->ev_copy, 0));
         c->copy_pending = false;
     }
     return KM_OK;

@@ -216,6 +216,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     // (a pipelined submission was the previous one: its tail first, and this one behind both lanes' chains)
     if (!piped && ((rc = units_flush_locked(c)) || (rc = join_lanes(c)))) return rc;
     const int lane = piped ? (old_tail.armed ? 1 - old_tail.lane : 0) : 0;
+    const bool pipe_start = piped && !old_tail.armed;      // (no pipelined submission directly in front of this one)
     hipStream_t const main_stream = c->stream;
     units_scope scope(c, false);
     int k;
@@ -230,6 +231,14 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     for (int i = 0; i < KM_LANE_EVENTS; i++)
         if ((rc = km_event(c, &c->ev_lane[lane][i]))) return rc;
     if (piped && (rc = km_stream(c, &c->chain_stream))) return rc;
+    // Pipeline start: the second stream goes behind whatever the main stream holds at this point.  A pipelined submission runs its min / max
+    // and its setup there AT ONCE, and takes lane 0 - the workspace of every other entry point: a tile still in flight on the main stream
+    // (km_klt_tile_frame_submit) owns lane 0's scalar block, LK table and partials, the call in front may have written the rasters on the
+    // main stream (km_shift_image_dev), and a second stream created a few lines up has seen none of the uploads the main stream was made to
+    // wait for (join_uploads, km_upload_join).  One device-side wait per pipeline start; behind another pipelined submission the lanes' own
+    // events order everything and nothing is added.
+    if (pipe_start && ((rc = km_event(c, &c->ev_units_start)) || (rc = km_record(c, c->ev_units_start, c->stream)) || (rc = km_wait(c, c->aux_stream, c->ev_units_start))))
+        return rc;
     km_event_h *ev = c->ev_lane[lane];
 
     // ---- layout: unit u's slices of the lane's workspace slots

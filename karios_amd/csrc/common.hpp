@@ -309,6 +309,7 @@ struct km_ctx {
     km_event_h ev_lk_start, ev_mm;       // early min/max: the next unit's K1 starts on aux_stream when this unit's LK launch starts
     bool lk_start_valid = false, lk_start_prev = false;   //   ... ev_lk_start was recorded by the tile call that directly preceded this one
     km_event_h ev_fork, ev_join;         // chain of small corner-selection kernels on `stream`, joined before LK
+    km_event_h ev_units_start;           // api_units.hip: the main stream at the start of a pipelined submission that does not directly follow another one
     bool copy_pending = false;           // uploads queued since the compute stream last waited for the whole copy stream
     std::vector<km_event_h> upload_marks;   // km_upload_mark tickets: events on the copy stream, empty = ticket consumed
     std::vector<km_event_h> free_marks;

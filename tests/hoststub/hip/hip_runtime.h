@@ -14,6 +14,8 @@
 #include <map>
 #include <mutex>
 
+#include "../stub_order.hpp"      // the happens-before checker (off by default: every hook below then returns at once)
+
 #define __host__
 #define __device__
 #define __global__
@@ -69,7 +71,7 @@ static inline const char *hipGetErrorString(hipError_t e) { return e == hipSucce
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipGetDeviceCount(int *n) { *n = getenv("KARIOS_STUB_NO_DEVICE") ? 0 : 1; return hipSuccess; }
 static inline hipError_t hipSetDevice(int) { return hipSuccess; }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
+static inline hipError_t hipDeviceSynchronize() { stub_order::host_join_all(); return hipSuccess; }
 static inline hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = -1; return hipSuccess; }
 
@@ -80,19 +82,25 @@ hipError_t hipHostFree(void *p);
 hipError_t hipPointerGetAttributes(hipPointerAttribute_t *at, const void *p);
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t s);
 hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t s);
-static inline hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind k) { return hipMemcpyAsync(dst, src, n, k, nullptr); }
-static inline hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t) { memset(dst, v, n); return hipSuccess; }
+// (blocking: an operation on the null stream, then the host knows it is through - it does not order behind non-blocking streams)
+static inline hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind k)
+{
+    const hipError_t e = hipMemcpyAsync(dst, src, n, k, nullptr);
+    stub_order::host_join_stream(nullptr);
+    return e;
+}
+static inline hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t s) { stub_order::op(s, "hipMemsetAsync").write(dst, n); memset(dst, v, n); return hipSuccess; }
 static inline hipError_t hipHostRegister(void *, size_t, unsigned) { return hipSuccess; }
 
 static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { return stub_create(s, stub().streams, 0); }
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int p) { return stub_create(s, stub().streams, p); }
-static inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) stub().streams--; delete s; return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t e, unsigned) { return e ? hipSuccess : hipErrorInvalidValue; }
+static inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) stub().streams--; stub_order::on_stream_destroy(s); delete s; return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t s) { stub_order::host_join_stream(s); return hipSuccess; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { if (!e) return hipErrorInvalidValue; stub_order::on_wait(s, e); return hipSuccess; }
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return stub_create(e, stub().events, 0); }
 static inline hipError_t hipEventCreate(hipEvent_t *e) { return stub_create(e, stub().events, 0); }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) stub().events--; delete e; return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { if (!e) return hipErrorInvalidValue; e->recorded++; return hipSuccess; }
-static inline hipError_t hipEventSynchronize(hipEvent_t e) { return e ? hipSuccess : hipErrorInvalidValue; }
-static inline hipError_t hipEventQuery(hipEvent_t e) { return e ? hipSuccess : hipErrorInvalidValue; }   // (the stand-in executes everything at once: always complete)
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) { stub().events--; stub_order::on_event_destroy(e); } delete e; return hipSuccess; }
+static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { if (!e) return hipErrorInvalidValue; e->recorded++; stub_order::on_record(e, s); return hipSuccess; }
+static inline hipError_t hipEventSynchronize(hipEvent_t e) { if (!e) return hipErrorInvalidValue; stub_order::host_join_event(e); return hipSuccess; }
+static inline hipError_t hipEventQuery(hipEvent_t e) { if (!e) return hipErrorInvalidValue; stub_order::host_join_event(e); return hipSuccess; }   // (the stand-in executes everything at once: always complete)
 static inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { *ms = 0.f; return a && b ? hipSuccess : hipErrorInvalidValue; }

@@ -27,7 +27,7 @@ static void require_all_created(const km_ctx *c)
 {
 #define HAS(member) REQUIRE((member), "never created: %s", #member)
     HAS(c->main_stream); HAS(c->copy_stream); HAS(c->aux_stream); HAS(c->d2h_stream); HAS(c->chain_stream);
-    HAS(c->ev_copy); HAS(c->ev_tail); HAS(c->ev_lk_start); HAS(c->ev_mm); HAS(c->ev_fork); HAS(c->ev_join); HAS(c->ev_readback);
+    HAS(c->ev_copy); HAS(c->ev_tail); HAS(c->ev_lk_start); HAS(c->ev_mm); HAS(c->ev_fork); HAS(c->ev_join); HAS(c->ev_units_start); HAS(c->ev_readback);
     for (int l = 0; l < 2; l++) for (int i = 0; i < KM_LANE_EVENTS; i++) HAS(c->ev_lane[l][i]);
     HAS(c->ev_ready); HAS(c->evs[0][0][0]); HAS(c->evs[KM_FRAME_SLOTS][ST_COUNT - 1][1]);
     HAS(c->land_ev[0]); HAS(c->land_ev[1]); HAS(c->land); HAS(c->chk_dev); HAS(c->chk_host); HAS(c->pinned_rb);

@@ -7,6 +7,10 @@
 // therefore run end to end on the CPU and are held to tests/ransac_restatement.py / tests/sift_restatement.py bit for bit
 // (driver_align.py).  Prep, match and align fill what the host reads back with simple arithmetic of their own; the exact formulas
 // live only in the kernels and are the GPU tests' business.
+//
+// Stream order (stub_order.hpp): the stand-ins of THIS file declare no accesses.  An unannotated launcher claims nothing, so it can only
+// hide a conflict from the checker, never invent one; the align step runs on the main stream alone.  The same holds for the clip stage's
+// stand-in, which lives in csrc/k_clip.hpp.
 #include "../../karios_amd/csrc/k_align.hpp"
 #include "../../karios_amd/csrc/k_match.hpp"
 #include "../../karios_amd/csrc/k_prep.hpp"
