@@ -7,8 +7,15 @@
 // window, a 6-step DPP wave scan + 4 ds_bpermute per product for the horizontal box sum, and one LDS append with ballot /
 // mbcnt arithmetic per pixel for the 3 % of the pixels that are candidates; 18 of its 128 columns and 16 of its 64 rows
 // are halo.  Here a lane owns 8 ADJACENT columns (one 8-byte load per row) and a wavefront 512:
-//   * Sobel: the odd-aligned pixel pairs are shared between neighbouring pairs of the same lane (5 byte alignments and
-//     2 DPP moves per 4 pairs and operand instead of 8 + 8);
+//   * Sobel + vertical box sum: the sum of a pixel is kept current by adding the product row that enters the window and
+//     subtracting the one that leaves it, BLOCK rows above.  The two rows travel together: a dword holds pixel p of the
+//     entering source row in its low half and pixel p of the leaving one in its high half, so ONE chain of packed 16-bit
+//     instructions computes both rows' derivatives (each half on its own; column sums <= 1020, |dx|, |dy| <= 1020), a pixel's
+//     horizontal neighbours are other registers of the same lane (no byte alignment; 4 DPP moves per row step, for pixels 0
+//     and 7), and `entering - leaving` of each of the three products is one v_dot2_i32_i16: (xl, xt) . (xl, -xt),
+//     (xl, xt) . (yl, -yt), (yl, yt) . (yl, -yt), the sign-flipped operands being dx and dy times the pair (1, -1) - or
+//     (1, 0) as long as no row leaves the window.  102 instructions per 512-pixel row step where two separate chains on
+//     horizontally adjacent pairs took 142 (profiles/eig3_paired_rows_isa.md);
 //   * the box filter (<= 15 wide) of a pixel spans this lane and its two neighbours only: it slides along the lane's pixels,
 //     W(p+1) = W(p) + V(p+1+R) - V(p-L), with the neighbours' vertical sums as DPP operands of the add / subtract itself -
 //     no scan, no LDS;
@@ -31,18 +38,8 @@ namespace {
 #define EIG3_MARGIN 12      // halo columns either side of a strip's outputs (>= L + 2, multiple of 4)
 #define EIG3_STRIDE (512 - 2 * EIG3_MARGIN)
 
-__device__ __forceinline__ int e3_mad_lo(uint32_t a, uint32_t b, int c)
-{
-    int d;
-    asm("v_mad_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ int e3_mad_hi(uint32_t a, uint32_t b, int c)
-{
-    int d;
-    asm("v_mad_i32_i16 %0, %1, %2, %3 op_sel:[1,1,0,0]" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
+// a.lo * b.lo + a.hi * b.hi + c: one v_dot2_i32_i16 (the builtin, not assembly: the compiler pads the DOT hazards of its own instructions)
+__device__ __forceinline__ int e3_dot2(uint32_t a, uint32_t b, int c) { return __builtin_amdgcn_sdot2(e2s(a), e2s(b), c, false); }
 __device__ __forceinline__ uint32_t e3_pk_mad2(uint32_t a, uint32_t c)   // a * 2 + c on both 16-bit halves: one v_pk_mad_u16
 {
     uint32_t d;
@@ -111,40 +108,42 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
         __builtin_memcpy(&v, rowp + e2_opaque((unsigned)c0), 8);
         return v;
     };
-    struct row4 { uint32_t q[4]; };                  // 8 pixels as four 16-bit pairs
-    auto unpack = [&](uint2 w) -> row4 {
-        row4 r;
-        r.q[0] = __builtin_amdgcn_perm(0u, w.x, 0x0c010c00u);
-        r.q[1] = __builtin_amdgcn_perm(0u, w.x, 0x0c030c02u);
-        r.q[2] = __builtin_amdgcn_perm(0u, w.y, 0x0c010c00u);
-        r.q[3] = __builtin_amdgcn_perm(0u, w.y, 0x0c030c02u);
+    // A source row of the ENTERING Sobel window and the same-numbered row of the LEAVING one (BLOCK rows above) as one row of
+    // eight dwords: pixel p's entering byte in the low half, its leaving byte in the high half.  The packed 16-bit arithmetic
+    // below runs both Sobel chains at once, each in its own half, and a pixel's horizontal neighbours are other registers of
+    // the same lane: no byte alignment, and only pixels 0 and 7 look into the adjacent lanes.
+    struct row8 { uint32_t d[8]; };
+    auto pack = [&](uint2 lead, uint2 trail) -> row8 {
+        row8 r;
+        r.d[0] = __builtin_amdgcn_perm(trail.x, lead.x, 0x0c040c00u);
+        r.d[1] = __builtin_amdgcn_perm(trail.x, lead.x, 0x0c050c01u);
+        r.d[2] = __builtin_amdgcn_perm(trail.x, lead.x, 0x0c060c02u);
+        r.d[3] = __builtin_amdgcn_perm(trail.x, lead.x, 0x0c070c03u);
+        r.d[4] = __builtin_amdgcn_perm(trail.y, lead.y, 0x0c040c00u);
+        r.d[5] = __builtin_amdgcn_perm(trail.y, lead.y, 0x0c050c01u);
+        r.d[6] = __builtin_amdgcn_perm(trail.y, lead.y, 0x0c060c02u);
+        r.d[7] = __builtin_amdgcn_perm(trail.y, lead.y, 0x0c070c03u);
         return r;
     };
-    // Sobel derivatives of the product row whose source rows are r0 (above), r1, r2 (below); NEG: also their negatives
-    auto derivs = [&](const row4 &r0, const row4 &r1, const row4 &r2, uint32_t (&dx)[4], uint32_t (&dy)[4]) {
-        uint32_t t0[4], t1[4], m0[5], m1[5];
+    // Sobel derivatives of the two product rows (low halves: entering, high halves: leaving) whose source rows are r0 (above), r1, r2 (below)
+    auto derivs = [&](const row8 &r0, const row8 &r1, const row8 &r2, uint32_t (&dx)[8], uint32_t (&dy)[8]) {
+        uint32_t t0[8], t1[8];
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            t0[i] = e3_pk_mad2(r1.q[i], e2u(e2s(r0.q[i]) + e2s(r2.q[i])));   // column sums (for dx)
-            t1[i] = e2u(e2s(r2.q[i]) - e2s(r0.q[i]));                         // column differences (for dy)
+        for (int p = 0; p < 8; p++) {
+            t0[p] = e3_pk_mad2(r1.d[p], e2u(e2s(r0.d[p]) + e2s(r2.d[p])));   // column sums (for dx): <= 1020
+            t1[p] = e2u(e2s(r2.d[p]) - e2s(r0.d[p]));                         // column differences (for dy): |.| <= 255
         }
         // t0 comes out of inline assembly, which the compiler's hazard recogniser cannot see into: a VGPR written by a VALU
         // instruction must not be read through DPP in the next two wait states
-        asm("s_nop 1" : "+v"(t0[0]), "+v"(t0[3]));
-        const uint32_t l0 = (uint32_t)e2_lane_m1((int)t0[3]), r0n = (uint32_t)e2_lane_p1((int)t0[0]);
-        const uint32_t l1 = (uint32_t)e2_lane_m1((int)t1[3]), r1n = (uint32_t)e2_lane_p1((int)t1[0]);
-        // m[i] = (pixel 2i-1, pixel 2i): the odd-aligned pairs, shared by the two even-aligned pairs either side
+        asm("s_nop 1" : "+v"(t0[0]), "+v"(t0[7]));
+        const uint32_t l0 = (uint32_t)e2_lane_m1((int)t0[7]), r0n = (uint32_t)e2_lane_p1((int)t0[0]);
+        const uint32_t l1 = (uint32_t)e2_lane_m1((int)t1[7]), r1n = (uint32_t)e2_lane_p1((int)t1[0]);
 #pragma unroll
-        for (int i = 0; i < 5; i++) {
-            const uint32_t lo0 = i == 0 ? l0 : t0[i - 1], hi0 = i == 4 ? r0n : t0[i];
-            const uint32_t lo1 = i == 0 ? l1 : t1[i - 1], hi1 = i == 4 ? r1n : t1[i];
-            m0[i] = __builtin_amdgcn_alignbyte(hi0, lo0, 2);
-            m1[i] = __builtin_amdgcn_alignbyte(hi1, lo1, 2);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            dx[i] = e2u(e2s(m0[i + 1]) - e2s(m0[i]));
-            dy[i] = e2u(e2s(e3_pk_mad2(t1[i], m1[i])) + e2s(m1[i + 1]));
+        for (int p = 0; p < 8; p++) {
+            const uint32_t lo0 = p == 0 ? l0 : t0[(p + 7) & 7], hi0 = p == 7 ? r0n : t0[(p + 1) & 7];
+            const uint32_t lo1 = p == 0 ? l1 : t1[(p + 7) & 7], hi1 = p == 7 ? r1n : t1[(p + 1) & 7];
+            dx[p] = e2u(e2s(hi0) - e2s(lo0));
+            dy[p] = e2u(e2s(e3_pk_mad2(t1[p], lo1)) + e2s(hi1));
         }
     };
     // vertical box sums of the three products, per pixel
@@ -153,17 +152,15 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
     for (int q = 0; q < 3; q++)
 #pragma unroll
         for (int p = 0; p < 8; p++) V[q][p] = 0;
-    auto accumulate = [&](const uint32_t (&dx)[4], const uint32_t (&dy)[4], bool subtract) {
+    // V += entering products - leaving products: (xl, xt) . (xl, -xt) and so on, one dot product per sum.  sign = (1, -1), or
+    // (1, 0) while no row leaves the window yet: whatever the high halves hold then contributes exactly nothing
+    auto accumulate = [&](const uint32_t (&dx)[8], const uint32_t (&dy)[8], uint32_t sign) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t x = dx[i], y = dy[i];
-            const uint32_t sx = subtract ? e2u(-e2s(x)) : x, sy = subtract ? e2u(-e2s(y)) : y;
-            V[0][2 * i] = e3_mad_lo(x, sx, V[0][2 * i]);
-            V[0][2 * i + 1] = e3_mad_hi(x, sx, V[0][2 * i + 1]);
-            V[1][2 * i] = e3_mad_lo(x, sy, V[1][2 * i]);
-            V[1][2 * i + 1] = e3_mad_hi(x, sy, V[1][2 * i + 1]);
-            V[2][2 * i] = e3_mad_lo(y, sy, V[2][2 * i]);
-            V[2][2 * i + 1] = e3_mad_hi(y, sy, V[2][2 * i + 1]);
+        for (int p = 0; p < 8; p++) {
+            const uint32_t sx = e2u(e2s(dx[p]) * e2s(sign)), sy = e2u(e2s(dy[p]) * e2s(sign));
+            V[0][p] = e3_dot2(dx[p], sx, V[0][p]);
+            V[1][p] = e3_dot2(dx[p], sy, V[1][p]);
+            V[2][p] = e3_dot2(dy[p], sy, V[2][p]);
         }
     };
     // horizontal box sums: window of pixel p = strip pixels p - L .. p + Rr, indices < 0 / > 7 live in the neighbouring lanes
@@ -254,8 +251,8 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
         thr_run = mk2 ? (float)__dmul_rn((double)e2_unkey(mk2), quality) : 0.f;
     };
 
-    // rotating state, slot = (step + k) % 3: source rows of the lead / trail Sobel windows, lambda rows y-2, y-1, y
-    row4 LW[3], TW[3];
+    // rotating state, slot = (step + k) % 3: source rows of the entering | leaving Sobel windows, lambda rows y-2, y-1, y
+    row8 PW[3];
     float E[3][8];
     float EM[8];                                      // lambda row y-1 with -inf where the mask / the column range excludes the pixel
 #pragma unroll
@@ -270,19 +267,15 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
     auto compute = [&](auto ph_tag, int m, uint2 mkraw, bool trail, bool out, bool cand) {
         constexpr int PH = decltype(ph_tag)::value;
         constexpr int S0 = PH, S1 = (PH + 1) % 3, S2 = (PH + 2) % 3;   // window rows: oldest, middle, newest
-        uint32_t dx[4], dy[4];
-        derivs(LW[S0], LW[S1], LW[S2], dx, dy);
-        accumulate(dx, dy, false);
-        if (trail) {
-            derivs(TW[S0], TW[S1], TW[S2], dx, dy);
-            accumulate(dx, dy, true);
-        }
+        uint32_t dx[8], dy[8];
+        derivs(PW[S0], PW[S1], PW[S2], dx, dy);
+        accumulate(dx, dy, trail ? 0xffff0001u : 0x00000001u);
         if (!out) return;
         const int y = m - Rr;                        // lambda row completed by this step
         constexpr int C = PH, P1 = (PH + 2) % 3, P2 = (PH + 1) % 3;    // lambda slots: row y, y-1, y-2
         {
-            // the vertical sums were written by inline assembly (v_mad_i32_i16) and are read through DPP - also inline assembly -
-            // below: 2 wait states after a VALU write of the operand, 5 after a VALU write of EXEC
+            // the vertical sums (v_dot2 results) are read through DPP - inline assembly, which the hazard recogniser does not look
+            // into - below: 3 wait states after a DOT write of the operand, 5 after a VALU write of EXEC
             asm("s_nop 4" : "+v"(V[0][0]), "+v"(V[0][1]), "+v"(V[0][2]), "+v"(V[0][3]), "+v"(V[0][4]), "+v"(V[0][5]), "+v"(V[0][6]), "+v"(V[0][7]),
                             "+v"(V[1][0]), "+v"(V[1][1]), "+v"(V[1][2]), "+v"(V[1][3]), "+v"(V[1][4]), "+v"(V[1][5]), "+v"(V[1][6]), "+v"(V[1][7]),
                             "+v"(V[2][0]), "+v"(V[2][1]), "+v"(V[2][2]), "+v"(V[2][3]), "+v"(V[2][4]), "+v"(V[2][5]), "+v"(V[2][6]), "+v"(V[2][7]));
@@ -369,19 +362,25 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
     };
 
     // ---- general step: both windows reloaded from their (mirrored) source rows; used for the warm-up and near the top / bottom
-    auto entering3 = [&](int m, row4 (&win)[3], auto ph_tag) {
+    auto entering3 = [&](int m, bool trail, auto ph_tag) {
         constexpr int PH = decltype(ph_tag)::value;
         const int r = km_reflect101(m, H);
-        win[PH] = unpack(load8(src, km_reflect101(r - 1, H)));
-        win[(PH + 1) % 3] = unpack(load8(src, r));
-        win[(PH + 2) % 3] = unpack(load8(src, km_reflect101(r + 1, H)));
+        uint2 t[3] = {make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};   // no leaving row yet: zero bytes
+        if (trail) {
+            const int rt = km_reflect101(m - BLOCK, H);
+            t[0] = load8(src, km_reflect101(rt - 1, H));
+            t[1] = load8(src, rt);
+            t[2] = load8(src, km_reflect101(rt + 1, H));
+        }
+        PW[PH] = pack(load8(src, km_reflect101(r - 1, H)), t[0]);
+        PW[(PH + 1) % 3] = pack(load8(src, r), t[1]);
+        PW[(PH + 2) % 3] = pack(load8(src, km_reflect101(r + 1, H)), t[2]);
     };
     auto clamp_row = [&](int r) { return min(max(r, 0), H - 1); };
     auto general_step = [&](int m, auto ph_tag) {
         const int step = m - m_first;
-        entering3(m, LW, ph_tag);
         const bool trail = step >= BLOCK;
-        if (trail) entering3(m - BLOCK, TW, ph_tag);
+        entering3(m, trail, ph_tag);
         const bool out = step >= BLOCK - 1;
         const uint2 mkraw = load8(mptr, clamp_row(m - Rr));
         compute(ph_tag, m, mkraw, trail, out, out && (m - Rr) >= ye0 + 2);
@@ -415,13 +414,13 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
             qt[k] = load8(src, max(m + k - BLOCK + 1, 0));      // (clamped rows are loaded before the trail / the mask are in use)
             qm[k] = load8(mptr, max(m + k - Rr, 0));
         }
-        // warm-up groups: not every part of a step is active yet
+        // warm-up groups: not every part of a step is active yet.  The leaving halves are filled from the start - the first leaving
+        // window (step BLOCK) needs the rows packed at steps BLOCK - 2 and BLOCK - 1 - and count for nothing until then (accumulate)
         while (m + 2 <= mi_hi && m - m_first < BLOCK + 1) {
             e3_for<3>([&](auto kt) {
                 constexpr int K = decltype(kt)::value;
                 const int step = m + K - m_first;
-                LW[(K + 2) % 3] = unpack(ql[K]);
-                TW[(K + 2) % 3] = unpack(qt[K]);
+                PW[(K + 2) % 3] = pack(ql[K], qt[K]);
                 compute(kt, m + K, qm[K], step >= BLOCK, step >= BLOCK - 1, step >= BLOCK - 1 && m + K - Rr >= ye0 + 2);
                 ql[K] = load8(src, m + K + 3 + 1);
                 qt[K] = load8(src, max(m + K + 3 - BLOCK + 1, 0));
@@ -436,8 +435,7 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
             for (; m + 2 <= seg_end; m += 3) {
                 e3_for<3>([&](auto kt) {
                     constexpr int K = decltype(kt)::value;
-                    LW[(K + 2) % 3] = unpack(ql[K]);
-                    TW[(K + 2) % 3] = unpack(qt[K]);
+                    PW[(K + 2) % 3] = pack(ql[K], qt[K]);
                     compute(kt, m + K, qm[K], true, true, true);
                     ql[K] = load8(src, m + K + 3 + 1);
                     qt[K] = load8(src, m + K + 3 - BLOCK + 1);
@@ -521,9 +519,11 @@ int launch_eig3_units(km_ctx *c, km_units &U, double scale2, double quality, boo
         A.n_border[u] = 2 * ((U.H[u] - 2 + A.rows2 - 1) / A.rows2);
         border_total += A.n_border[u];
     }
-    // rows per strip item.  A single tile: 3 waves per SIMD are resident (168 VGPRs); the border items hold a slot each while they run.
+    // rows per strip item.  A single tile: 3 waves per SIMD are resident (150 VGPRs); the border items hold a slot each while they run.
     // Measured at 10980^2: 0.336 ms with 96-row items (2645 + 344 items: one round), 0.341 at 48 (two rounds), 0.373 at 64 (1.4 rounds),
-    // 0.424 at 128 (slots left empty) - km_pick_rows (a warm-up row of an item costs about a third of a full row).  A batch: what that
+    // 0.424 at 128 (slots left empty) - km_pick_rows (a warm-up row of an item costs about a third of a full row).  With the entering
+    // and the leaving row as one packed pair a warm-up row costs the whole Sobel chain, not half of it, and the order is the same:
+    // 0.303 ms at 96 rows, 0.365 at 48, 0.350 at 64, 0.374 at 128 (profiles/eig3_paired_rows_kernel_stats.md).  A batch: what that
     // rule picks for the LARGEST unit alone (one round: ~96 rows for a 10980^2 tile), clamped to [48, 96].  A batch is several rounds
     // anyway, and measured at four 10980^2 units the item height, not the number of rounds, decides: 0.357 ms per unit at 96 rows, 0.347
     // at 64, 0.381 at 128, 0.423 at the ~192 rows a rounds x height cost model prefers (long items drain the last round slowly); 16 units
