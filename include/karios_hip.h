@@ -628,7 +628,7 @@ int km_sift_detect_and_compute_dev(km_ctx *ctx, const uint8_t *d_img, int H, int
                                    float *d_size, float *d_angle, float *d_response, int *d_octave, void *d_desc, int desc_dtype,
                                    ptrdiff_t desc_stride, int *count, int64_t *stats);
 
-/* ---- KariosAPI.analyze_accuracy on resident data (api_score.hip, k_accuracy.hip, accuracy_math.hpp) ------------------------------------
+/* ---- KariosAPI.analyze_accuracy on resident data (api_accuracy.hip, k_accuracy.hip, accuracy_math.hpp) -----------------------------------
  * The arithmetic is restated in tests/accuracy_restatement.py (the definition the library is held to, bit for bit).
  *
  * np.count_nonzero of the monitored raster with the pixels under mask == 0 set to 0 (karios/api/core.py:284-290): an H x W raster

@@ -528,6 +528,17 @@ int h2d_now(km_ctx *c, void *dst, const void *src, size_t bytes)
     return km_h2d_staged(c, c->stream, dst, bytes, src, bytes, bytes, 1);
 }
 
+int upload_columns(km_ctx *c, int slot, const float *const *src, int k, int n, float **d)
+{
+    const size_t pitch = n > 0 ? (size_t)n : 1;
+    float *base = (float *)km_ws(c, slot, pitch * (size_t)k * sizeof(float));
+    if (!base) return KM_E_NOMEM;
+    for (int i = 0; i < k && n > 0; i++)
+        if (src[i]) { const int rch = h2d_now(c, base + (size_t)i * pitch, src[i], (size_t)n * sizeof(float)); if (rch) return rch; }
+    *d = base;
+    return KM_OK;
+}
+
 // diagnosis (KARIOS_HIP_VERIFY_UPLOAD): read a device image back on the library stream and compare it with its host source
 int verify_upload(km_ctx *c, const char *when, int slot, const void *host, size_t elem, int H, int W, ptrdiff_t stride, const void *d)
 {

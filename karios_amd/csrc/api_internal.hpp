@@ -91,6 +91,8 @@ int km_block_stream(km_ctx *c);                           // the block-copy stre
 
 // ---- api.hip: caller memory <-> device (through the page-locked ring / landing arena, staging.hip)
 int h2d_now(km_ctx *c, void *dst, const void *src, size_t bytes);
+// caller columns -> one workspace slot: column i at *d + i * pitch, pitch = max(n, 1); a null column is skipped, n == 0 copies nothing
+int upload_columns(km_ctx *c, int slot, const float *const *src, int k, int n, float **d);
 int verify_upload(km_ctx *c, const char *when, int slot, const void *host, size_t elem, int H, int W, ptrdiff_t stride, const void *d);
 int upload_image(km_ctx *c, int slot, const void *host, size_t elem, int H, int W, ptrdiff_t stride, void **dptr);
 km_scalars *scalars(km_ctx *c);

@@ -187,7 +187,7 @@ enum km_slot {
     WS_SF_DESC,     //   ... and their descriptors
     WS_SF_PERM,     //   the final order
     WS_SF_OUT,      //   results of the host-API form
-    WS_AC_IN,       // api_score.hip (accuracy): dx | dy | score of the host-API form
+    WS_AC_IN,       // api_accuracy.hip: dx | dy | score of the host-API form
     WS_AC_COLS,     //   the sample's columns x | y | c
     WS_AC_BSUM,     //   sums of the 8192-blocks of the three columns
     WS_AC_STATE,    //   ka_state, the result block, the pixel count
@@ -198,12 +198,12 @@ enum km_slot {
     WS_AC_KEYS1,    //   ... the sort's second buffer
     WS_CL_COLS,     // k_clip.hip: the working columns dx | dy | row name | new label of every unit of a clip launch
     WS_RP_STATE,    // api_prep.hip (display range): the select's state (k_report.hip) and the result block
-    WS_RP_KEYS0,    // api_score.hip (mean profiles): (group key << 32 | row) of one profile
+    WS_RP_KEYS0,    // api_report.hip (mean profiles): (group key << 32 | row) of one profile
     WS_RP_KEYS1,    //   ... the sort's second buffer, then the gathered values and the group heads
     WS_RP_FLAG,     //   head flags and their exclusive scan; the counts of every profile of the call
     WS_RP_SCAN,     //   tile sums of that scan
     WS_RP_IO,       //   columns and outputs of the host-API form
-    WS_PD_MISC,     // api_score.hip (box statistics; its keys, flags and scan use the WS_RP_* slots): gathered values, heads, group indices, block sums
+    WS_PD_MISC,     // api_report.hip (box statistics; its keys, flags and scan use the WS_RP_* slots): gathered values, heads, group indices, block sums
     WS_COUNT
 };
 

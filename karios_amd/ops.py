@@ -807,7 +807,7 @@ def sift_detect_and_compute(image, *, contrast_threshold: float = 0.02, edge_thr
     return out
 
 
-# ---- KariosAPI.analyze_accuracy (csrc/api_score.hip, k_accuracy.hip) ---------------------------------------------------------------
+# ---- KariosAPI.analyze_accuracy (csrc/api_accuracy.hip, k_accuracy.hip) ------------------------------------------------------------
 ACCURACY_STAT_NAMES = tuple(f"{k}_{col}" for col in "xyc" for k in ("min", "max", "median", "mean", "std"))
 ACCURACY_MAX_ROWS = 1 << 24          # beyond it float32(n) is not n: numpy on the host
 
@@ -816,44 +816,66 @@ def _on_device(a):
     return hasattr(a, "data_ptr")
 
 
+def _torch_np_dtype(t):
+    return np.dtype(str(t.dtype).replace("torch.", ""))
+
+
+def _raster_arg(a, what, dtype=None):
+    """A 2-D raster with contiguous rows, numpy array or device tensor -> (on device, pointer argument, numpy dtype, H, W, row
+    stride, device or None).  `dtype` names the pixel type of a tensor that only stores its bit pattern."""
+    if not _on_device(a):
+        a = as_image(a)
+        return False, ptr(a), a.dtype, a.shape[0], a.shape[1], row_stride(a), None
+    if a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1):
+        raise ValueError(f"{what}: expected a 2-D tensor with contiguous rows")
+    dt = _torch_np_dtype(a)
+    if dtype is not None:
+        if np.dtype(dtype).itemsize != dt.itemsize:
+            raise ValueError(f"{what}: pixel type {np.dtype(dtype)} in {dt} storage")
+        dt = np.dtype(dtype)
+    H, W = int(a.shape[0]), int(a.shape[1])
+    return True, C.c_void_p(a.data_ptr()), dt, H, W, (int(a.stride(0)) if H > 1 else W), a.device
+
+
+def _mask_arg(mask, dev, H, W, what):
+    """The optional uint8 mask of an H x W raster, living where the raster lives -> (pointer argument or None, row stride)."""
+    if mask is None:
+        return None, 0
+    if dev:
+        import torch
+        if not _on_device(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or (W > 1 and mask.stride(1) != 1):
+            raise ValueError(f"{what}: the mask must be a uint8 tensor of the raster's shape with contiguous rows")
+        return C.c_void_p(mask.data_ptr()), (int(mask.stride(0)) if H > 1 else W)
+    m = np.asarray(mask)
+    if m.shape != (H, W):
+        raise ValueError(f"{what}: mask shape differs from the raster's")
+    m = as_image(m if m.dtype == np.uint8 else (m != 0).astype(np.uint8))
+    return ptr(m), row_stride(m)
+
+
+def _empty(shape, np_dtype, device):
+    """An uninitialised tensor on `device`, or a numpy array when `device` is None."""
+    if device is None:
+        return np.empty(shape, np_dtype)
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=device)
+
+
 def count_valid_pixels(arr, mask=None, ctx: Context | None = None) -> int:
     """np.count_nonzero of `arr` with the pixels under mask == 0 set to 0 (core.py:284-290): a 2-D uint8 / uint16 / int16 /
     float32 raster and an optional uint8 mask of its shape, both numpy arrays or both torch tensors on the context's device (rows
     contiguous, a row stride is fine).  float32 counts by its bits: NaN and denormals are non-zero, -0.0 is zero."""
-    if _on_device(arr):
-        import torch
-        if arr.dim() != 2 or (arr.shape[1] > 1 and arr.stride(1) != 1):
-            raise ValueError("count_valid_pixels: expected a 2-D tensor with contiguous rows")
-        dt = np.dtype(str(arr.dtype).replace("torch.", ""))
-        H, W = int(arr.shape[0]), int(arr.shape[1])
-        stride = int(arr.stride(0)) if H > 1 else W
-        img_arg, mask_arg, mstride = C.c_void_p(arr.data_ptr()), None, 0
-        if mask is not None:
-            if not _on_device(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or (W > 1 and mask.stride(1) != 1):
-                raise ValueError("count_valid_pixels: the mask must be a uint8 tensor of the raster's shape with contiguous rows")
-            mask_arg, mstride = C.c_void_p(mask.data_ptr()), (int(mask.stride(0)) if H > 1 else W)
-        what = "km_count_valid_pixels_dev"
-    else:
-        a = as_image(arr)
-        dt = a.dtype
-        H, W = a.shape
-        stride = row_stride(a)
-        img_arg, mask_arg, mstride = ptr(a), None, 0
-        if mask is not None:
-            m = np.asarray(mask)
-            if m.shape != a.shape:
-                raise ValueError("count_valid_pixels: mask shape differs from the raster's")
-            m = as_image(m if m.dtype == np.uint8 else (m != 0).astype(np.uint8))
-            mask_arg, mstride = ptr(m), row_stride(m)
-        what = "km_count_valid_pixels"
+    dev, img_arg, dt, H, W, stride, device = _raster_arg(arr, "count_valid_pixels")
+    mask_arg, mstride = _mask_arg(mask, dev, H, W, "count_valid_pixels")
+    what = "km_count_valid_pixels_dev" if dev else "km_count_valid_pixels"
     if dt not in PREP_DTYPES:
         raise KariosHipError(f"count_valid_pixels: unsupported pixel type {dt} (uint8, uint16, int16, float32)")
     if H < 1 or W < 1:
         return 0
     c = _ctx(ctx)
-    if _on_device(arr):
+    if dev:
         import torch
-        torch.cuda.synchronize(arr.device)
+        torch.cuda.synchronize(device)
     n = C.c_int64()
     c.check(getattr(c.lib, what)(c.handle, img_arg, _lib._DTYPES[dt], H, W, stride, mask_arg, mstride, C.byref(n)), what)
     return int(n.value)
@@ -934,15 +956,12 @@ def accuracy_statistics(dx, dy, score, confidence, carto: bool = False, factor=1
     c = _ctx(ctx)
     if dev:
         torch.cuda.synchronize(dx.device)
-        args = [C.c_void_p(a.data_ptr()) if n else None for a in cols]
-        what = "km_accuracy_stats_dev"
     else:
         cols = tuple(np.ascontiguousarray(a) for a in cols)
-        args = [ptr(a) if n else None for a in cols]
-        what = "km_accuracy_stats"
+    what = "km_accuracy_stats_dev" if dev else "km_accuracy_stats"
     res = _lib.AccuracyResult()
     q = (C.c_double * max(len(percents), 1))(*percents)
-    c.check(getattr(c.lib, what)(c.handle, *args, n, thr, int(bool(carto)), float(np.float32(factor)), len(percents), q, C.byref(res)), what)
+    c.check(getattr(c.lib, what)(c.handle, *_col_args(dev, cols, n), n, thr, int(bool(carto)), float(np.float32(factor)), len(percents), q, C.byref(res)), what)
     if res.n_nan:
         return _accuracy_host(*(to_host(a) for a in cols), confidence, carto, factor, percents)
     sample = int(res.sample)
@@ -956,13 +975,9 @@ def accuracy_statistics(dx, dy, score, confidence, carto: bool = False, factor=1
     return AccuracyStatistics(sample, 0, stats, tuple(ce), "device")
 
 
-# ---- ChipService.generate_chips (csrc/api_score.hip km_chip_select / km_chips, k_chips.hip) ----------------------------------------
+# ---- ChipService.generate_chips (csrc/api_chips.hip km_chip_select / km_chips, k_chips.hip) ----------------------------------------
 CHIP_SIZE = _lib.CHIP_SIZE
 CHIP_KSIZES = (1, 3, 5, 7, 9, 11)
-
-
-def _torch_np_dtype(t):
-    return np.dtype(str(t.dtype).replace("torch.", ""))
 
 
 def _f32_columns(cols, what, names):
@@ -1009,11 +1024,9 @@ def select_chip_points(x0, y0, score, width, height, threshold, grid=(5, 5), ctx
     if dev:
         import torch
         torch.cuda.synchronize(cols[0].device)
-        out = torch.empty(cap, dtype=torch.int32, device=cols[0].device)
-        c.check(c.lib.km_chip_select_dev(c.handle, *_col_args(dev, cols, n), *tail, C.c_void_p(out.data_ptr()), C.byref(count)), "km_chip_select_dev")
-    else:
-        out = np.empty(cap, np.int32)
-        c.check(c.lib.km_chip_select(c.handle, *_col_args(dev, cols, n), *tail, ptr(out), C.byref(count)), "km_chip_select")
+    out = _empty(cap, np.int32, cols[0].device if dev else None)
+    what = "km_chip_select_dev" if dev else "km_chip_select"
+    c.check(getattr(c.lib, what)(c.handle, *_col_args(dev, cols, n), *tail, *_col_args(dev, (out,), cap), C.byref(count)), what)
     return out[:count.value]
 
 
@@ -1047,54 +1060,35 @@ def extract_chips(ref, mon, x0, y0, dx, dy, ksize_ref=None, ksize_mon=None, ctx:
         raise ValueError("extract_chips: rasters and columns must all be numpy arrays or all be device tensors")
     if n > _lib.CHIP_MAX_ROWS:
         raise ValueError(f"extract_chips: {n} rows (at most 2^20)")
-    if dev:
-        import torch
-        if any(a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1) for a in (ref, mon)):
-            raise ValueError("extract_chips: expected 2-D tensors with contiguous rows")
-        dt, dt_m = _torch_np_dtype(ref), _torch_np_dtype(mon)
-        shapes = [(int(a.shape[0]), int(a.shape[1])) for a in (ref, mon)]
-        strides = [int(a.stride(0)) if a.shape[0] > 1 else int(a.shape[1]) for a in (ref, mon)]
-        img_args = [C.c_void_p(ref.data_ptr()), C.c_void_p(mon.data_ptr())]
-
-        def empty(shape, dtype):
-            return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=ref.device)
-
-        def address(a):
-            return a.data_ptr()
-    else:
-        ref, mon = as_image(ref), as_image(mon)
-        dt, dt_m = ref.dtype, mon.dtype
-        shapes = [ref.shape, mon.shape]
-        strides = [row_stride(ref), row_stride(mon)]
-        img_args = [ptr(ref), ptr(mon)]
-        empty = np.empty
-
-        def address(a):
-            return a.ctypes.data
+    if dev and any(a.dim() != 2 or (a.shape[1] > 1 and a.stride(1) != 1) for a in (ref, mon)):
+        raise ValueError("extract_chips: expected 2-D tensors with contiguous rows")
+    _, ref_arg, dt, Hr, Wr, sref, device = _raster_arg(ref, "extract_chips")
+    _, mon_arg, dt_m, Hm, Wm, smon, _ = _raster_arg(mon, "extract_chips")
     if dt != dt_m or dt not in PREP_DTYPES:
         raise KariosHipError(f"extract_chips: rasters of {dt} and {dt_m} (one of uint8, uint16, int16, float32 for both)")
-    if min(shapes[0] + shapes[1]) < CHIP_SIZE:
-        raise ValueError(f"extract_chips: rasters of {shapes[0]} and {shapes[1]} (at least {CHIP_SIZE} x {CHIP_SIZE})")
+    if min(Hr, Wr, Hm, Wm) < CHIP_SIZE:
+        raise ValueError(f"extract_chips: rasters of {(Hr, Wr)} and {(Hm, Wm)} (at least {CHIP_SIZE} x {CHIP_SIZE})")
     shape = (n, CHIP_SIZE, CHIP_SIZE)
-    res = ChipImages(ok=empty((n,), np.uint8), windows=empty((n, 4), np.int32), ref_raw=empty(shape, dt), mon_raw=empty(shape, dt),
-                     ref_u8=empty(shape, np.uint8), mon_u8=empty(shape, np.uint8), ref_lap=empty(shape, np.uint8) if kr else None,
-                     mon_lap=empty(shape, np.uint8) if km else None)
+    res = ChipImages(ok=_empty((n,), np.uint8, device), windows=_empty((n, 4), np.int32, device), ref_raw=_empty(shape, dt, device),
+                     mon_raw=_empty(shape, dt, device), ref_u8=_empty(shape, np.uint8, device), mon_u8=_empty(shape, np.uint8, device),
+                     ref_lap=_empty(shape, np.uint8, device) if kr else None, mon_lap=_empty(shape, np.uint8, device) if km else None)
     if n:
         c = _ctx(ctx)
         if dev:
-            torch.cuda.synchronize(ref.device)
-        out = _lib.ChipOutputs(*(address(getattr(res, k)) if getattr(res, k) is not None else None
-                                 for k in ("ref_raw", "mon_raw", "ref_u8", "mon_u8", "ref_lap", "mon_lap", "ok", "windows")))
+            import torch
+            torch.cuda.synchronize(device)
+        out = _lib.ChipOutputs(*((a.data_ptr() if dev else a.ctypes.data) if a is not None else None
+                                 for a in (res.ref_raw, res.mon_raw, res.ref_u8, res.mon_u8, res.ref_lap, res.mon_lap, res.ok, res.windows)))
         what = "km_chips_dev" if dev else "km_chips"
-        c.check(getattr(c.lib, what)(c.handle, *img_args, _lib._DTYPES[dt], shapes[0][0], shapes[0][1], shapes[1][0], shapes[1][1], strides[0], strides[1],
-                                     *_col_args(dev, cols, n), n, kr, km, C.byref(out)), what)
+        c.check(getattr(c.lib, what)(c.handle, ref_arg, mon_arg, _lib._DTYPES[dt], Hr, Wr, Hm, Wm, sref, smon, *_col_args(dev, cols, n), n, kr, km, C.byref(out)),
+                what)
         if dev:
             c.sync()
     res.ok = res.ok != 0
     return res
 
 
-# ---- the tracker's outlier clip (csrc/api_score.hip km_sigma_clip_dev, k_clip.hip) --------------------------------------------------
+# ---- the tracker's outlier clip (csrc/api_accuracy.hip km_sigma_clip_dev, k_clip.hip) -----------------------------------------------
 CLIP_MAX_ROWS = _lib.CLIP_MAX_ROWS
 
 
@@ -1198,7 +1192,7 @@ def sigma_clip(dx, dy, ctx: Context | None = None, return_rounds: bool = False):
     return (keep, rounds) if return_rounds else keep
 
 
-# ---- the report's numbers (csrc/api_prep.hip km_display_range, csrc/api_score.hip km_mean_profiles, k_report.hip) -------------------
+# ---- the report's numbers (csrc/api_prep.hip km_display_range, csrc/api_report.hip km_mean_profiles, k_report.hip) ------------------
 DISPLAY_MAX_NO_VALUES = _lib.DISPLAY_MAX_NO_VALUES
 PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = _lib.PROFILE_MAX, _lib.PROFILE_MAX_ROWS, _lib.PROFILE_MAX_BIN
 
@@ -1247,40 +1241,17 @@ def display_range(arr, mask=None, no_values=None, nodata=None, percents=(0.5, 99
     numpy arrays or both torch tensors on the context's device (rows contiguous; windows of wider buffers are fine, each with its own
     pitch).  A Python-number `nodata` compares with a float32 raster in float32 as numpy's does, an np.float64 in float64."""
     values, pp = _display_range_lists(no_values, percents)
-    if _on_device(arr):
-        import torch
-        if arr.dim() != 2 or (arr.shape[1] > 1 and arr.stride(1) != 1):
-            raise ValueError("display_range: expected a 2-D tensor with contiguous rows")
-        dt = _torch_np_dtype(arr)
-        H, W = int(arr.shape[0]), int(arr.shape[1])
-        stride = int(arr.stride(0)) if H > 1 else W
-        img_arg, mask_arg, mstride = C.c_void_p(arr.data_ptr()), None, 0
-        if mask is not None:
-            if not _on_device(mask) or mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or (W > 1 and mask.stride(1) != 1):
-                raise ValueError("display_range: the mask must be a uint8 tensor of the raster's shape with contiguous rows")
-            mask_arg, mstride = C.c_void_p(mask.data_ptr()), (int(mask.stride(0)) if H > 1 else W)
-        what = "km_display_range_dev"
-    else:
-        a = as_image(arr)
-        dt = a.dtype
-        H, W = a.shape
-        stride = row_stride(a)
-        img_arg, mask_arg, mstride = ptr(a), None, 0
-        if mask is not None:
-            m = np.asarray(mask)
-            if m.shape != a.shape:
-                raise ValueError("display_range: mask shape differs from the raster's")
-            m = as_image(m if m.dtype == np.uint8 else (m != 0).astype(np.uint8))
-            mask_arg, mstride = ptr(m), row_stride(m)
-        what = "km_display_range"
+    dev, img_arg, dt, H, W, stride, device = _raster_arg(arr, "display_range")
+    mask_arg, mstride = _mask_arg(mask, dev, H, W, "display_range")
+    what = "km_display_range_dev" if dev else "km_display_range"
     if dt not in PREP_DTYPES:
         raise KariosHipError(f"display_range: unsupported pixel type {dt} (uint8, uint16, int16, float32)")
     if H < 1 or W < 1:
         raise ValueError("display_range: empty raster")
     c = _ctx(ctx)
-    if _on_device(arr):
+    if dev:
         import torch
-        torch.cuda.synchronize(arr.device)
+        torch.cuda.synchronize(device)
     return _display_range_call(c, what, img_arg, dt, H, W, stride, mask_arg, mstride, values, nodata, pp)
 
 
@@ -1344,11 +1315,7 @@ def mean_profiles(profiles, ctx: Context | None = None):
         import torch
         torch.cuda.synchronize(cols[0].device)
     for i in range(k):
-        if dev:
-            import torch
-            o = [torch.empty(n, dtype=t, device=cols[0].device) for t in (torch.float32, torch.int32, torch.int32, torch.float32, torch.float32)]
-        else:
-            o = [np.empty(n, t) for t in (np.float32, np.int32, np.int32, np.float32, np.float32)]
+        o = [_empty(n, t, cols[0].device if dev else None) for t in (np.float32, np.int32, np.int32, np.float32, np.float32)]
         outs.append(o)
         args = _col_args(dev, (cols[2 * i], cols[2 * i + 1]) + tuple(o), n)
         r = recs[i]
@@ -1362,7 +1329,7 @@ def mean_profiles(profiles, ctx: Context | None = None):
     return [ProfileColumns(*(a[:groups[i]] for a in outs[i])) for i in range(k)]
 
 
-# ---- the report's products and the altitude figure's numbers (csrc/api_score.hip km_point_rasters, km_sample_points, km_box_stats,
+# ---- the report's products and the altitude figure's numbers (csrc/api_report.hip km_point_rasters, km_sample_points, km_box_stats,
 # k_products.hip) --------------------------------------------------------------------------------------------------------------------
 BOX_STAT_NAMES = ("q1", "med", "q3", "iqr", "cilo", "cihi", "whislo", "whishi")     # the columns of km_box_stats, in its order
 
@@ -1377,10 +1344,7 @@ def _raster_shape(shape, what):
 def _out_plane(out, shape, np_dtype, dev, device, what):
     """The caller's buffer for one output - a window of a wider buffer is fine - or a fresh one."""
     if out is None:
-        if dev:
-            import torch
-            return torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=device)
-        return np.empty(shape, np_dtype)
+        return _empty(shape, np_dtype, device)
     if _on_device(out) != dev:
         raise ValueError(f"{what}: the output must live where the columns live")
     dt = _torch_np_dtype(out) if dev else out.dtype
@@ -1441,20 +1405,7 @@ def sample_points(raster, x0, y0, dtype=None, ctx: Context | None = None):
     dev, cols, n = _f32_columns((x0, y0), "sample_points", "x0 and y0")
     if _on_device(raster) != dev:
         raise ValueError("sample_points: raster and columns must all be numpy arrays or all be device tensors")
-    if dev:
-        if raster.dim() != 2 or (raster.shape[1] > 1 and raster.stride(1) != 1):
-            raise ValueError("sample_points: expected a 2-D tensor with contiguous rows")
-        dt = _torch_np_dtype(raster)
-        if dtype is not None:
-            if np.dtype(dtype).itemsize != dt.itemsize:
-                raise ValueError(f"sample_points: pixel type {np.dtype(dtype)} in {dt} storage")
-            dt = np.dtype(dtype)
-        H, W = int(raster.shape[0]), int(raster.shape[1])
-        stride = int(raster.stride(0)) if H > 1 else W
-        img_arg = C.c_void_p(raster.data_ptr())
-    else:
-        a = as_image(raster)
-        dt, (H, W), stride, img_arg = a.dtype, a.shape, row_stride(a), ptr(a)
+    _, img_arg, dt, H, W, stride, device = _raster_arg(raster, "sample_points", dtype)
     if dt not in PREP_DTYPES:
         raise KariosHipError(f"sample_points: unsupported pixel type {dt} (uint8, uint16, int16, float32)")
     if H < 1 or W < 1:
@@ -1464,10 +1415,8 @@ def sample_points(raster, x0, y0, dtype=None, ctx: Context | None = None):
     c = _ctx(ctx)
     if dev:
         import torch
-        torch.cuda.synchronize(raster.device)
-        out = torch.empty(n, dtype=raster.dtype, device=raster.device)
-    else:
-        out = np.empty(n, dt)
+        torch.cuda.synchronize(device)
+    out = _empty(n, _torch_np_dtype(raster) if dev else dt, device)      # (a tensor's storage type)
     bad = C.c_int32()
     what = "km_sample_points_dev" if dev else "km_sample_points"
     c.check(getattr(c.lib, what)(c.handle, img_arg, _lib._DTYPES[dt], H, W, stride, n, *_col_args(dev, cols + (out,), n), C.byref(bad)), what)
@@ -1499,15 +1448,12 @@ def box_stats(values, positions, bin_size, ctx: Context | None = None) -> BoxSta
         raise ValueError(f"box_stats: bin size {bin_size} (an integer, 1 .. 2^24)")
     c = _ctx(ctx)
     k = _lib.BOX_STATS
+    device = cols[0].device if dev else None
     if dev:
         import torch
-        device = cols[0].device
         torch.cuda.synchronize(device)
-        key, count, mean = (torch.empty(n, dtype=t, device=device) for t in (torch.float32, torch.int32, torch.float32))
-        stats, cls = torch.empty((k, n), dtype=torch.float64, device=device), torch.empty(n, dtype=torch.int8, device=device)
-    else:
-        key, count, mean = (np.empty(n, t) for t in (np.float32, np.int32, np.float32))
-        stats, cls = np.empty((k, n), np.float64), np.empty(n, np.int8)
+    key, count, mean = (_empty(n, t, device) for t in (np.float32, np.int32, np.float32))
+    stats, cls = _empty((k, n), np.float64, device), _empty(n, np.int8, device)
     groups = C.c_int32()
     a = _col_args(dev, cols + (key, count, mean, stats, cls), n)
     what = "km_box_stats_dev" if dev else "km_box_stats"

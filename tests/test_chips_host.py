@@ -334,7 +334,7 @@ def test_abi_carries_the_entry_points():
     for name, value in (("KM_CHIP_SIZE", _lib.CHIP_SIZE), ("KM_CHIP_MAX_GRID", _lib.CHIP_MAX_GRID), ("KM_CHIP_PICKS", _lib.CHIP_PICKS)):
         assert f"#define {name} {value}" in header
     # the entry points live in a file the host build already lists
-    assert all(f"int {name}(" in open(os.path.join(ROOT, "karios_amd", "csrc", "api_score.hip")).read() for name in ENTRY_POINTS)
+    assert all(f"int {name}(" in open(os.path.join(ROOT, "karios_amd", "csrc", "api_chips.hip")).read() for name in ENTRY_POINTS)
 
 
 def test_host_build_of_the_api_files_still_links():

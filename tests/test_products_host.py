@@ -417,7 +417,7 @@ ENTRY_POINTS = ("km_point_rasters", "km_point_rasters_dev", "km_sample_points", 
 def test_abi_carries_the_entry_points():
     import ctypes
     header = open(os.path.join(ROOT, "include", "karios_hip.h")).read()
-    api = open(os.path.join(ROOT, "karios_amd", "csrc", "api_score.hip")).read()      # a file the host build already lists
+    api = open(os.path.join(ROOT, "karios_amd", "csrc", "api_report.hip")).read()     # a file the host build lists
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in ENTRY_POINTS:
         assert name in _lib.SIGNATURES and f"int {name}(" in header and hasattr(lib, name) and f"int {name}(" in api

@@ -369,8 +369,8 @@ def test_host_profiles_equal_the_restatement(program, profile_cases):
 
 
 # ---- 3. the ABI, the host build, the arguments ----------------------------------------------------------------------------------------------
-ENTRY_POINTS = {"km_display_range": "api_prep.hip", "km_display_range_dev": "api_prep.hip", "km_mean_profiles": "api_score.hip",
-                "km_mean_profiles_dev": "api_score.hip"}
+ENTRY_POINTS = {"km_display_range": "api_prep.hip", "km_display_range_dev": "api_prep.hip", "km_mean_profiles": "api_report.hip",
+                "km_mean_profiles_dev": "api_report.hip"}
 
 
 def test_abi_carries_the_entry_points():
