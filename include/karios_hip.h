@@ -802,6 +802,57 @@ int km_box_stats(km_ctx *ctx, int n, const float *values, const float *positions
 int km_box_stats_dev(km_ctx *ctx, int n, const float *d_values, const float *d_positions, int bin_size, float *d_key, int32_t *d_count,
                      float *d_mean, double *d_stats, int8_t *d_cls, int32_t *n_groups);
 
+/* ---- the numbers of the circular-error figure on resident data (karios/report/circular_error_plot.py:181-228, 254-303, 359-368);
+ * tests/ce_figure_restatement.py is the definition.  numpy builds the bin edges and scipy fits the spline, both on the host and from
+ * a handful of numbers, so one figure is THREE calls with the same columns, in this order; the context keeps the sample between them.
+ *
+ * KM_CE_SAMPLE  the sample of km_accuracy_stats (rows with (double)score > thr in row order, dy negated with carto != 0; n <= 2^24),
+ *               scaled: x = dx (float)res, y = +-dy (float)res, radial error sqrt(x x + y y), each operation one float32 rounding.
+ *               *block: the sample's size, its rows with a NaN in dx or dy (the caller then takes numpy: nothing below is defined),
+ *               minimum and maximum of dx, +-dy, x, y, and np.mean / np.std of x and of y in float32 as km_accuracy_stats forms them.
+ *               An empty sample leaves the extremes undefined.
+ * KM_CE_COUNTS  np.histogram of x on edges_x (bins_x + 1 float32 edges, numpy's linspace over the range; bins_x <= KM_CE_MAX_BINS;
+ *               0 skips the axis) -> hist_x[bins_x], the same for y, and np.histogram2d(x, y, bins=10) on edges_grid (11 edges of x,
+ *               then 11 of y) -> counts_grid[100], row-major with x first.  Edges and counts are host memory in both forms.
+ * KM_CE_CURVES  z = the bicubic spline (tx, ty: 14 knots each, coef: 100 coefficients, as scipy's RectBivariateSpline on the 10 bin
+ *               centres gives them) at every point inside box = {cx[0], cx[9], cy[0], cy[9]} (float32 comparisons), evaluated as
+ *               FITPACK's bispeu does in float64 and rounded to float32; NaN outside.  scatter_x / _y / _z: the sample in the stable
+ *               ascending order of z, NaN last; radial: the radial errors ascending (capacity n each: host memory in the host form,
+ *               device memory in the device form).  *tail: the elements [k - 1], [k] of `radial` for 0.9 and for 0.95 as
+ *               km_accuracy_stats picks them, and the number of NaN in z.
+ * block and tail are host memory in both forms.  The device form reads the columns from the device and copies nothing else to the
+ * host than the block, the counts and the tail; it completes the context stream before it returns. */
+#define KM_CE_SAMPLE 0
+#define KM_CE_COUNTS 1
+#define KM_CE_CURVES 2
+#define KM_CE_MAX_BINS 65536
+typedef struct km_ce_block {
+    int32_t sample, n_nan;
+    float ext[8];                              /* min, max of dx; of +-dy; of x; of y */
+    float mu_x, sigma_x, mu_y, sigma_y;
+    float pad[2];
+} km_ce_block;
+typedef struct km_ce_tail {
+    float order[4];                            /* r[k - 1], r[k] for 0.9, then for 0.95 */
+    int32_t n_outside;                         /* points outside the grid of centres: NaN in z */
+    int32_t pad[3];
+} km_ce_tail;
+typedef struct km_ce_job {
+    int32_t stage, n, carto, pad;
+    const float *dx, *dy, *score;              /* every stage: the same columns */
+    double thr, res;
+    km_ce_block *block;                        /* KM_CE_SAMPLE */
+    const float *edges_x, *edges_y, *edges_grid;   /* KM_CE_COUNTS */
+    int32_t bins_x, bins_y;
+    uint32_t *hist_x, *hist_y, *counts_grid;
+    const double *tx, *ty, *coef;              /* KM_CE_CURVES */
+    const float *box;
+    float *scatter_x, *scatter_y, *scatter_z, *radial;
+    km_ce_tail *tail;
+} km_ce_job;
+int km_ce_figure(km_ctx *ctx, const km_ce_job *job);
+int km_ce_figure_dev(km_ctx *ctx, const km_ce_job *job);
+
 #ifdef __cplusplus
 }
 #endif

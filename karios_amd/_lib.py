@@ -84,6 +84,31 @@ class Profile(C.Structure):
                 ("mean", C.c_void_p), ("std", C.c_void_p), ("bin_size", C.c_int32)]
 
 
+class CeBlock(C.Structure):
+    """km_ce_block of include/karios_hip.h."""
+    _fields_ = [("sample", C.c_int32), ("n_nan", C.c_int32), ("ext", C.c_float * 8), ("mu_x", C.c_float), ("sigma_x", C.c_float),
+                ("mu_y", C.c_float), ("sigma_y", C.c_float), ("pad", C.c_float * 2)]
+
+
+class CeTail(C.Structure):
+    """km_ce_tail of include/karios_hip.h."""
+    _fields_ = [("order", C.c_float * 4), ("n_outside", C.c_int32), ("pad", C.c_int32 * 3)]
+
+
+class CeJob(C.Structure):
+    """km_ce_job of include/karios_hip.h."""
+    _fields_ = [("stage", C.c_int32), ("n", C.c_int32), ("carto", C.c_int32), ("pad", C.c_int32),
+                ("dx", C.c_void_p), ("dy", C.c_void_p), ("score", C.c_void_p), ("thr", C.c_double), ("res", C.c_double),
+                ("block", C.POINTER(CeBlock)),
+                ("edges_x", C.c_void_p), ("edges_y", C.c_void_p), ("edges_grid", C.c_void_p), ("bins_x", C.c_int32), ("bins_y", C.c_int32),
+                ("hist_x", C.c_void_p), ("hist_y", C.c_void_p), ("counts_grid", C.c_void_p),
+                ("tx", C.c_void_p), ("ty", C.c_void_p), ("coef", C.c_void_p), ("box", C.c_void_p),
+                ("scatter_x", C.c_void_p), ("scatter_y", C.c_void_p), ("scatter_z", C.c_void_p), ("radial", C.c_void_p),
+                ("tail", C.POINTER(CeTail))]
+
+
+CE_SAMPLE, CE_COUNTS, CE_CURVES = 0, 1, 2   # KM_CE_*: the stages of km_ce_figure
+CE_MAX_BINS = 65536            # KM_CE_MAX_BINS
 DISPLAY_MAX_NO_VALUES = 16     # KM_DISPLAY_MAX_NO_VALUES
 PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = 8, 1 << 20, 1 << 24   # KM_PROFILE_MAX; rows and bin size km_mean_profiles takes
 BOX_STATS = 8                  # KM_BOX_STATS: q1, med, q3, iqr, cilo, cihi, whislo, whishi
@@ -213,6 +238,8 @@ SIGNATURES = {
     "km_display_range_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _sz, _pd, _pd, _i, _i, _pd, C.POINTER(DisplayRangeResult), _pd, _pd, _pd]),
     "km_mean_profiles": (_i, [_vp, _i, _i, C.POINTER(Profile), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "km_mean_profiles_dev": (_i, [_vp, _i, _i, C.POINTER(Profile), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "km_ce_figure": (_i, [_vp, C.POINTER(CeJob)]),
+    "km_ce_figure_dev": (_i, [_vp, C.POINTER(CeJob)]),
     "km_point_rasters": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _sz, C.POINTER(C.c_int32)]),
     "km_point_rasters_dev": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz, _sz, C.POINTER(C.c_int32)]),
     "km_sample_points": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _vp, _vp, C.POINTER(C.c_int32)]),

@@ -1,8 +1,9 @@
 """`GeometricStat` of karios/accuracy_analysis/accuracy_statistics.py with the numbers computed by `ops.accuracy_statistics`
 (csrc/k_accuracy.hip): the sample above the confidence threshold, minimum / maximum / median / mean / standard deviation of
 dx, dy and the score, and the CE percentiles of the radial error.  The attribute names and the text written to `correl_res.txt`
-are the reference's; the statistics are np.float32 scalars, so `str()` of them reads the same.  `display_results` and
-`get_string_block` (log and plot text) are not mirrored."""
+are the reference's; the statistics are np.float32 scalars, so `str()` of them reads the same.  `get_string_block` gives the
+reference's text block; `display_results` (log text) is not mirrored.  `columns` and `device_sample` hand the sample on where it
+lives (karios_amd.report.circular_error)."""
 from __future__ import annotations
 
 import os
@@ -70,6 +71,31 @@ class GeometricStat:
     v_x_th = property(lambda self: self._host_sample()[0])
     v_y_th = property(lambda self: self._host_sample()[1])
     v_c_th = property(lambda self: self._host_sample()[2])
+
+    @property
+    def columns(self):
+        """(dx, dy, score, threshold, carto) as they were given: what `ops.accuracy_statistics` and `ops.ce_figure` take."""
+        return self._dx, self._dy, self.v_c, self.confidence, self._carto
+
+    def device_sample(self):
+        """The sample's columns (x, y, score) where the frame's columns live: device tensors stay on the device, compacted there in
+        row order with the comparison `ops.accuracy_statistics` makes; numpy columns give `v_x_th`, `v_y_th`, `v_c_th`."""
+        if not hasattr(self.v_c, "data_ptr"):
+            return self._host_sample()
+        import torch
+        t = self.confidence
+        thr = float(t) if isinstance(t, np.float64) else float(np.float32(t))
+        keep = self.v_c.to(torch.float64) > thr
+        return self.v_x[keep], self.v_y[keep], self.v_c[keep]
+
+    def get_string_block(self, scale_factor, direction="x"):
+        """The text block of one direction as the reference writes it (after `compute_stats`)."""
+        pick = {name: getattr(self, f"{name}_{direction}") for name in ("min", "max", "mean", "std", "median")}
+        head = f" Conf_Value : {self.confidence:.2f}" if direction == "x" else f" Conf_Value :{self.confidence:.2f}"
+        lines = [head, f" %Conf Px   :{self.percentage_of_pixel:.2f}%", f"Minimum    : {(pick['min'] * scale_factor):.2f}",
+                 f"Maximum   : {(pick['max'] * scale_factor):.2f}", f"Mean          : {(pick['mean'] * scale_factor):.2f}",
+                 f"Std Dev      : {(pick['std'] * scale_factor):.2f}", f"Median       : {(pick['median'] * scale_factor):.2f}"]
+        return "\n ".join(lines)
 
     def compute_stats(self, nb_pixels, confidence_threshold=None):
         if confidence_threshold is not None:

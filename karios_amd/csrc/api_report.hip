@@ -1,9 +1,14 @@
 // mean_profile of the report's figures (report/commons.py:49-71); the report's products (report/product_generator.py:138-218), the altitude
 // column (core.py:1049-1053) and the box statistics of the altitude figure (report/shift_by_alt_plot.py:127-171): every check in front of
-// the first launch or copy.
+// the first launch or copy.  The numbers of the circular-error figure (report/circular_error_plot.py), in three stages.
 #include "api_internal.hpp"
+#include "k_ce.hpp"
 #include "k_products.hpp"
 #include "k_report.hpp"
+
+#include <math.h>
+#include <string.h>
+#include <vector>
 
 // ---- mean_profile of the report's figures
 namespace {
@@ -291,6 +296,138 @@ int km_box_stats(km_ctx *c, int n, const float *values, const float *positions, 
     KM_D2H(c, cls, b.cls, (size_t)n);
     KM_FLUSH(c);
     return KM_OK;
+}
+
+}  // extern "C"
+
+// ---- the circular-error figure's numbers (karios/report/circular_error_plot.py): three stages on one sample, which the context keeps
+namespace {
+
+int check_ce_args(km_ctx *c, const km_ce_job *j)
+{
+    if (!j) return km_fail(c, KM_E_ARG, "ce_figure: null job");
+    if (j->n < 0 || j->n > (1 << 24)) return km_fail(c, KM_E_ARG, "ce_figure: %d rows (0 .. 2^24)", j->n);
+    if (j->n > 0 && (!j->dx || !j->dy || !j->score)) return km_fail(c, KM_E_ARG, "ce_figure: null column");
+    switch (j->stage) {
+    case KM_CE_SAMPLE:
+        if (j->thr != j->thr) return km_fail(c, KM_E_ARG, "ce_figure: the threshold is NaN");
+        if (!isfinite((float)j->res)) return km_fail(c, KM_E_ARG, "ce_figure: the resolution is not a finite float32");
+        if (!j->block) return km_fail(c, KM_E_ARG, "ce_figure: null block");
+        return KM_OK;
+    case KM_CE_COUNTS:
+        if (j->bins_x < 0 || j->bins_x > KM_CE_MAX_BINS || j->bins_y < 0 || j->bins_y > KM_CE_MAX_BINS)
+            return km_fail(c, KM_E_ARG, "ce_figure: %d and %d bins (0 .. %d each)", j->bins_x, j->bins_y, KM_CE_MAX_BINS);
+        if ((j->bins_x && (!j->edges_x || !j->hist_x)) || (j->bins_y && (!j->edges_y || !j->hist_y)) || !j->edges_grid || !j->counts_grid)
+            return km_fail(c, KM_E_ARG, "ce_figure: null edges or counts");
+        break;
+    case KM_CE_CURVES:
+        if (!j->tx || !j->ty || !j->coef || !j->box || !j->scatter_x || !j->scatter_y || !j->scatter_z || !j->radial || !j->tail)
+            return km_fail(c, KM_E_ARG, "ce_figure: null spline or output");
+        break;
+    default: return km_fail(c, KM_E_ARG, "ce_figure: stage %d", j->stage);
+    }
+    if (j->n == 0 || c->ce_rows != j->n || c->ce_cols != j->dx || c->ce_sample < 1)
+        return km_fail(c, KM_E_ARG, "ce_figure: stage %d needs KM_CE_SAMPLE of the same columns first, with a sample that is not empty", j->stage);
+    return KM_OK;
+}
+
+int ce_sample_stage(km_ctx *c, const km_ce_job *j, const float *d_dx, const float *d_dy, const float *d_score)
+{
+    c->ce_rows = -1;
+    *j->block = km_ce_block();
+    if (j->n == 0) return KM_OK;
+    const size_t cap = (size_t)j->n;
+    kce_state *s = (kce_state *)km_ws(c, WS_CE_STATE, sizeof(kce_state));
+    float *cols = (float *)km_ws(c, WS_AC_COLS, cap * 3 * sizeof(float));
+    float *scaled = (float *)km_ws(c, WS_CE_COLS, cap * 4 * sizeof(float));
+    float *bsum = (float *)km_ws(c, WS_AC_BSUM, (size_t)ka_nblocks(j->n) * 3 * sizeof(float));
+    if (!s || !cols || !scaled || !bsum) return KM_E_NOMEM;
+    int rc;
+    if ((rc = ka_compact(c, d_dx, d_dy, d_score, j->n, j->thr, j->carto, cols, &s->st)) || (rc = kce_scale(c, cols, j->n, (float)j->res, scaled, s)) ||
+        (rc = ka_block_sums(c, scaled, j->n, &s->scaled, 0, bsum)) || (rc = ka_finish(c, bsum, j->n, &s->scaled, 0)) ||
+        (rc = ka_block_sums(c, scaled, j->n, &s->scaled, 1, bsum)) || (rc = ka_finish(c, bsum, j->n, &s->scaled, 1)) || (rc = kce_block(c, s)))
+        return rc;
+    KM_D2H(c, j->block, &s->block, sizeof(km_ce_block));
+    KM_FLUSH(c);
+    c->ce_rows = j->n; c->ce_sample = j->block->sample; c->ce_cols = j->dx;
+    return KM_OK;
+}
+
+int ce_counts_stage(km_ctx *c, const km_ce_job *j)
+{
+    kce_state *s = (kce_state *)km_ws_peek(c, WS_CE_STATE);
+    const float *scaled = (const float *)km_ws_peek(c, WS_CE_COLS);
+    // WS_CE_TAB: edges of x (bins_x + 1) | of y (bins_y + 1) | of the grid (22) | counters of x | of y | of the grid (100), zero
+    const size_t bx = (size_t)j->bins_x, by = (size_t)j->bins_y, ng = 2 * (ce::GRID + 1), nc = ce::GRID * ce::GRID;
+    const size_t off_y = bx + 1, off_g = off_y + by + 1, off_cx = off_g + ng, off_cy = off_cx + bx, off_cg = off_cy + by, words = off_cg + nc;
+    uint32_t *tab = (uint32_t *)km_ws(c, WS_CE_TAB, words * sizeof(uint32_t));
+    if (!s || !scaled || !tab) return s && scaled ? KM_E_NOMEM : km_fail(c, KM_E_ARG, "ce_figure: the sample has left the context");
+    std::vector<uint32_t> host(words, 0u);
+    if (bx) memcpy(host.data(), j->edges_x, (bx + 1) * sizeof(float));
+    if (by) memcpy(host.data() + off_y, j->edges_y, (by + 1) * sizeof(float));
+    memcpy(host.data() + off_g, j->edges_grid, ng * sizeof(float));
+    int rc;
+    if ((rc = h2d_now(c, tab, host.data(), words * sizeof(uint32_t)))) return rc;
+    const kce_axis ax = {(const float *)tab, tab + off_cx, j->bins_x}, ay = {(const float *)(tab + off_y), tab + off_cy, j->bins_y};
+    if ((rc = kce_axis_hist(c, scaled, j->n, s, ax, ay)) || (rc = kce_grid_hist(c, scaled, j->n, s, (const float *)(tab + off_g), tab + off_cg))) return rc;
+    if (bx) KM_D2H(c, j->hist_x, tab + off_cx, bx * sizeof(uint32_t));
+    if (by) KM_D2H(c, j->hist_y, tab + off_cy, by * sizeof(uint32_t));
+    KM_D2H(c, j->counts_grid, tab + off_cg, nc * sizeof(uint32_t));
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+int ce_curves_stage(km_ctx *c, const km_ce_job *j, bool dev)
+{
+    const size_t cap = (size_t)j->n, got = (size_t)c->ce_sample;
+    kce_state *s = (kce_state *)km_ws_peek(c, WS_CE_STATE);
+    float *scaled = (float *)km_ws_peek(c, WS_CE_COLS);
+    kce_spline *d_sp = (kce_spline *)km_ws(c, WS_CE_TAB, sizeof(kce_spline));
+    unsigned long long *k0 = (unsigned long long *)km_ws(c, WS_AC_KEYS0, 2 * cap * sizeof(unsigned long long));
+    unsigned long long *k1 = (unsigned long long *)km_ws(c, WS_AC_KEYS1, 2 * cap * sizeof(unsigned long long));
+    float *io = dev ? nullptr : (float *)km_ws(c, WS_CE_IO, 4 * cap * sizeof(float));
+    if (!s || !scaled) return km_fail(c, KM_E_ARG, "ce_figure: the sample has left the context");
+    if (!d_sp || !k0 || !k1 || (!dev && !io)) return KM_E_NOMEM;
+    kce_spline sp;
+    memcpy(sp.tx, j->tx, sizeof sp.tx); memcpy(sp.ty, j->ty, sizeof sp.ty); memcpy(sp.c, j->coef, sizeof sp.c); memcpy(sp.box, j->box, sizeof sp.box);
+    int rc;
+    if ((rc = h2d_now(c, d_sp, &sp, sizeof sp))) return rc;
+    float *out[4] = {dev ? j->scatter_x : io, dev ? j->scatter_y : io + cap, dev ? j->scatter_z : io + 2 * cap, dev ? j->radial : io + 3 * cap};
+    if ((rc = kce_density_keys(c, scaled, j->n, s, d_sp, scaled + 3 * cap, k0)) ||
+        (rc = kce_sort_gather(c, scaled, scaled + 3 * cap, k0, k1, j->n, s, out[0], out[1], out[2], out[3])))
+        return rc;
+    KM_D2H(c, j->tail, &s->tail, sizeof(km_ce_tail));
+    if (!dev) {
+        float *dst[4] = {j->scatter_x, j->scatter_y, j->scatter_z, j->radial};
+        for (int k = 0; k < 4; k++) KM_D2H(c, dst[k], out[k], got * sizeof(float));
+    }
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int km_ce_figure_dev(km_ctx *c, const km_ce_job *job)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_ce_args(c, job))) return rc;
+    if (job->stage == KM_CE_SAMPLE) return ce_sample_stage(c, job, job->dx, job->dy, job->score);
+    return job->stage == KM_CE_COUNTS ? ce_counts_stage(c, job) : ce_curves_stage(c, job, true);
+}
+
+int km_ce_figure(km_ctx *c, const km_ce_job *job)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_ce_args(c, job))) return rc;
+    if (job->stage == KM_CE_COUNTS) return ce_counts_stage(c, job);
+    if (job->stage == KM_CE_CURVES) return ce_curves_stage(c, job, false);
+    const size_t cap = job->n > 0 ? (size_t)job->n : 1;
+    const float *src[3] = {job->dx, job->dy, job->score};
+    float *in;
+    if ((rc = upload_columns(c, WS_AC_IN, src, 3, job->n, &in))) return rc;
+    return ce_sample_stage(c, job, in, in + cap, in + 2 * cap);
 }
 
 }  // extern "C"

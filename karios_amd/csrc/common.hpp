@@ -204,6 +204,10 @@ enum km_slot {
     WS_RP_SCAN,     //   tile sums of that scan
     WS_RP_IO,       //   columns and outputs of the host-API form
     WS_PD_MISC,     // api_report.hip (box statistics; its keys, flags and scan use the WS_RP_* slots): gathered values, heads, group indices, block sums
+    WS_CE_STATE,    // api_report.hip (circular-error figure; the sample itself goes through the WS_AC_* slots): kce_state, kept between the stages
+    WS_CE_COLS,     //   x | y | radial error of the scaled sample, kept between the stages; then the density z
+    WS_CE_TAB,      //   the edges of a stage and its counters
+    WS_CE_IO,       //   columns and outputs of the host-API form
     WS_COUNT
 };
 
@@ -316,6 +320,9 @@ struct km_ctx {
     km_window window;                    // km_set_image_window
     size_t band_capk = 0;                // km_band_eigen_dev -> km_band_keys_dev: capacity of the candidate keys left in WS_KEYS0
     bool band_fused = false;             //   ... emitted by the fused kernel (else: eig map in WS_EIG, candidates still to be scanned)
+    int ce_rows = -1;                    // km_ce_figure: rows of the figure whose sample sits in WS_CE_COLS (-1: none), ...
+    int ce_sample = 0;                   //   ... the sample's size and ...
+    const float *ce_cols = nullptr;      //   ... the device columns (dx) it was taken from
     void *frame_sink = nullptr;          // km_set_frame_sink: device-side copy of every frame block
     size_t frame_sink_cap = 0;
     size_t frame_sink_pitch = 0;         // km_set_frame_sink_pitch: distance between the blocks of a batched submission (0: block size)

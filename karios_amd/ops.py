@@ -1460,3 +1460,182 @@ def box_stats(values, positions, bin_size, ctx: Context | None = None) -> BoxSta
     c.check(getattr(c.lib, what)(c.handle, n, a[0], a[1], int(bin_size), *a[2:], C.byref(groups)), what)
     g = groups.value
     return BoxStats(key[:g], count[:g], mean[:g], [stats[j, :g] for j in range(k)], cls)
+
+
+# ---- the circular-error figure's numbers (csrc/api_report.hip km_ce_figure, k_ce.hip) ------------------------------------------------
+CE_MAX_BINS = _lib.CE_MAX_BINS      # bins of one axis histogram the device counts; beyond it numpy on a host copy
+CE_FIELDS = ("hist_x", "bins_x", "hist_y", "bins_y", "mu_x", "sigma_x", "mu_y", "sigma_y", "scatter_x", "scatter_y", "scatter_z", "counts2d",
+             "x_edges", "y_edges", "radial", "plot_limit", "ce90", "ce95", "sample")
+
+
+class CeFigure:
+    """Result of `ce_figure`, what `CircularErrorPlot._plot` hands to matplotlib: `hist_x` (int64) on `bins_x` (float32 edges) and
+    the same for y; `mu_*`, `sigma_*` of the scaled columns (np.float32); `scatter_x`, `scatter_y`, `scatter_z` in drawing order
+    and `radial` ascending (float32, `sample` rows; device tensors for device input); `counts2d` (float64, 10 x 10) on `x_edges`,
+    `y_edges`; `plot_limit`, `ce90`, `ce95` (np.float32).  `path` is "device" or "host"; `host_hist_x` / `host_hist_y` tell that
+    numpy counted that axis on a host copy (more than CE_MAX_BINS bins); `n_outside` points lie outside the grid of bin centres
+    (NaN density, drawn last)."""
+
+    def __init__(self, **kw):
+        self.path, self.host_hist_x, self.host_hist_y, self.n_outside = "device", False, False, 0
+        self.__dict__.update(kw)
+
+
+def _ce_histogram_host(vect, img_res):
+    """`_compute_histogram`'s numpy expression (circular_error_plot.py:185-207)."""
+    v_max = np.max([np.abs(np.max(vect)), np.abs(np.min(vect))])
+    return np.histogram(vect * img_res, bins="sqrt", range=(-v_max * img_res, v_max * img_res))
+
+
+def _ce_host(dx, dy, score, threshold, img_res, carto):
+    """The reference's own numpy / scipy expressions (circular_error_plot.py:181-228, 254-303, 359-368) on host arrays of any dtype;
+    only the drawing order is this project's: stable."""
+    from scipy.interpolate import interpn
+    dx, dy, score = np.asarray(dx), np.asarray(dy), np.asarray(score)
+    keep = score > threshold
+    vx, vy = dx[keep], (-dy if carto else dy)[keep]
+    r = CeFigure(path="host", sample=int(vx.size))
+    (r.hist_x, r.bins_x), (r.hist_y, r.bins_y) = _ce_histogram_host(vx, img_res), _ce_histogram_host(vy, img_res)
+    x, y = vx * img_res, vy * img_res
+    with np.errstate(invalid="ignore"):
+        r.mu_x, r.sigma_x, r.mu_y, r.sigma_y = np.mean(x), np.std(x), np.mean(y), np.std(y)
+        r.plot_limit = np.max([np.max(np.abs(x)), np.max(np.abs(y))])
+        r.counts2d, r.x_edges, r.y_edges = np.histogram2d(x, y, bins=10)
+        z = interpn((0.5 * (r.x_edges[1:] + r.x_edges[:-1]), 0.5 * (r.y_edges[1:] + r.y_edges[:-1])), r.counts2d, np.vstack([x, y]).T,
+                    method="splinef2d", bounds_error=False)
+        idx = np.argsort(z, kind="stable")
+        r.scatter_x, r.scatter_y, r.scatter_z = x[idx], y[idx], z[idx]
+        r.radial = np.sort(np.sqrt(x * x + y * y))
+    r.n_outside = int(np.count_nonzero(np.isnan(z)))
+    r.ce90, r.ce95 = _accuracy_host(dx, dy, score, threshold, carto, img_res, (0.9, 0.95)).ce
+    return r
+
+
+def _ce_axis_edges(lo, hi, v_min, v_max, n, res32):
+    """np.histogram(bins="sqrt", range=...)'s edges (numpy/lib/_histograms_impl.py `_get_bin_edges`) from the extremes of the unscaled
+    (lo, hi) and the scaled (v_min, v_max) column of n rows -> float32 edges."""
+    bound = max(np.float32(abs(hi)), np.float32(abs(lo)))
+    last = np.float32(bound * res32)
+    first = np.float32(-last)
+    if first == last:
+        first, last = np.float32(first - np.float32(0.5)), np.float32(last + np.float32(0.5))
+    width = np.float32(v_max - v_min) / np.sqrt(n)
+    n_bins = int(np.ceil(np.float32(last - first) / width)) if width else 1
+    edges = np.linspace(first, last, n_bins + 1, endpoint=True, dtype=np.float32)
+    if np.any(edges[:-1] >= edges[1:]):
+        raise ValueError(f"Too many bins for data range. Cannot create {n_bins} finite-sized bins.")
+    return edges
+
+
+def _ce_grid_edges(lo, hi):
+    """np.histogramdd's edges of one axis: 11 float32 edges over [min, max], widened by 0.5 when they are equal."""
+    if lo == hi:
+        lo, hi = np.float32(lo - np.float32(0.5)), np.float32(hi + np.float32(0.5))
+    return np.linspace(lo, hi, 11)
+
+
+def ce_figure(dx, dy, score, threshold, img_res, carto: bool = False, ctx: Context | None = None) -> CeFigure:
+    """Every array and scalar `CircularErrorPlot._plot` (karios/report/circular_error_plot.py) hands to matplotlib, for the columns dx,
+    dy, score of a frame, the confidence threshold (compared as `accuracy_statistics` compares it), the resolution `img_res` (a
+    Python float: the products are float32) and `carto` -> `CeFigure`.  float32 numpy arrays, or float32 torch tensors on the
+    context's device: then no column crosses to the host - 64 bytes of extremes and sizes, the counts of the three histograms and
+    32 bytes of final scalars do; numpy builds the bin edges and scipy fits the 10 x 10 spline from those, the GPU counts, evaluates
+    the spline per point, sorts and gathers.  The drawing order is the stable one (np.argsort(z, kind="stable")).  ValueError for
+    an empty sample, as the reference's np.max raises.  numpy / scipy on the host take the call where the GPU form is not
+    defined: columns that are not float32, more than 2^24 rows, an np.float64 `img_res`, a NaN in dx or dy of the sample; and ONE
+    axis histogram of more than CE_MAX_BINS bins (`host_hist_x` / `host_hist_y`)."""
+    dev = _on_device(dx)
+    if dev != _on_device(dy) or dev != _on_device(score):
+        raise ValueError("ce_figure: dx, dy and score must all be numpy arrays or all be device tensors")
+
+    def to_host(a):
+        return a.detach().cpu().numpy() if dev else np.asarray(a)
+
+    cols = (dx, dy, score)
+    if dev:
+        import torch
+        f32_cols = all(a.dtype == torch.float32 and a.dim() == 1 and a.is_contiguous() for a in cols)
+    else:
+        cols = tuple(np.asarray(a) for a in cols)
+        f32_cols = all(a.dtype == np.float32 and a.ndim == 1 for a in cols)
+    if any(len(a.shape) != 1 for a in cols) or any(int(a.shape[0]) != int(cols[0].shape[0]) for a in cols):
+        raise ValueError("ce_figure: dx, dy and score must be 1-D columns of one length")
+    n = int(cols[0].shape[0])
+    if isinstance(img_res, (bool, str)) or not isinstance(img_res, (float, int, np.floating, np.integer)):
+        raise ValueError(f"ce_figure: img_res {img_res!r} is not a number")
+    scalar_thr = isinstance(threshold, (float, int, np.floating, np.integer))
+    if not f32_cols or n > ACCURACY_MAX_ROWS or isinstance(img_res, np.float64) or not scalar_thr or not np.isfinite(np.float32(img_res)):
+        return _ce_host(*(to_host(a) for a in cols), threshold, img_res, carto)
+    if n == 0:
+        raise ValueError("ce_figure: zero-size sample: no row lies above the threshold")
+    thr = float(threshold) if isinstance(threshold, np.float64) else float(np.float32(threshold))
+    res32 = np.float32(img_res)
+    c = _ctx(ctx)
+    device = cols[0].device if dev else None
+    if dev:
+        torch.cuda.synchronize(device)
+    else:
+        cols = tuple(np.ascontiguousarray(a) for a in cols)
+    what = "km_ce_figure_dev" if dev else "km_ce_figure"
+    fn = getattr(c.lib, what)
+    job, blk, tail = _lib.CeJob(), _lib.CeBlock(), _lib.CeTail()
+    job.n, job.carto, job.thr, job.res = n, int(bool(carto)), thr, float(res32)
+    job.dx, job.dy, job.score = (C.cast(a, C.c_void_p).value for a in _col_args(dev, cols, n))
+    job.block, job.tail = C.pointer(blk), C.pointer(tail)
+
+    job.stage = _lib.CE_SAMPLE
+    c.check(fn(c.handle, C.byref(job)), what)
+    if blk.n_nan:
+        return _ce_host(*(to_host(a) for a in cols), threshold, img_res, carto)
+    sample = int(blk.sample)
+    if sample == 0:
+        raise ValueError("ce_figure: zero-size sample: no row lies above the threshold")
+    ext = np.array(blk.ext, np.float32)
+    r = CeFigure(sample=sample, mu_x=np.float32(blk.mu_x), sigma_x=np.float32(blk.sigma_x), mu_y=np.float32(blk.mu_y), sigma_y=np.float32(blk.sigma_y))
+    r.plot_limit = np.max(np.abs(ext[4:8]))
+
+    # the edges: numpy's own linspace on the extremes
+    r.bins_x = _ce_axis_edges(ext[0], ext[1], ext[4], ext[5], sample, res32)
+    r.bins_y = _ce_axis_edges(ext[2], ext[3], ext[6], ext[7], sample, res32)
+    r.x_edges, r.y_edges = _ce_grid_edges(ext[4], ext[5]), _ce_grid_edges(ext[6], ext[7])
+    r.host_hist_x, r.host_hist_y = r.bins_x.size - 1 > CE_MAX_BINS, r.bins_y.size - 1 > CE_MAX_BINS
+    grid = np.ascontiguousarray(np.concatenate([r.x_edges, r.y_edges]), np.float32)
+    hx = np.zeros(0 if r.host_hist_x else r.bins_x.size - 1, np.uint32)
+    hy = np.zeros(0 if r.host_hist_y else r.bins_y.size - 1, np.uint32)
+    counts = np.zeros(100, np.uint32)
+    job.stage = _lib.CE_COUNTS
+    job.edges_x, job.edges_y, job.edges_grid = r.bins_x.ctypes.data, r.bins_y.ctypes.data, grid.ctypes.data
+    job.bins_x, job.bins_y = hx.size, hy.size
+    job.hist_x, job.hist_y, job.counts_grid = hx.ctypes.data, hy.ctypes.data, counts.ctypes.data
+    c.check(fn(c.handle, C.byref(job)), what)
+    r.hist_x, r.hist_y = hx.astype(np.int64), hy.astype(np.int64)
+    if r.host_hist_x or r.host_hist_y:
+        h_dx, h_dy, h_score = (to_host(a) for a in cols)
+        keep = h_score.astype(np.float64) > thr
+        if r.host_hist_x:
+            r.hist_x = _ce_histogram_host(h_dx[keep], img_res)[0]
+        if r.host_hist_y:
+            r.hist_y = _ce_histogram_host((-h_dy if carto else h_dy)[keep], img_res)[0]
+    r.counts2d = counts.astype(np.float64).reshape(10, 10)
+
+    # the fit: scipy's own, on 100 numbers
+    from scipy.interpolate import RectBivariateSpline
+    cx, cy = 0.5 * (r.x_edges[1:] + r.x_edges[:-1]), 0.5 * (r.y_edges[1:] + r.y_edges[:-1])
+    tx, ty, coef = (np.ascontiguousarray(a, np.float64) for a in RectBivariateSpline(cx, cy, r.counts2d).tck[:3])
+    if (tx.size, ty.size, coef.size) != (14, 14, 100):
+        raise KariosHipError(f"ce_figure: a spline of {tx.size} x {ty.size} knots and {coef.size} coefficients (14 x 14, 100)")
+    box = np.array([cx[0], cx[-1], cy[0], cy[-1]], np.float32)
+    outs = [_empty(n, np.float32, device) for _ in range(4)]
+    job.stage = _lib.CE_CURVES
+    job.tx, job.ty, job.coef, job.box = tx.ctypes.data, ty.ctypes.data, coef.ctypes.data, box.ctypes.data
+    job.scatter_x, job.scatter_y, job.scatter_z, job.radial = (C.cast(a, C.c_void_p).value for a in _col_args(dev, outs, n))
+    c.check(fn(c.handle, C.byref(job)), what)
+    r.scatter_x, r.scatter_y, r.scatter_z, r.radial = (a[:sample] for a in outs)
+    r.n_outside = int(tail.n_outside)
+    order = np.array(tail.order, np.float32)
+    ce = []
+    for k, percent in enumerate((0.9, 0.95)):
+        frac = _ce_ranks(percent, sample)[2]
+        ce.append(order[2 * k] + (order[2 * k + 1] - order[2 * k]) * frac)       # accuracy_statistics.py:237, as `accuracy_statistics` forms it
+    r.ce90, r.ce95 = ce
+    return r

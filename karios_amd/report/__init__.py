@@ -1,4 +1,5 @@
 """Mirror of `karios.report`: the key-point chips of a matched pair, selected and cut on the GPU; the display ranges of the overview
 figure (`overview`), the mean profiles of the row / column / altitude figures (`commons`), the key-point rasters of the products
-(`product_generator`) and the altitude column and box statistics of the DEM figures (`shift_by_alt`) on resident data."""
+(`product_generator`), the altitude column and box statistics of the DEM figures (`shift_by_alt`) and the numbers of the circular-error
+figure (`circular_error`) on resident data."""
 from .chip_service import CenterAndQuarterCellPointSelector, Chips, ChipService  # noqa: F401
