@@ -272,6 +272,14 @@ int km_auto_mask(km_ctx *ctx, const void *mon, const void *ref, int dtype, int H
 /* Test hook: the oscillation stop of the LK kernels' iteration (cv2.calcOpticalFlowPyrLK, klt.py:134-140; OpenCV compares the
  * float32 |delta + prevDelta| with the DOUBLE literal 0.01) evaluated on the device for n host quadruples (ddx, pdx, ddy, pdy). */
 int km_lk_oscillation_probe(km_ctx *ctx, const float *quads, int n, uint8_t *out);
+/* Test hook: the frame stage alone (klt.py:142-168, 341-348: forward-backward distance, the cut d < 0.1f, score, tile origin, dx / dy,
+ * stable compaction, (x0, y0) row order with pandas' labels) on host point lists of n_units (1 .. 16) units.  p0 / p1 / p0r: n_units x
+ * n_max x 2 floats; n[k]: the unit's count word (rows behind it are not read; larger than n_max: clamped), negative = the unit has no
+ * count word; width[k]: columns of the unit (corner columns < width), 0 = unknown; out: n_units blocks of 4 int32 {rows, Ninit, 0, 0} +
+ * 6 * cap float32 (x0 | y0 | dx | dy | score | index bits).  One unit runs as a tile's frame does, several as a batched submission's
+ * (at most 32768 rows each; there every unit has a count word: a negative n[k] becomes n_max, an unknown width the widest map).  The first n[k] corners of a unit must be integer-valued and non-negative: the caller checks. */
+int km_frame_from_tracks(km_ctx *ctx, int n_units, const float *p0, const float *p1, const float *p0r, const int *n, const float *x_off,
+                         const float *y_off, const int *width, int n_max, int cap, void *out);
 /* cv2.Laplacian(u8, CV_8U, ksize) (klt.py:359-360, 427-434, 480-483) */
 int km_laplacian_u8(km_ctx *ctx, const uint8_t *src, int H, int W, int ksize, uint8_t *dst);
 /* cornerMinEigenVal inside cv2.goodFeaturesToTrack (klt.py:120) */

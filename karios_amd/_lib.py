@@ -168,6 +168,7 @@ SIGNATURES = {
     "km_to_uint8": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _pd]),
     "km_auto_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _pd, _pd, _vp, C.POINTER(C.c_int64)]),
     "km_lk_oscillation_probe": (_i, [_vp, _vp, _i, _vp]),
+    "km_frame_from_tracks": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "km_laplacian_u8": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "km_min_eigen": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "km_good_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _i, _pi]),

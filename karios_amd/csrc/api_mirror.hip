@@ -168,4 +168,49 @@ int km_lk_oscillation_probe(km_ctx *c, const float *quads, int n, uint8_t *out)
     return KM_OK;
 }
 
+// test hook: the frame stage alone (k_frame.hip: forward-backward cut, score, compaction, (x0, y0) order) on host point lists.  One unit
+// goes through kf_frame, several through kf_frame_units as a batched submission's do (a km_units with the fields that call reads); the
+// threshold is the pipelines' 0.1f.  frame_launch owns WS_MISC0 / 1 / 2 and WS_FRAME_CNT: the lists are staged in WS_PTS0 / 1 / 2, one
+// scalar block per unit (its n_corners is the count word, flags and candidates stay 0) in WS_MISC3, the blocks in WS_FRAME
+int km_frame_from_tracks(km_ctx *c, int n_units, const float *p0, const float *p1, const float *p0r, const int *n, const float *x_off, const float *y_off,
+                         const int *width, int n_max, int cap, void *out)
+{
+    int rc;
+    if ((rc = begin_call(c))) return rc;
+    if (n_units < 1 || n_units > KM_UNITS_MAX || n_max <= 0 || cap <= 0 || !p0 || !p1 || !p0r || !n || !x_off || !y_off || !width || !out)
+        return km_fail(c, KM_E_ARG, "frame_from_tracks: bad arguments");
+    for (int k = 0; k < n_units; k++) {
+        if (width[k] < 0) return km_fail(c, KM_E_ARG, "frame_from_tracks: width %d", width[k]);
+        if ((rc = check_frame_width(c, "frame_from_tracks", "unit", width[k]))) return rc;
+    }
+    const size_t lb = (size_t)n_max * 2 * sizeof(float), pb = up256(lb), sb = up256(sizeof(km_scalars));
+    const km_frame_layout L(cap, false, false);
+    char *d_p0 = (char *)km_ws(c, WS_PTS0, pb * n_units), *d_p1 = (char *)km_ws(c, WS_PTS1, pb * n_units), *d_p0r = (char *)km_ws(c, WS_PTS2, pb * n_units);
+    char *d_sc = (char *)km_ws(c, WS_MISC3, sb * n_units);
+    char *d_out = (char *)km_ws(c, WS_FRAME, L.ob_al * n_units);
+    if (!d_p0 || !d_p1 || !d_p0r || !d_sc || !d_out) return KM_E_NOMEM;
+    if ((rc = frame_block_free(c))) return rc;
+    std::vector<char> h_sc(sb * n_units, 0);
+    km_units U;
+    U.n = n_units;
+    for (int k = 0; k < n_units; k++) {
+        const size_t at = (size_t)k * n_max * 2;
+        if ((rc = h2d_now(c, d_p0 + pb * k, p0 + at, lb)) || (rc = h2d_now(c, d_p1 + pb * k, p1 + at, lb)) || (rc = h2d_now(c, d_p0r + pb * k, p0r + at, lb))) return rc;
+        U.p0[k] = (float *)(d_p0 + pb * k); U.p1[k] = (float *)(d_p1 + pb * k); U.p0r[k] = (float *)(d_p0r + pb * k);
+        U.sc[k] = (km_scalars *)(d_sc + sb * k);
+        ((km_scalars *)(h_sc.data() + sb * k))->n_corners = n[k] < 0 ? n_max : n[k];      // (a batched unit always has a count word)
+        U.frame[k] = d_out + L.ob_al * k;
+        U.x_off[k] = x_off[k]; U.y_off[k] = y_off[k];
+        U.W[k] = width[k] > 0 ? width[k] : 65535;      // (unknown: the widest map)
+    }
+    if ((rc = h2d_now(c, d_sc, h_sc.data(), h_sc.size()))) return rc;
+    // a negative count: the single unit has no count word
+    if (n_units == 1) rc = kf_frame(c, U.p0[0], U.p1[0], U.p0r[0], n[0] < 0 ? nullptr : &U.sc[0]->n_corners, n_max, cap, 0.1f, x_off[0], y_off[0], U.frame[0], nullptr, width[0]);
+    else rc = kf_frame_units(c, U, n_max, cap, 0.1f);
+    if (rc) return rc;
+    for (int k = 0; k < n_units; k++) KM_D2H(c, (char *)out + L.ob * k, d_out + L.ob_al * k, L.ob);
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
 }  // extern "C"

@@ -35,6 +35,14 @@ struct fb_units_args {
     fb_unit u[KM_UNITS_MAX];
 };
 
+// d = max(|x0 - xr|, |y0 - yr|) as numpy's `max` takes it: a NaN in EITHER component is the distance (fmaxf would return the other
+// component and keep a row that the reference drops)
+__device__ __forceinline__ float fb_distance(float x0, float y0, float xr, float yr)
+{
+    const float ax = fabsf(__fsub_rn(x0, xr)), ay = fabsf(__fsub_rn(y0, yr));
+    return (ax > ay || ax != ax) ? ax : ay;
+}
+
 // stable compaction of the kept points (rank = position in p0 order): pass 1 counts per workgroup, pass 2 writes
 template <bool WRITE>
 __global__ __launch_bounds__(FB_T) void fb_compact_kernel(fb_units_args A, int n_max, float back_thr, int cap, int n_sort)
@@ -56,7 +64,7 @@ __global__ __launch_bounds__(FB_T) void fb_compact_kernel(fb_units_args A, int n
     float x0 = 0, y0 = 0, x1 = 0, y1 = 0, d = 0;
     if (i < n) {
         x0 = p0[2 * i]; y0 = p0[2 * i + 1];
-        d = fmaxf(fabsf(__fsub_rn(x0, p0r[2 * i])), fabsf(__fsub_rn(y0, p0r[2 * i + 1])));
+        d = fb_distance(x0, y0, p0r[2 * i], p0r[2 * i + 1]);
         keep = d < back_thr;   // NaN compares false, like numpy
         if (WRITE) { x1 = p1[2 * i]; y1 = p1[2 * i + 1]; }
     }
@@ -322,7 +330,7 @@ __global__ __launch_bounds__(256) void fb_count_kernel(const float *__restrict__
     const int n = min(d_n ? *d_n : n_max, n_max);
     int local = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float d = fmaxf(fabsf(__fsub_rn(p0[2 * i], p0r[2 * i])), fabsf(__fsub_rn(p0[2 * i + 1], p0r[2 * i + 1])));
+        const float d = fb_distance(p0[2 * i], p0[2 * i + 1], p0r[2 * i], p0r[2 * i + 1]);
         local += d < back_thr ? 1 : 0;
     }
     for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
@@ -344,7 +352,7 @@ __global__ __launch_bounds__(256) void fb_count_jobs_kernel(km_count_jobs J, int
     const int n = min(J.d_n[j] ? *J.d_n[j] : n_max, n_max);
     int local = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float d = fmaxf(fabsf(__fsub_rn(p0[2 * i], p0r[2 * i])), fabsf(__fsub_rn(p0[2 * i + 1], p0r[2 * i + 1])));
+        const float d = fb_distance(p0[2 * i], p0[2 * i + 1], p0r[2 * i], p0r[2 * i + 1]);
         local += d < back_thr ? 1 : 0;
     }
     for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);

@@ -126,6 +126,45 @@ def lk_oscillation_probe(quads, ctx: Context | None = None):
     return out.astype(bool)
 
 
+def frame_from_tracks(units, n_max: int, cap: int, ctx: Context | None = None, raw: bool = False):
+    """Test hook: the frame stage of the device pipelines alone (klt.py:142-168, 341-348) on host point lists.
+
+    `units`: 1 to 16 mappings with `p0`, `p1`, `p0r` (`n_max` points each), `n` (the count word the kernels read; negative: the
+    unit has none), `x_off`, `y_off` (tile origin) and `width` (columns of the unit, 0: unknown).  One unit runs as a tile's frame
+    does, several as one batched submission's (there a unit
+    without a count word gets `n_max` as its count).  -> list of DataFrame / None (`frames.block_to_frame`); `raw`: the blocks instead.
+    The ordering key of the device code assumes integer-valued, non-negative corners and origins: anything else among the rows
+    in front of `n` is refused here."""
+    from . import frames
+    c = _ctx(ctx)
+    units = list(units)
+    n_max, cap, k = int(n_max), int(cap), len(units)
+    if not 1 <= k <= _lib.UNITS_PER_SUBMISSION or n_max <= 0 or cap <= 0:
+        raise KariosHipError(f"frame_from_tracks: {k} units of {n_max} points, capacity {cap}")
+    lists = np.empty((3, k, n_max, 2), np.float32)
+    counts, widths = np.empty(k, np.int32), np.empty(k, np.int32)
+    origins = np.empty((2, k), np.float32)
+    for j, u in enumerate(units):
+        for i, name in enumerate(("p0", "p1", "p0r")):
+            a = np.asarray(u[name], np.float32).reshape(-1, 2)
+            if a.shape[0] != n_max:
+                raise KariosHipError(f"frame_from_tracks: unit {j}: {name} holds {a.shape[0]} points, not {n_max}")
+            lists[i, j] = a
+        counts[j], widths[j] = int(u["n"]), int(u.get("width", 0))
+        origins[0, j], origins[1, j] = u.get("x_off", 0), u.get("y_off", 0)
+        live = lists[0, j, :n_max if counts[j] < 0 else min(int(counts[j]), n_max)]
+        if not (np.isfinite(live).all() and (live >= 0).all() and (live == np.floor(live)).all() and (live <= 2.0 ** 24).all()):
+            raise KariosHipError(f"frame_from_tracks: unit {j}: corners must be non-negative integers up to 2^24")
+        if not (np.isfinite(origins[:, j]).all() and (origins[:, j] == np.floor(origins[:, j])).all()):
+            raise KariosHipError(f"frame_from_tracks: unit {j}: the tile origin must be integer-valued")
+    words = frames.block_words(cap)
+    out = np.empty((k, words), np.float32)
+    x_off, y_off = np.ascontiguousarray(origins[0]), np.ascontiguousarray(origins[1])
+    c.check(c.lib.km_frame_from_tracks(c.handle, k, ptr(lists[0]), ptr(lists[1]), ptr(lists[2]), ptr(counts), ptr(x_off), ptr(y_off),
+                                       ptr(widths), n_max, cap, ptr(out)), "km_frame_from_tracks")
+    return list(out) if raw else [frames.block_to_frame(b, cap) for b in out]
+
+
 def make_params(conf, mon_ksize=1, ref_ksize=1, invert_mon=False) -> KltParams:
     """KLTConfiguration duck type (core/configuration.py:36-50) -> km_klt_params with the fixed
     LK criteria of klt.py:128-132."""

@@ -6,7 +6,9 @@
 //   3. km_klt_auto_ksize_frame_dev on the stand-in - all batched, corners batched + trackers one by one, all one by one, flagged units
 //      repaired - per case the same ratios, winner and frame block in every form;
 //   4. a blocking tile frame call and a three-unit batched submission with ZNCC and MI columns: every column at its word.
-// 3 and 4 use the public C ABI only and print one digest line per case.  Prints 'FRAME-LAYOUT OK' at the end.
+//   5. km_frame_from_tracks (the frame stage alone, tests/test_frame_host.py): a handful of cases with their expected rows written out;
+//      `frame --tracks IN OUT` runs the records of a file through it instead and prints 'FRAME-TRACKS OK'.
+// 3 to 5 use the public C ABI only and print one digest line per case.  Prints 'FRAME-LAYOUT OK' at the end.
 #ifdef FRAME_MAIN_ABI_ONLY      // (parts 3 and 4 alone: they build against any csrc/ with the same C ABI)
 #include "../../karios_amd/csrc/common.hpp"
 #else
@@ -242,8 +244,144 @@ static void check_tile_and_units(km_ctx *c)
     CALL(km_set_option(c, "frame_mi", 0));
 }
 
-int main()
+// ---- km_frame_from_tracks (the frame stage alone, tests/test_frame_host.py)
+struct track_unit {
+    std::vector<float> p0, p1, p0r;
+    int n = 0, width = 0;
+    float x_off = 0.f, y_off = 0.f;
+};
+static int run_tracks(km_ctx *c, const std::vector<track_unit> &units, int n_max, int cap, std::vector<char> &blocks)
 {
+    const size_t k = units.size(), pts = (size_t)n_max * 2;
+    std::vector<float> p0(k * pts), p1(k * pts), p0r(k * pts), xo(k), yo(k);
+    std::vector<int> n(k), width(k);
+    for (size_t u = 0; u < k; u++) {
+        REQUIRE(units[u].p0.size() == pts && units[u].p1.size() == pts && units[u].p0r.size() == pts, "unit %zu: %d points each", u, n_max);
+        memcpy(&p0[u * pts], units[u].p0.data(), pts * 4); memcpy(&p1[u * pts], units[u].p1.data(), pts * 4); memcpy(&p0r[u * pts], units[u].p0r.data(), pts * 4);
+        n[u] = units[u].n; width[u] = units[u].width; xo[u] = units[u].x_off; yo[u] = units[u].y_off;
+    }
+    blocks.assign(k * 4 * block_words(cap, 0), 0x5a);
+    return km_frame_from_tracks(c, (int)k, p0.data(), p1.data(), p0r.data(), n.data(), xo.data(), yo.data(), width.data(), n_max, cap, blocks.data());
+}
+struct want_row { float x0, y0, dx, dy, score; int label; };
+static unsigned bits_of(float v) { unsigned u; memcpy(&u, &v, 4); return u; }
+static void expect_block(const char *what, const char *block, int cap, int n_init, const std::vector<want_row> &rows)
+{
+    const int *hdr = (const int *)block;
+    const float *f = (const float *)block;
+    REQUIRE(hdr[0] == (int)rows.size() && hdr[1] == n_init && hdr[2] == 0 && hdr[3] == 0, "%s: header %d %d %d %d, expected %zu rows of %d", what, hdr[0], hdr[1], hdr[2], hdr[3],
+            rows.size(), n_init);
+    if (hdr[0] != (int)rows.size()) return;
+    for (size_t i = 0; i < rows.size(); i++) {
+        const float got[5] = {f[word_of_col(cap, 0) + i], f[word_of_col(cap, 1) + i], f[word_of_col(cap, 2) + i], f[word_of_col(cap, 3) + i], f[word_of_col(cap, 4) + i]};
+        const float exp[5] = {rows[i].x0, rows[i].y0, rows[i].dx, rows[i].dy, rows[i].score};
+        for (int c2 = 0; c2 < 5; c2++) REQUIRE(bits_of(got[c2]) == bits_of(exp[c2]), "%s: row %zu column %d = %g (%08x), expected %g (%08x)", what, i, c2, (double)got[c2], bits_of(got[c2]),
+                                               (double)exp[c2], bits_of(exp[c2]));
+        int label;
+        memcpy(&label, &f[word_of_col(cap, 5) + i], 4);
+        REQUIRE(label == rows[i].label, "%s: row %zu label %d, expected %d", what, i, label, rows[i].label);
+    }
+}
+// one unit of n_max rows: corner (x, y) tracked to (x + 0.5, y - 0.25), back to (x + ex, y + ey)
+static track_unit unit_of(const std::vector<float> &x, const std::vector<float> &y, const std::vector<float> &ex, const std::vector<float> &ey)
+{
+    track_unit u;
+    for (size_t i = 0; i < x.size(); i++) {
+        u.p0.push_back(x[i]); u.p0.push_back(y[i]);
+        u.p1.push_back(x[i] + 0.5f); u.p1.push_back(y[i] - 0.25f);
+        u.p0r.push_back(x[i] + ex[i]); u.p0r.push_back(y[i] + ey[i]);
+    }
+    u.n = (int)x.size();
+    return u;
+}
+// a handful of the cases of tests/frame_cases.py, expected values written out by hand
+static void check_tracks(km_ctx *c)
+{
+    const float thr = 0.1f, below = std::nextafterf(thr, 0.f), above = std::nextafterf(thr, 1.f), nan = NAN, inf = INFINITY;
+    std::vector<char> blocks;
+    {   // the cut at the threshold, in x alone, in y alone, NaN / inf in one component; every corner at 0 (the distance is exact there)
+        const std::vector<float> ex = {0.f, below, thr, above, 0.f, 0.f, nan, 0.05f, inf, -0.f, 0.f}, ey = {0.f, 0.f, 0.f, 0.f, below, thr, 0.05f, nan, 0.f, 0.f, 0.f};
+        const std::vector<float> z(ex.size(), 0.f);
+        track_unit u = unit_of(z, z, ex, ey);
+        u.n = (int)ex.size() - 1;                       // (the last row lies behind the count word)
+        CALL(run_tracks(c, {u}, (int)ex.size(), 16, blocks));
+        const float s_below = 1.f - below / thr;
+        // all corners equal: the rows keep their list order, the labels count up
+        expect_block("cut", blocks.data(), 16, u.n, {{0, 0, .5f, -.25f, 1.f, 0}, {0, 0, .5f, -.25f, s_below, 1}, {0, 0, .5f, -.25f, s_below, 2}, {0, 0, .5f, -.25f, 1.f, 3}});
+    }
+    {   // order, ties, origin, capacity: corners (3,1) (1,2) (3,1) (1,0) (2,9), capacity 4, origin (10, 20), no count word
+        track_unit u = unit_of({3, 1, 3, 1, 2}, {1, 2, 1, 0, 9}, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0});
+        u.n = -1; u.x_off = 10.f; u.y_off = 20.f; u.width = 4;
+        CALL(run_tracks(c, {u}, 5, 4, blocks));
+        expect_block("order", blocks.data(), 4, 5, {{11, 20, .5f, -.25f, 1.f, 3}, {11, 22, .5f, -.25f, 1.f, 1}, {13, 21, .5f, -.25f, 1.f, 0}, {13, 21, .5f, -.25f, 1.f, 2}});
+    }
+    {   // three units of different length in one call, a count word above n_max, an empty unit; each as when submitted alone
+        track_unit a = unit_of({5, 4, 3}, {0, 0, 0}, {0, 0.2f, 0}, {0, 0, 0}), b = unit_of({7, 7, 7}, {2, 1, 0}, {0, 0, 0}, {0, 0, 0}), e = b;
+        a.n = 5000; b.n = 2; e.n = 0; b.y_off = 67108864.f; a.width = b.width = e.width = 8;
+        CALL(run_tracks(c, {a, b, e}, 3, 3, blocks));
+        const size_t ob = 4 * block_words(3, 0);
+        expect_block("units[0]", blocks.data(), 3, 3, {{3, 0, .5f, -.25f, 1.f, 1}, {5, 0, .5f, -.25f, 1.f, 0}});
+        // (2^26 + 2 and 2^26 + 1 both round to 2^26 in float32: a tie, the rows keep their list order)
+        expect_block("units[1]", blocks.data() + ob, 3, 2, {{7, 67108864.f, .5f, -.25f, 1.f, 0}, {7, 67108864.f, .5f, -.25f, 1.f, 1}});
+        expect_block("units[2]", blocks.data() + 2 * ob, 3, 0, {});
+        for (const track_unit *u : {&a, &b, &e}) {
+            std::vector<char> alone;
+            CALL(run_tracks(c, {*u}, 3, 3, alone));
+            REQUIRE(alone.size() == ob && !memcmp(alone.data(), blocks.data() + ob * (size_t)(u == &a ? 0 : u == &b ? 1 : 2), ob), "a unit alone differs");
+        }
+    }
+    {   // refused on the host: too many units, a negative width, a width beyond the ordering's
+        track_unit u = unit_of({1}, {1}, {0}, {0});
+        std::vector<track_unit> many(17, u);
+        REQUIRE(run_tracks(c, many, 1, 1, blocks) == KM_E_ARG, "17 units");
+        u.width = 65536;
+        REQUIRE(run_tracks(c, {u}, 1, 1, blocks) == KM_E_ARG, "width 65536");
+        u.width = -1;
+        REQUIRE(run_tracks(c, {u}, 1, 1, blocks) == KM_E_ARG, "width -1");
+    }
+    printf("tracks 4 groups\n");
+}
+
+// `frame --tracks IN OUT`: every record of IN {int32 n_units, n_max, cap; per unit int32 n, int32 width, float32 x_off, y_off; then the
+// units' p0, p1, p0r lists} through km_frame_from_tracks on ONE context; OUT gets {int32 status; the blocks if status == 0} per record
+static int tracks_from_file(km_ctx *c, const char *in_path, const char *out_path)
+{
+    FILE *in = fopen(in_path, "rb"), *out = fopen(out_path, "wb");
+    if (!in || !out) { fprintf(stderr, "cannot open %s / %s\n", in_path, out_path); return 1; }
+    int head[3], records = 0;
+    while (fread(head, sizeof head, 1, in) == 1) {
+        const int k = head[0], n_max = head[1], cap = head[2];
+        if (k < 1 || k > 64 || n_max < 1 || cap < 1) { fprintf(stderr, "record %d: bad header\n", records); return 1; }
+        std::vector<int> meta(4 * (size_t)k);
+        std::vector<float> pts((size_t)3 * k * n_max * 2);
+        if (fread(meta.data(), 16, (size_t)k, in) != (size_t)k || fread(pts.data(), 4, pts.size(), in) != pts.size()) { fprintf(stderr, "record %d: truncated\n", records); return 1; }
+        std::vector<int> n((size_t)k), width((size_t)k);
+        std::vector<float> xo((size_t)k), yo((size_t)k);
+        for (int u = 0; u < k; u++) { n[u] = meta[4 * u]; width[u] = meta[4 * u + 1]; memcpy(&xo[u], &meta[4 * u + 2], 4); memcpy(&yo[u], &meta[4 * u + 3], 4); }
+        const size_t list = (size_t)k * n_max * 2;
+        std::vector<char> blocks((size_t)k * 4 * block_words(cap, 0), 0x5a);
+        const int rc = km_frame_from_tracks(c, k, pts.data(), pts.data() + list, pts.data() + 2 * list, n.data(), xo.data(), yo.data(), width.data(), n_max, cap, blocks.data());
+        fwrite(&rc, sizeof rc, 1, out);
+        if (rc == KM_OK) fwrite(blocks.data(), 1, blocks.size(), out);
+        records++;
+    }
+    fclose(in);
+    if (fclose(out)) return 1;
+    printf("tracks-file %d records\n", records);
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc == 4 && !strcmp(argv[1], "--tracks")) {
+        km_ctx *c = nullptr;
+        if (km_ctx_create(0, &c) != KM_OK) { fprintf(stderr, "km_ctx_create failed: %s\n", km_last_error(nullptr)); return 1; }
+        const int rc = tracks_from_file(c, argv[2], argv[3]);
+        REQUIRE(km_ctx_destroy(c) == KM_OK, "km_ctx_destroy");
+        if (rc || g_failures) return 1;
+        printf("FRAME-TRACKS OK\n");
+        return 0;
+    }
 #ifndef FRAME_MAIN_ABI_ONLY
     check_layout();
     check_arena();
@@ -252,6 +390,7 @@ int main()
     if (km_ctx_create(0, &c) != KM_OK) { fprintf(stderr, "km_ctx_create failed: %s\n", km_last_error(nullptr)); return 1; }
     check_search(c);
     check_tile_and_units(c);
+    check_tracks(c);
     REQUIRE(km_ctx_destroy(c) == KM_OK, "km_ctx_destroy");
     const stub_state &s = stub();
     REQUIRE(s.streams == 0 && s.events == 0 && s.device_allocs == 0 && s.host_allocs == 0, "left behind %ld streams, %ld events, %ld device, %ld page-locked allocations", s.streams,

@@ -510,7 +510,10 @@ static void count_kept_of(const float *p0, const float *p0r, const int *d_n, int
 {
     const int n = std::min(*d_n, n_max);
     int k = 0;
-    for (int i = 0; i < n; i++) k += std::max(fabsf(p0[2 * i] - p0r[2 * i]), fabsf(p0[2 * i + 1] - p0r[2 * i + 1])) < thr;
+    for (int i = 0; i < n; i++) {
+        const float ax = fabsf(p0[2 * i] - p0r[2 * i]), ay = fabsf(p0[2 * i + 1] - p0r[2 * i + 1]);
+        k += ((ax > ay || ax != ax) ? ax : ay) < thr;      // (numpy's max: a NaN in either component is the distance)
+    }
     *cnt = k;
 }
 static void count_kept_declare(const launch &L, const float *p0, const float *p0r, const int *d_n, int n_max, int *cnt, so::kind how)
@@ -543,7 +546,8 @@ int kf_dn_keep(km_ctx *c, const void *ref, const void *mon, int dtype, int H, in
 static void frame_unit_declare(const launch &L, const float *p0, const float *p1, const float *p0r, const int *d_n, int n_max, int cap, void *out, const km_scalars *hdr)
 {
     const size_t pts = (size_t)n_max * 2 * sizeof(float);
-    L.read(p0, pts); L.read(p1, pts); L.read(p0r, pts); L.read(d_n, sizeof *d_n);
+    L.read(p0, pts); L.read(p1, pts); L.read(p0r, pts);
+    if (d_n) L.read(d_n, sizeof *d_n);
     if (hdr) { L.fields(so::READ, hdr, SC_FIELD(flags)); L.fields(so::READ, hdr, SC_FIELD(cut)); }
     L.write(out, 16 + (size_t)cap * 6 * sizeof(float));
 }
@@ -562,19 +566,32 @@ int kf_frame(km_ctx *c, const float *p0, const float *p1, const float *p0r, cons
     frame_unit_declare(L, p0, p1, p0r, d_n, n_max, cap, out, hdr);
     return frame_of(p0, p1, p0r, d_n, n_max, cap, thr, xo, yo, out, hdr);
 }
+// the frame stage as the device code defines it (k_frame.hip), in plain loops: d = max(|p0 - p0r|) with numpy's NaN rule (a NaN in either
+// component is the distance), the cut d < thr, at most `cap` kept rows (the first in list order), rows behind the count word ignored
+// (no count word: n_max rows), then the stable (x0, y0) order with the row's position in the kept list as its label
 static int frame_of(const float *p0, const float *p1, const float *p0r, const int *d_n, int n_max, int cap, float thr, float xo, float yo, void *out, const km_scalars *hdr)
 {
-    const int n = std::min(*d_n, n_max);
+    const int n = d_n ? std::min(*d_n, n_max) : n_max;
     int *h = (int *)out;
     float *f = (float *)((char *)out + 16);
     for (size_t i = 0; i < (size_t)6 * cap; i++) f[i] = 0.f;
-    int k = 0;
+    std::vector<float> col[5];
     for (int i = 0; i < n; i++) {
-        const float d = std::max(fabsf(p0[2 * i] - p0r[2 * i]), fabsf(p0[2 * i + 1] - p0r[2 * i + 1]));
-        if (!(d < thr)) continue;
-        f[k] = p0[2 * i] + xo; f[cap + k] = p0[2 * i + 1] + yo; f[2 * (size_t)cap + k] = p1[2 * i] - p0[2 * i]; f[3 * (size_t)cap + k] = p1[2 * i + 1] - p0[2 * i + 1];
-        f[4 * (size_t)cap + k] = 1.f - d / thr;
-        k++;
+        const float ax = fabsf(p0[2 * i] - p0r[2 * i]), ay = fabsf(p0[2 * i + 1] - p0r[2 * i + 1]);
+        const float d = (ax > ay || ax != ax) ? ax : ay;
+        if (!(d < thr) || (int)col[0].size() >= cap) continue;
+        col[0].push_back(p0[2 * i] + xo); col[1].push_back(p0[2 * i + 1] + yo);
+        col[2].push_back(p1[2 * i] - p0[2 * i]); col[3].push_back(p1[2 * i + 1] - p0[2 * i + 1]);
+        col[4].push_back(1.f - d / thr);
+    }
+    const int k = (int)col[0].size();
+    std::vector<int> order((size_t)k);
+    for (int i = 0; i < k; i++) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return col[0][a] < col[0][b] || (col[0][a] == col[0][b] && col[1][a] < col[1][b]); });
+    for (int i = 0; i < k; i++) {
+        const int r = order[(size_t)i];
+        for (int c2 = 0; c2 < 5; c2++) f[(size_t)c2 * cap + i] = col[c2][(size_t)r];
+        memcpy(&f[(size_t)5 * cap + i], &r, sizeof r);
     }
     h[0] = k; h[1] = n; h[2] = hdr ? (int)hdr->flags : 0; h[3] = hdr ? (int)hdr->cut[3] : 0;
     return KM_OK;
@@ -843,6 +860,7 @@ int kl_units_launch(km_ctx *c, int n_units, int n_max, int)
 }
 int kf_frame_units(km_ctx *c, const km_units &U, int n_max, int cap, float thr)
 {
+    if (std::min(n_max, cap) > 32768 && U.n != 1) return km_fail(c, KM_E_UNSUPPORTED, "frame: batched units hold at most 32768 rows each");      // (k_frame.hip frame_launch)
     const launch L(c, "kf_frame_units");
     frame_scratch(L, U.n, n_max, cap);
     for (int u = 0; u < U.n; u++) {
