@@ -523,7 +523,7 @@ int km_refine_ecc_candidates_dev(km_ctx *ctx, const uint8_t *d_mon, int hm, int 
  * v1[j] = the value of rank min(floor(vi) + 1, n - 1), vi_out[j] = vi.  The values are exact (a radix select on an
  * order-preserving key of the float32 bit pattern, three passes over the raster, integer counters: bitwise repeatable); -0.0 sorts
  * below +0.0.  n = 0 is not an error: *n = 0 and v0 / v1 / vi_out are left alone.  The interpolation between v0 and v1 is the
- * caller's (numpy does it in the source dtype: karios_amd/ops.py).  q, n, v0, v1, vi_out: host memory in both forms. */
+ * caller's (numpy does it in the source dtype: karios_amd/ops/prep.py).  q, n, v0, v1, vi_out: host memory in both forms. */
 int km_order_statistics(km_ctx *ctx, const void *img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q,
                         int64_t *n, double *v0, double *v1, double *vi_out);
 int km_order_statistics_dev(km_ctx *ctx, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q,

@@ -1,7 +1,7 @@
 // The dense front half of the global align step (karios/matcher/global_align.py:87-108, _to_uint8 and _preprocess) and the
 // percentiles of the quality check (karios/api/core.py:491-506): exact order statistics of a raster, the percentile stretch to uint8
 // and CLAHE.  The kernels live in k_prep.hip.  The interpolation between the two order statistics of a percentile is numpy's and stays
-// with the caller (karios_amd/ops.py): it is arithmetic of the SOURCE dtype there, wrap-around of int16 included.
+// with the caller (karios_amd/ops/prep.py): it is arithmetic of the SOURCE dtype there, wrap-around of int16 included.
 // Also the display range of the report's overview figure (karios/report/overview_plot.py:134-194): the same select under the
 // reference's invalid-pixel rule; kernels in k_report.hip.
 #include "api_internal.hpp"

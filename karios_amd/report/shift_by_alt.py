@@ -18,7 +18,7 @@ def _dem_raster(dem):
     if hasattr(dem, "tensor"):                      # DeviceRasterImage
         return dem.tensor, np.dtype(dem.dtype)
     if hasattr(dem, "data_ptr"):
-        return dem, ops._torch_np_dtype(dem)
+        return dem, ops.tensor_np_dtype(dem)
     a = np.asarray(dem.array if hasattr(dem, "array") else dem)
     return a, a.dtype
 
@@ -109,7 +109,7 @@ def altitude_profile(points, dem, dimension, x_res, bin_size, ctx=None) -> Altit
     col = points[dimension]
     if hasattr(col, "data_ptr"):
         # a device column: torch multiplies a float32 tensor by a Python number in float32, as pandas does; anything else goes to the host
-        weak = ops._torch_np_dtype(col) == f32 and (type(x_res) in (int, float) or isinstance(x_res, f32))
+        weak = ops.tensor_np_dtype(col) == f32 and (type(x_res) in (int, float) or isinstance(x_res, f32))
         values = col * float(f32(x_res)) if weak else col.cpu().numpy() * x_res
     else:
         values = col * x_res                                   # the reference's expression, with pandas' or numpy's own result type

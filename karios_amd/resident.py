@@ -752,14 +752,14 @@ class ResidentPair:
         (mon, ref) `ops.DisplayRange`: the monitored raster under the pair's mask, `no_values` and `no_data_mon`; the reference
         raster without mask under `no_values` and `no_data_ref`."""
         from . import ops
-        values, pp = ops._display_range_lists(no_values, percents)
+        values, pp = ops.display_range_lists(no_values, percents)
         self._ready()
         c = self.ctx
         H, W = self.y_size, self.x_size
         mask = C.c_void_p(self.mask_ptr) if self.mask_ptr else None
-        mon = ops._display_range_call(c, "km_display_range_dev", C.c_void_p(self.mon_ptr), self.dtype, H, W, W, mask, W if mask else 0, values,
+        mon = ops.display_range_call(c, "km_display_range_dev", C.c_void_p(self.mon_ptr), self.dtype, H, W, W, mask, W if mask else 0, values,
                                       self.no_data_mon, pp)
-        ref = ops._display_range_call(c, "km_display_range_dev", C.c_void_p(self.ref_ptr), self.dtype, H, W, W, None, 0, values, self.no_data_ref, pp)
+        ref = ops.display_range_call(c, "km_display_range_dev", C.c_void_p(self.ref_ptr), self.dtype, H, W, W, None, 0, values, self.no_data_ref, pp)
         return mon, ref
 
     # ------------------------------------------------------------------ the report's products

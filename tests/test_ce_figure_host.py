@@ -203,11 +203,11 @@ def run_figure(program, dx, dy, score, t, res, carto, want, pad=0):
     r.scatter_x, r.scatter_y, r.scatter_z, r.radial = cols
     r.mu_x, r.sigma_x, r.mu_y, r.sigma_y = (f32(v) for v in (blk.mu_x, blk.sigma_x, blk.mu_y, blk.sigma_y))
     ext = np.array(blk.ext, f32)
-    r.bins_x, r.bins_y = (ops._ce_axis_edges(ext[2 * k], ext[2 * k + 1], ext[4 + 2 * k], ext[5 + 2 * k], r.sample, f32(res)) for k in (0, 1))
-    r.x_edges, r.y_edges = ops._ce_grid_edges(ext[4], ext[5]), ops._ce_grid_edges(ext[6], ext[7])
+    r.bins_x, r.bins_y = (ops.ce_axis_edges(ext[2 * k], ext[2 * k + 1], ext[4 + 2 * k], ext[5 + 2 * k], r.sample, f32(res)) for k in (0, 1))
+    r.x_edges, r.y_edges = ops.ce_grid_edges(ext[4], ext[5]), ops.ce_grid_edges(ext[6], ext[7])
     r.plot_limit = np.max(np.abs(ext[4:8]))
     order = np.array(tail.order, f32)
-    r.ce90, r.ce95 = (order[2 * k] + (order[2 * k + 1] - order[2 * k]) * ops._ce_ranks(p, r.sample)[2] for k, p in enumerate((0.9, 0.95)))
+    r.ce90, r.ce95 = (order[2 * k] + (order[2 * k + 1] - order[2 * k]) * ops.ce_ranks(p, r.sample)[2] for k, p in enumerate((0.9, 0.95)))
     assert tail.n_outside == int(np.isnan(r.scatter_z).sum()) and blk.n_nan == 0
     return r
 

@@ -321,7 +321,7 @@ def run_range(program, a, mask, no_values, nodata, percents=(0.5, 99.5), pad=0):
     d = np.frombuffer(raw[16:], np.float64)
     vi, v0, v1, rmin, rmax = d[0:4], d[4:8], d[8:12], a.dtype.type(d[12]), a.dtype.type(d[13])
     k = len(q)
-    vals = ops._lerp_as_numpy(v0[:k], v1[:k], vi[:k], n_valid, a.dtype) if n_valid else [rmin, rmax]
+    vals = ops.lerp_as_numpy(v0[:k], v1[:k], vi[:k], n_valid, a.dtype) if n_valid else [rmin, rmax]
     return ops.DisplayRange(vals, n_valid, n_invalid, rmin, rmax)
 
 
