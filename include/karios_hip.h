@@ -156,6 +156,8 @@ int km_set_profiling(km_ctx *ctx, int enable);
  *   "stash_cap"    kept keys a workgroup of the scatter launch stashes in LDS -> its second read of the keys
  *   "spec_flag"    KM_FLAG bits the synchronisation-free path raises artificially -> the flag-and-repeat logic
  *   "defer"        0: pyramid jobs of the exact path run after the selection's read-back waits instead of under them
+ *   "mask_edge_chunk" edges of a feature the polygon fill (km_rasterize_polygons*) stages in LDS at a time (0 = default 896; 1 .. 896)
+ *                  -> many chunks per feature
  *  profiling
  *   "profile_stage" with km_set_profiling(1): time only stage i of km_stage_name (every timed span records two events on the
  *                  library stream and the kernels either side no longer overlap: ~6 us per span); -1 (default): every stage
@@ -809,6 +811,31 @@ int km_box_stats(km_ctx *ctx, int n, const float *values, const float *positions
                  double *stats, int8_t *cls, int32_t *n_groups);
 int km_box_stats_dev(km_ctx *ctx, int n, const float *d_values, const float *d_positions, int bin_size, float *d_key, int32_t *d_count,
                      float *d_mean, double *d_stats, int8_t *d_cls, int32_t *n_groups);
+
+/* ---- vector masks on the device (karios/core/image.py:104-191 rasterize_vector_mask, karios/api/core.py:538-620 _load_mask);
+ * tests/rasterize_restatement.py is the definition: GDAL's polygon burn with BURN=1 and ALL_TOUCHED=TRUE, restated from knowledge of
+ * GDAL 3.x (the scan-line fill at pixel centres, OR the all-touched line pass over every ring); parity with GDAL itself is unpinned.
+ *
+ * n_features features; feature f owns the next feature_rings[f] rings, ring r the next ring_sizes[r] vertices of `xy` (x, y pairs of
+ * float64 in pixel / line space; n_rings rings and n_vertices vertices in all, at most 2^20 vertices).  Every ring is closed (last
+ * vertex == first) and has at least 2 vertices; every coordinate is finite with |v| <= 2^30; H x W has fewer than 2^32 - 1 pixels:
+ * anything else is KM_E_ARG before a launch.  All three tables are HOST memory in both forms.  `out` (host memory; device memory for
+ * _dev; row stride in bytes) becomes 1 where a feature burns and 0 elsewhere: every byte of the H x W window is written exactly once
+ * by the fill, nothing outside it.  A walk of the line pass that exceeds 4 (H + W) + 64 steps is KM_E_INTERNAL (none is known).
+ * The device form completes the context stream before it returns. */
+int km_rasterize_polygons(km_ctx *ctx, const double *xy, int n_vertices, const int32_t *ring_sizes, int n_rings, const int32_t *feature_rings,
+                          int n_features, int H, int W, uint8_t *out, ptrdiff_t out_stride);
+int km_rasterize_polygons_dev(km_ctx *ctx, const double *xy, int n_vertices, const int32_t *ring_sizes, int n_rings, const int32_t *feature_rings,
+                              int n_features, int H, int W, uint8_t *d_out, ptrdiff_t out_stride);
+/* kernel time of the two passes of the last km_rasterize_polygons* call, which ran under km_set_profiling(1) (KM_E_ARG otherwise): the
+ * fill and the line pass, in milliseconds, between events on the library's stream (tools/ubench/mask_rasterize.py) */
+int km_mask_pass_ms(km_ctx *ctx, float *fill_ms, float *lines_ms);
+/* out = (a > 0) & (b > 0) as uint8 0 / 1 of two H x W uint8 masks (row strides in bytes), and from the same pass counts[3] = pixels
+ * with a > 0, with b > 0, with both (the three numbers _load_mask logs).  counts is host memory in both forms. */
+int km_mask_and(km_ctx *ctx, const uint8_t *a, ptrdiff_t a_stride, const uint8_t *b, ptrdiff_t b_stride, int H, int W, uint8_t *out,
+                ptrdiff_t out_stride, int64_t *counts);
+int km_mask_and_dev(km_ctx *ctx, const uint8_t *d_a, ptrdiff_t a_stride, const uint8_t *d_b, ptrdiff_t b_stride, int H, int W, uint8_t *d_out,
+                    ptrdiff_t out_stride, int64_t *counts);
 
 /* ---- the numbers of the circular-error figure on resident data (karios/report/circular_error_plot.py:181-228, 254-303, 359-368);
  * tests/ce_figure_restatement.py is the definition.  numpy builds the bin edges and scipy fits the spline, both on the host and from

@@ -112,6 +112,7 @@ CE_MAX_BINS = 65536            # KM_CE_MAX_BINS
 DISPLAY_MAX_NO_VALUES = 16     # KM_DISPLAY_MAX_NO_VALUES
 PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = 8, 1 << 20, 1 << 24   # KM_PROFILE_MAX; rows and bin size km_mean_profiles takes
 BOX_STATS = 8                  # KM_BOX_STATS: q1, med, q3, iqr, cilo, cihi, whislo, whishi
+MASK_MAX_VERTICES, MASK_MAX_COORD = 1 << 20, float(2 ** 30)   # vertices and |coordinate| km_rasterize_polygons takes
 CHIP_SIZE, CHIP_MAX_GRID, CHIP_PICKS = 57, 16, 5     # KM_CHIP_SIZE, KM_CHIP_MAX_GRID, KM_CHIP_PICKS
 CHIP_SELECT_MAX_ROWS, CHIP_MAX_ROWS = 1 << 24, 1 << 20
 CLIP_MAX_ROWS = 32768          # rows one unit of km_sigma_clip_dev / the "frame_clip" stage holds
@@ -247,6 +248,11 @@ SIGNATURES = {
     "km_sample_points_dev": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "km_box_stats": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "km_box_stats_dev": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "km_rasterize_polygons": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz]),
+    "km_rasterize_polygons_dev": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz]),
+    "km_mask_pass_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "km_mask_and": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _sz, C.POINTER(C.c_int64)]),
+    "km_mask_and_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _sz, C.POINTER(C.c_int64)]),
 }
 
 _lib = None
@@ -466,6 +472,12 @@ class Context:
 
     def set_profiling(self, on: bool):
         self.check(self.lib.km_set_profiling(self.handle, int(bool(on))), "km_set_profiling")
+
+    def mask_pass_ms(self) -> tuple:
+        """(fill, line pass) kernel milliseconds of the last `ops.rasterize_polygons` call, made under `set_profiling(True)`."""
+        fill, lines = C.c_float(), C.c_float()
+        self.check(self.lib.km_mask_pass_ms(self.handle, C.byref(fill), C.byref(lines)), "km_mask_pass_ms")
+        return float(fill.value), float(lines.value)
 
     def upload_check_stats(self):
         """-> (uploads checked, uploads whose first consumer saw stale rows) with KARIOS_HIP_UPLOAD_CHECKSUM=1 (csrc/staging.hip)."""

@@ -95,6 +95,30 @@ class DeviceWindow:
         self.shape = tuple(view.shape)
 
 
+def rasterize_vector_mask(vector, reference_image, geo_transform=None):
+    """karios.core.image.rasterize_vector_mask (image.py:104-191) minus the files: the polygons of `vector` burnt on the grid of
+    `reference_image` as `gdal.RasterizeLayer(..., options=['BURN=1', 'ALL_TOUCHED=TRUE'])` burns them, on the GPU
+    (`ops.rasterize_polygons`; tests/rasterize_restatement.py is the definition - GDAL itself was never run against it).
+
+    `vector`: a GeoJSON path or a parsed GeoJSON dict (FeatureCollection, Feature, Polygon, MultiPolygon, GeometryCollection of those)
+    in the raster's CRS, taken to pixel / line space by `geo_transform` (None: `reference_image.geo_transform` when it has one, else
+    GDAL's default, the identity); or a list of features already in pixel space (each a list of rings of (x, y)), taken as it is.
+    Other geometry types and other file formats raise NotImplementedError: they need OGR, which stays with the integrator, as does
+    reprojection between CRSs.  -> a `DeviceRasterImage` when `reference_image` is one (nothing but the vertices crosses PCIe), else
+    a `NumpyRasterImage`; either goes to `KLT.match` as its mask."""
+    shape = (int(reference_image.y_size), int(reference_image.x_size))
+    if isinstance(vector, (list, tuple)):
+        features = vector
+    else:
+        gt = geo_transform if geo_transform is not None else getattr(reference_image, "geo_transform", None)
+        features = ops.read_vector_features(vector, "rasterize_vector_mask")
+        if gt is not None:
+            features = [[ops.geo_to_pixel(ring, gt) for ring in feature] for feature in features]
+    if isinstance(reference_image, DeviceRasterImage):
+        return DeviceRasterImage(ops.rasterize_polygons(features, shape, device=reference_image.tensor.device), filepath="vector_mask.tif")
+    return NumpyRasterImage(ops.rasterize_polygons(features, shape), filepath="vector_mask.tif")
+
+
 def shift_image(img, y_off=0, x_off=0):
     """karios.core.image.shift_image (image.py:70-101), executed on the GPU."""
     return ops.shift_image(img, y_off=y_off, x_off=x_off)

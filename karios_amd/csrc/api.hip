@@ -180,6 +180,7 @@ int km_set_option(km_ctx *c, const char *name, int value)
     if (strcmp(name, "topk_factor") == 0) { c->opt_topk_factor = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "select_first") == 0) { c->opt_select_first = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "stash_cap") == 0) { c->opt_stash_cap = value < 0 ? 0 : value; return KM_OK; }
+    if (strcmp(name, "mask_edge_chunk") == 0) { c->opt_mask_edge_chunk = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "spec_flag") == 0) { c->opt_spec_flag = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "ransac_first_batch") == 0) { c->opt_ransac_first_batch = value < 0 ? 0 : value; return KM_OK; }
     if (strcmp(name, "defer") == 0) { c->opt_no_defer = value == 0; return KM_OK; }

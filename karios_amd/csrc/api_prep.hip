@@ -4,12 +4,17 @@
 // with the caller (karios_amd/ops/prep.py): it is arithmetic of the SOURCE dtype there, wrap-around of int16 included.
 // Also the display range of the report's overview figure (karios/report/overview_plot.py:134-194): the same select under the
 // reference's invalid-pixel rule; kernels in k_report.hip.
+// And the masks a pair is matched under (karios/api/core.py:538-620 _load_mask): a vector mask burnt on the monitored raster's grid
+// (karios/core/image.py:104-191) and its AND with a raster mask; kernels in k_mask.hip.
 #include "api_internal.hpp"
+#include "k_mask.hpp"
 #include "k_prep.hpp"
 #include "k_report.hpp"
 
 #include <stddef.h>
 #include <string.h>
+
+#include <vector>
 
 namespace {
 
@@ -149,9 +154,151 @@ int clahe_dev(km_ctx *c, const uint8_t *d_img, int H, int W, ptrdiff_t stride, c
     return kp_clahe(c, d_img, H, W, stride, g, d_hist, (uint8_t *)(d_hist + tiles * 256), d_out, ostride);
 }
 
+// ---- vector masks (k_mask.hip)
+struct polygon_tables {
+    std::vector<mk::edge> edges;
+    std::vector<kmk_feature> features;
+};
+
+int polygons_args(km_ctx *c, const double *xy, int n_vertices, const int32_t *ring_sizes, int n_rings, const int32_t *feature_rings, int n_features, int H,
+                  int W, const uint8_t *out, ptrdiff_t stride, polygon_tables &t)
+{
+    if (H < 1 || W < 1 || (unsigned long long)H * (unsigned long long)W >= 0xFFFFFFFFull)
+        return km_fail(c, KM_E_ARG, "rasterize_polygons: a raster of %d x %d (at least 1 x 1, fewer than 2^32 - 1 pixels)", H, W);
+    if (!out || stride < W) return km_fail(c, KM_E_ARG, "rasterize_polygons: null output or row stride %td < width %d", stride, W);
+    const char *why = kmk_tables(xy, n_vertices, ring_sizes, n_rings, feature_rings, n_features, H, t.edges, t.features);
+    if (why) return km_fail(c, KM_E_ARG, "rasterize_polygons: %s", why);
+    return KM_OK;
+}
+
+// the tables to the device, then the fill and the line pass into d_out; *d_flag: raised by a walk that exceeded its cap
+int polygons_enqueue(km_ctx *c, const polygon_tables &t, int H, int W, uint8_t *d_out, ptrdiff_t stride, int32_t **d_flag)
+{
+    const size_t eb = t.edges.size() * sizeof(mk::edge), fb = t.features.size() * sizeof(kmk_feature);
+    char *d_tab = (char *)km_ws(c, WS_MK_EDGES, up256(eb) + up256(fb) + 256);
+    *d_flag = (int32_t *)km_ws(c, WS_MK_STATE, 256);
+    if (!d_tab || !*d_flag) return KM_E_NOMEM;
+    int rc;
+    if (eb && (rc = km_h2d_small(c, d_tab, t.edges.data(), eb))) return rc;
+    if (fb && (rc = km_h2d_small(c, d_tab + up256(eb), t.features.data(), fb))) return rc;
+    KM_HIP(c, hipMemsetAsync(*d_flag, 0, sizeof(int32_t), c->stream));
+    const kmk_polygons p = {(const mk::edge *)d_tab, (int)t.edges.size(), (const kmk_feature *)(d_tab + up256(eb)), (int)t.features.size(), H, W, d_out, stride};
+    c->mask_timed = false;
+    const bool timed = c->profiling;
+    if (timed) {
+        for (auto &e : c->ev_mask) KM_HIP(c, e.create(0));      // (flags 0: timing events)
+        KM_HIP(c, hipEventRecord(c->ev_mask[0], c->stream));
+    }
+    if ((rc = kmk_fill(c, p, c->opt_mask_edge_chunk))) return rc;
+    if (timed) KM_HIP(c, hipEventRecord(c->ev_mask[1], c->stream));
+    if ((rc = kmk_lines(c, p, *d_flag))) return rc;
+    if (timed) KM_HIP(c, hipEventRecord(c->ev_mask[2], c->stream));
+    c->mask_timed = timed;
+    return KM_OK;
+}
+
+int polygons_flag(km_ctx *c, int32_t flag)
+{
+    return flag ? km_fail(c, KM_E_INTERNAL, "rasterize_polygons: a line walk exceeded 4 (H + W) + 64 steps") : (int)KM_OK;
+}
+
+int mask_and_args(km_ctx *c, const uint8_t *a, ptrdiff_t sa, const uint8_t *b, ptrdiff_t sb, int H, int W, const uint8_t *out, ptrdiff_t so,
+                  const int64_t *counts)
+{
+    int rc;
+    if ((rc = check_image(c, a, H, W, sa, "mask_and")) || (rc = check_image(c, b, H, W, sb, "mask_and")) || (rc = check_image(c, out, H, W, so, "mask_and output")))
+        return rc;
+    if (!counts) return km_fail(c, KM_E_ARG, "mask_and: null counts");
+    return KM_OK;
+}
+
+int mask_and_dev(km_ctx *c, const uint8_t *d_a, ptrdiff_t sa, const uint8_t *d_b, ptrdiff_t sb, int H, int W, uint8_t *d_out, ptrdiff_t so,
+                 unsigned long long **d_counts)
+{
+    *d_counts = (unsigned long long *)km_ws(c, WS_MK_STATE, 256);
+    if (!*d_counts) return KM_E_NOMEM;
+    return kmk_mask_and(c, d_a, sa, d_b, sb, H, W, d_out, so, *d_counts);
+}
+
+// a dense device plane back into the caller's rows: one copy where they are dense, else row by row
+int plane_out(km_ctx *c, uint8_t *out, ptrdiff_t stride, const uint8_t *d_plane, int H, int W)
+{
+    if (stride == W || H == 1) KM_D2H(c, out, d_plane, (size_t)H * W);
+    else for (int y = 0; y < H; y++) KM_D2H(c, out + (ptrdiff_t)y * stride, d_plane + (size_t)y * W, (size_t)W);
+    return KM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int km_rasterize_polygons_dev(km_ctx *c, const double *xy, int n_vertices, const int32_t *ring_sizes, int n_rings, const int32_t *feature_rings,
+                              int n_features, int H, int W, uint8_t *d_out, ptrdiff_t out_stride)
+{
+    int rc;
+    polygon_tables t;
+    if ((rc = begin_call(c)) || (rc = polygons_args(c, xy, n_vertices, ring_sizes, n_rings, feature_rings, n_features, H, W, d_out, out_stride, t)))
+        return rc;
+    int32_t *d_flag, flag = 0;
+    if ((rc = polygons_enqueue(c, t, H, W, d_out, out_stride, &d_flag))) return rc;
+    KM_D2H(c, &flag, d_flag, sizeof flag);
+    KM_FLUSH(c);
+    return polygons_flag(c, flag);
+}
+
+int km_rasterize_polygons(km_ctx *c, const double *xy, int n_vertices, const int32_t *ring_sizes, int n_rings, const int32_t *feature_rings,
+                          int n_features, int H, int W, uint8_t *out, ptrdiff_t out_stride)
+{
+    int rc;
+    polygon_tables t;
+    if ((rc = begin_call(c)) || (rc = polygons_args(c, xy, n_vertices, ring_sizes, n_rings, feature_rings, n_features, H, W, out, out_stride, t)))
+        return rc;
+    uint8_t *d_out = (uint8_t *)km_ws(c, WS_MK_IO, (size_t)H * W);
+    if (!d_out) return KM_E_NOMEM;
+    int32_t *d_flag, flag = 0;
+    if ((rc = polygons_enqueue(c, t, H, W, d_out, W, &d_flag)) || (rc = plane_out(c, out, out_stride, d_out, H, W))) return rc;
+    KM_D2H(c, &flag, d_flag, sizeof flag);
+    KM_FLUSH(c);
+    return polygons_flag(c, flag);
+}
+
+int km_mask_pass_ms(km_ctx *c, float *fill_ms, float *lines_ms)
+{
+    if (!c || !fill_ms || !lines_ms) return km_fail(c, KM_E_ARG, "km_mask_pass_ms: null argument");
+    if (!c->mask_timed) return km_fail(c, KM_E_ARG, "km_mask_pass_ms: the last km_rasterize_polygons* call did not run under km_set_profiling(1)");
+    KM_HIP(c, hipEventElapsedTime(fill_ms, c->ev_mask[0], c->ev_mask[1]));
+    KM_HIP(c, hipEventElapsedTime(lines_ms, c->ev_mask[1], c->ev_mask[2]));
+    return KM_OK;
+}
+
+int km_mask_and_dev(km_ctx *c, const uint8_t *d_a, ptrdiff_t a_stride, const uint8_t *d_b, ptrdiff_t b_stride, int H, int W, uint8_t *d_out,
+                    ptrdiff_t out_stride, int64_t *counts)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = mask_and_args(c, d_a, a_stride, d_b, b_stride, H, W, d_out, out_stride, counts))) return rc;
+    unsigned long long *d_counts;
+    if ((rc = mask_and_dev(c, d_a, a_stride, d_b, b_stride, H, W, d_out, out_stride, &d_counts))) return rc;
+    KM_D2H(c, counts, d_counts, 3 * sizeof(int64_t));
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+int km_mask_and(km_ctx *c, const uint8_t *a, ptrdiff_t a_stride, const uint8_t *b, ptrdiff_t b_stride, int H, int W, uint8_t *out,
+                ptrdiff_t out_stride, int64_t *counts)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = mask_and_args(c, a, a_stride, b, b_stride, H, W, out, out_stride, counts))) return rc;
+    void *d_a, *d_b;
+    uint8_t *d_out = (uint8_t *)km_ws(c, WS_MK_IO, (size_t)H * W);
+    if (!d_out) return KM_E_NOMEM;
+    if ((rc = upload_image(c, WS_RAW_A, a, 1, H, W, a_stride, &d_a)) || (rc = upload_image(c, WS_RAW_B, b, 1, H, W, b_stride, &d_b))) return rc;
+    unsigned long long *d_counts;
+    if ((rc = mask_and_dev(c, (const uint8_t *)d_a, W, (const uint8_t *)d_b, W, H, W, d_out, W, &d_counts)) || (rc = plane_out(c, out, out_stride, d_out, H, W)))
+        return rc;
+    KM_D2H(c, counts, d_counts, 3 * sizeof(int64_t));
+    KM_FLUSH(c);
+    return KM_OK;
+}
 
 int km_order_statistics_dev(km_ctx *c, const void *d_img, int dtype, int H, int W, ptrdiff_t stride, int exclude, int n_q, const double *q,
                             int64_t *n_out, double *v0, double *v1, double *vi)

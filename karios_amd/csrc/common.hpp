@@ -208,6 +208,9 @@ enum km_slot {
     WS_CE_COLS,     //   x | y | radial error of the scaled sample, kept between the stages; then the density z
     WS_CE_TAB,      //   the edges of a stage and its counters
     WS_CE_IO,       //   columns and outputs of the host-API form
+    WS_MK_EDGES,    // api_prep.hip (vector masks, k_mask.hip): the edges of every feature, 32 bytes each, then the feature table
+    WS_MK_STATE,    //   the walk-cap flag; the three counts of km_mask_and
+    WS_MK_IO,       //   planes of the host-API forms
     WS_COUNT
 };
 
@@ -345,6 +348,8 @@ struct km_ctx {
     // synchronisations of the corner selection): km_wait_readback runs ONE deferred job between the copy and the wait.
     std::vector<std::function<int()>> deferred;
     km_event_h ev_readback;
+    km_event_h ev_mask[3];     // km_rasterize_polygons* under km_set_profiling(1): in front of the fill, between the passes, behind the lines
+    bool mask_timed = false;   //   ... the last such call recorded them (km_mask_pass_ms)
     bool profiling = false;
     int fused_eig = 1;         // km_set_option("fused_eig"): 1 = K3+K4 fused (k_eig2.hip, no eig map), 0 = eig map + candidate scan
     // test knobs (km_set_option, 0 = default): shrunken capacities that force the corner detector's retry paths
@@ -365,6 +370,7 @@ struct km_ctx {
     int opt_profile_stage = -1;    // "profile_stage": with profiling on, time only this stage (-1: every stage; each timed span costs two events = two pipeline drains)
     int opt_stash_cap = 0;         // "stash_cap": kept keys a workgroup of the scatter launch stashes in LDS (small values force its second read of the keys)
     int opt_spec_flag = 0;         // "spec_flag": KM_FLAG_* bits raised artificially by the speculative path (tests of the repeat logic)
+    int opt_mask_edge_chunk = 0;   // "mask_edge_chunk": edges per LDS chunk of the polygon fill (k_mask.hip; small values force many chunks per feature)
     bool opt_roctx = false;        // "roctx": roctx ranges around the stages
     bool opt_fft_cross_fused = true;   // "fft_cross": the cross-power step fused into the first inverse pass's row load (61 M rows)
     bool opt_fft_herm = true;      // "fft_herm" 1 (default): the inverse transform of the float32 phase correlation works on the Hermitian half plane (rows of length 61 M on both sides)

@@ -21,3 +21,4 @@ from .sift import *
 from .accuracy import *
 from .chips import *
 from .report import *
+from .mask import *

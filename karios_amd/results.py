@@ -8,7 +8,9 @@
   * `_check_quality`       - `KariosAPI._check_quality` (core.py:491-506): the dynamic range between the 2nd and 98th percentile
                               of both rasters, a warning when it is 10 or less;
   * `analyze_accuracy`     - `KariosAPI.analyze_accuracy` (core.py:268-328): valid pixels of the monitored raster under the mask,
-                              `GeometricStat`'s statistics, CE90 / CE95 and the line of `correl_res.txt`.
+                              `GeometricStat`'s statistics, CE90 / CE95 and the line of `correl_res.txt`;
+  * `load_mask`            - `KariosAPI._load_mask` (core.py:538-620): the raster mask, the vector mask burnt on the monitored image's
+                              grid (`core.image.rasterize_vector_mask`), or their AND with the three logged counts.
 
 The pixel work (ZNCC, MI / NMI, DN gather) runs on the device through `ResidentPair`; the column arithmetic and the
 CSV formatting are the reference's own numpy / pandas expressions.
@@ -107,6 +109,49 @@ def _check_quality(monitored_image, reference_image) -> tuple:
     if min_max_ref[1] - min_max_ref[0] <= 10:
         logger.warning("Low dynamic range detected for reference, you could get poor results")
     return min_max_mon, min_max_ref
+
+
+def _mask_pixels(image):
+    """The pixels of a mask image: a device tensor for a `DeviceRasterImage`, else its array."""
+    return image.tensor if hasattr(image, "tensor") else image.array if hasattr(image, "array") else np.asarray(image)
+
+
+def load_mask(monitored, raster_mask=None, vector=None, geo_transform=None):
+    """`KariosAPI._load_mask` (core.py:538-620) minus the files: `raster_mask` (a raster image of the monitored image's shape, or
+    None) and `vector` (what `core.image.rasterize_vector_mask` takes, or None) -> None, the one mask given, or their AND - a pixel
+    is valid only if it is valid in BOTH - with the reference's log line and its three counts.  The vector mask is burnt, and the AND
+    taken, where the monitored image lives: for a `DeviceRasterImage` nothing but the polygon's vertices (and a raster mask that
+    is still on the host) crosses PCIe.  ValueError for a raster mask of another shape (the reference's geo-information check
+    stays with the integrator, who holds the geo information)."""
+    from .core.image import DeviceRasterImage, NumpyRasterImage, rasterize_vector_mask
+    shape = (int(monitored.y_size), int(monitored.x_size))
+    if raster_mask is not None:
+        if (int(raster_mask.y_size), int(raster_mask.x_size)) != shape:
+            raise ValueError(f"Mask shape {(raster_mask.y_size, raster_mask.x_size)} not compatible with monitored image {shape}")
+        logger.info("Raster mask loaded")
+    vector_mask = None
+    if vector is not None:
+        vector_mask = rasterize_vector_mask(vector, monitored, geo_transform)
+        logger.info("Vector mask rasterized and loaded")
+    if raster_mask is None and vector_mask is None:
+        logger.info("No mask provided")
+        return None
+    if raster_mask is None:
+        return vector_mask
+    if vector_mask is None:
+        return raster_mask
+    logger.info("Combining raster and vector masks with AND logic")
+    a, b = _mask_pixels(raster_mask), _mask_pixels(vector_mask)
+    on_device = hasattr(b, "data_ptr")
+    if on_device and not hasattr(a, "data_ptr"):
+        import torch
+        a = torch.as_tensor(np.ascontiguousarray((np.asarray(a) > 0).astype(np.uint8)), device=b.device)
+    elif not on_device and hasattr(a, "data_ptr"):
+        a = a.detach().cpu().numpy()
+    combined, (raster_valid, vector_valid, combined_valid) = ops.combine_masks(a, b)
+    logger.info("Mask combination: raster=%d valid pixels, vector=%d valid pixels, combined=%d valid pixels (AND logic)",
+                raster_valid, vector_valid, combined_valid)
+    return DeviceRasterImage(combined, filepath="combined_mask.tif") if on_device else NumpyRasterImage(combined, filepath="combined_mask.tif")
 
 
 @dataclass
