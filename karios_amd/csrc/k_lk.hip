@@ -155,8 +155,10 @@ __device__ __forceinline__ long long wave_sum_split(int v)
     const int lo = v & 0xffff, hi = v >> 16;
     return ((long long)wave_sum_i32_dpp(hi) << 16) + (long long)wave_sum_i32_dpp(lo);
 }
-// the same for a per-lane magnitude < 2^29 (the mismatch sums: <= 10 pixels x 8160 x 4080 = 3.3e8): the first two steps of the scan add
-// at most four lanes - still an int32 - so they run once, unsplit; only the remaining four steps need the two 16-bit halves
+// the same when the sum over FOUR NEIGHBOURING LANES (4 i .. 4 i + 3) has a magnitude < 2^31: the first two steps of the scan add at
+// most four lanes - still an int32 - so they run once, unsplit; only the remaining four steps need the two 16-bit halves.  A bound on
+// the single lane is not enough: the four lanes of a group hold runs of the same window rows and reach their largest values together
+// (0 / 255 stripes, tests/lk_cases.py).  Callers: lk_mismatch_sum below.
 __device__ __forceinline__ long long wave_sum_split4(int v)
 {
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
@@ -201,6 +203,17 @@ typedef short lk_s2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ lk_s2 lk_as_s2(uint32_t v) { return __builtin_bit_cast(lk_s2, v); }
 __device__ __forceinline__ uint32_t lk_as_u(lk_s2 v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ uint32_t lk_pack16(int lo, int hi) { return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u); }
+
+// Wave sum of a mismatch component of the resident-patch form.  A pixel contributes at most 8160 x 4080 (Q5 difference of two uint8
+// x Scharr value), a lane holds 5 NR pixels, so four lanes stay below 2^31 for NR <= 3 (4 x 15 x 8160 x 4080 = 2.0e9: winSize <= 30,
+// the win-25 kernels among them) and wave_sum_split4 is exact.  NR = 4 (winSize 31 .. 35) reaches 2.66e9 and NR = 5 (36 .. 40) 3.33e9
+// on saturated stripes - the unsplit steps wrapped and b was off by a multiple of 2^32 x 2^-20 - so those split before the first step.
+template <int NR>
+__device__ __forceinline__ long long lk_mismatch_sum(int v)
+{
+    if constexpr (4ll * LK_RUN * NR * 8160 * 4080 < (1ll << 31)) return wave_sum_split4(v);
+    else return wave_sum_split(v);
+}
 
 // Track one point from image pyramid I to J (all lanes hold identical scalars).
 // run_desc[t] = y | x0 << 8 | n << 16 (n = 0: the lane has no t-th run).
@@ -724,7 +737,7 @@ __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, u
                     sb2 = __builtin_amdgcn_sdot2(jv, lk_as_s2(IyP[t][q2]), sb2, false);
                 }
             }
-            const long long ib1 = wave_sum_split4(sb1), ib2 = wave_sum_split4(sb2);
+            const long long ib1 = lk_mismatch_sum<NR>(sb1), ib2 = lk_mismatch_sum<NR>(sb2);
             const float b1 = (float)ib1 * FLT_SCALE, b2 = (float)ib2 * FLT_SCALE;
             const float ddx = (A12 * b2 - A22 * b1) * D;
             const float ddy = (A12 * b1 - A11 * b2) * D;
