@@ -334,6 +334,27 @@ int km_zncc_batch(km_ctx *ctx, const void *ref, const void *mon, int dtype, int 
 int km_zncc_windows(km_ctx *ctx, const void *img1, const void *img2, int dtype1, int dtype2, int H1, int W1, int H2,
                     int W2, ptrdiff_t stride1, ptrdiff_t stride2, const int32_t *uv, int half_size, int count,
                     double *out, uint8_t *out_outside);
+/* ---- the ZNCC search around each key point (no counterpart in the reference's call graph; tests/zncc_search_restatement.py is the
+ * definition).  Centres and skip rule are km_zncc_batch's: X0 = int(x0), X1 = round(x0 + dx) on the float32 sum.  For oy, ox in
+ * -radius .. radius (S = 2 radius + 1, 1 <= radius <= 8), surface[oy][ox] = _zncc2(ref, mon, Y0, X0, Y1 + oy, X1 + ox, 21): NaN where
+ * the 43 x 43 window leaves `mon` or a window has no variance; the value at (0, 0) is km_zncc_batch's.  Integer pixel types take the
+ * value from exact integer moments (a function of the pixels alone, the same bits on the host and the device); float32 from two-pass
+ * float64 sums.  The peak is the largest value, the first in raster order among equals; per axis the vertex of the parabola through
+ * the peak and its two neighbours refines it (float64, (zl - 2 zc) + zr in the denominator, |step| <= 0.5).
+ *   out_offset[k] = (bx, by); out_peak[k]; out_shift[k] = (X1 + bx - X0 + sx, Y1 + by - Y0 + sy)
+ *   out_status[k] bits: 1 row skipped (outputs NaN, offset 0); 2 no offset has a value (the same); 4 the peak lies on the rim of the
+ *   square or a neighbour has no value, in x (then sx = 0); 8 the same in y
+ *   out_surface: NULL, or n x S x S
+ * Strides in pixels; 0 <= n <= 2^20 (n == 0: KM_OK, nothing launched).  KM_E_ARG: a bad dtype, radius, n, or a null array with n > 0.
+ * With an image window set (km_set_image_window) both forms return KM_E_UNSUPPORTED and queue nothing.  The device form leaves its
+ * work queued on the context stream. */
+int km_zncc_search(km_ctx *ctx, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon,
+                   ptrdiff_t stride_ref, ptrdiff_t stride_mon, const float *x0, const float *y0, const float *dx, const float *dy,
+                   int n, int radius, int32_t *out_offset, double *out_peak, double *out_shift, uint8_t *out_status, double *out_surface);
+int km_zncc_search_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int Href, int Wref, int Hmon, int Wmon,
+                       ptrdiff_t stride_ref, ptrdiff_t stride_mon, const float *d_x0, const float *d_y0, const float *d_dx,
+                       const float *d_dy, int n, int radius, int32_t *d_offset, double *d_peak, double *d_shift, uint8_t *d_status,
+                       double *d_surface);
 /* Mutual-information scores per keypoint on the 57x57 chips (next to ZNCC in _handle_klt_results, api/core.py:894-907):
  * out_studholme[k] = MutualInfoService._mutual_info  (matcher/mutual_info_service.py:32-63, column mutual_info_score)
  * out_nmi[k]       = ZNCCService._mutual_information (matcher/zncc_service.py:129-151,      column mi_score)

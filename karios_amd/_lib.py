@@ -112,6 +112,7 @@ CE_MAX_BINS = 65536            # KM_CE_MAX_BINS
 DISPLAY_MAX_NO_VALUES = 16     # KM_DISPLAY_MAX_NO_VALUES
 PROFILE_MAX, PROFILE_MAX_ROWS, PROFILE_MAX_BIN = 8, 1 << 20, 1 << 24   # KM_PROFILE_MAX; rows and bin size km_mean_profiles takes
 BOX_STATS = 8                  # KM_BOX_STATS: q1, med, q3, iqr, cilo, cihi, whislo, whishi
+ZNCC_SEARCH_MAX_RADIUS, ZNCC_SEARCH_MAX_ROWS = 8, 1 << 20   # radius and rows km_zncc_search takes
 MASK_MAX_VERTICES, MASK_MAX_COORD = 1 << 20, float(2 ** 30)   # vertices and |coordinate| km_rasterize_polygons takes
 CHIP_SIZE, CHIP_MAX_GRID, CHIP_PICKS = 57, 16, 5     # KM_CHIP_SIZE, KM_CHIP_MAX_GRID, KM_CHIP_PICKS
 CHIP_SELECT_MAX_ROWS, CHIP_MAX_ROWS = 1 << 24, 1 << 20
@@ -181,6 +182,8 @@ SIGNATURES = {
     "km_tile_prefilter": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _pd, _pd, _i, _i, _i, _vp, _vp, _vp, C.POINTER(C.c_int64)]),
     "km_zncc_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _vp]),
     "km_mi_batch": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "km_zncc_search": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "km_zncc_search_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "km_zncc_windows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _sz, _sz, _vp, _i, _i, _vp, _vp]),
     "km_phase_shift": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _pd]),
     "km_shift_image": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _i, _vp]),

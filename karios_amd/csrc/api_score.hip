@@ -1,8 +1,80 @@
-// Scoring entry points: ZNCCService.compute_zncc / _zncc2 (zncc_service.py:45-238), the mutual-information scores
+// Scoring entry points: ZNCCService.compute_zncc / _zncc2 (zncc_service.py:45-238), the ZNCC search around each key point
+// (k_zncc_search.hip; no counterpart in the reference's call graph), the mutual-information scores
 // (mutual_info_service.py:73-130, zncc_service.py:240-287), the DN-value filter of the key points (core.py:650-737).
 #include "api_internal.hpp"
+#include "k_zncc_search.hpp"
+
+namespace {
+
+// what km_zncc_search and km_zncc_search_dev refuse alike; n == 0 passes (nothing is launched then)
+int search_args(km_ctx *c, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref, ptrdiff_t smon,
+                const float *x0, const float *y0, const float *dx, const float *dy, int n, int radius, const int32_t *offset, const double *peak,
+                const double *shift, const uint8_t *status)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_image(c, ref, Href, Wref, sref, "zncc_search")) || (rc = check_image(c, mon, Hmon, Wmon, smon, "zncc_search")))
+        return rc;
+    if (!km_dtype_size(dtype)) return km_fail(c, KM_E_ARG, "zncc_search: bad dtype %d", dtype);
+    if (radius < 1 || radius > zs::MAX_RADIUS) return km_fail(c, KM_E_ARG, "zncc_search: radius %d (1 .. %d)", radius, zs::MAX_RADIUS);
+    if (n < 0 || n > zs::MAX_ROWS) return km_fail(c, KM_E_ARG, "zncc_search: %d rows (0 .. 2^20)", n);
+    if (n > 0 && (!x0 || !y0 || !dx || !dy || !offset || !peak || !shift || !status)) return km_fail(c, KM_E_ARG, "zncc_search: null keypoint or output array");
+    if (c->window.H) return km_fail(c, KM_E_UNSUPPORTED, "zncc_search: an image window is set (km_set_image_window); the search reads whole rasters");
+    return KM_OK;
+}
+
+}  // namespace
 
 extern "C" {
+
+int km_zncc_search_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref,
+                       ptrdiff_t smon, const float *d_x0, const float *d_y0, const float *d_dx, const float *d_dy, int n, int radius,
+                       int32_t *d_offset, double *d_peak, double *d_shift, uint8_t *d_status, double *d_surface)
+{
+    int rc;
+    if ((rc = search_args(c, d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_shift, d_status)))
+        return rc;
+    if (n == 0) return KM_OK;
+    const kzs_args a = {d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_shift, d_status, d_surface};
+    c->evs_used[c->ev_cur][ST_ZNCC] = false;
+    km_stage_timer t(c, ST_ZNCC);
+    return kzs_search(c, a);
+}
+
+int km_zncc_search(km_ctx *c, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref,
+                   ptrdiff_t smon, const float *x0, const float *y0, const float *dx, const float *dy, int n, int radius, int32_t *out_offset,
+                   double *out_peak, double *out_shift, uint8_t *out_status, double *out_surface)
+{
+    int rc;
+    if ((rc = search_args(c, ref, mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, x0, y0, dx, dy, n, radius, out_offset, out_peak, out_shift, out_status)))
+        return rc;
+    if (n == 0) return KM_OK;
+    const size_t es = km_dtype_size(dtype), N = (size_t)n, SS = (size_t)(2 * radius + 1) * (2 * radius + 1);
+    void *d_ref, *d_mon;
+    if ((rc = upload_image(c, WS_RAW_A, ref, es, Href, Wref, sref, &d_ref)) || (rc = upload_image(c, WS_RAW_B, mon, es, Hmon, Wmon, smon, &d_mon)))
+        return rc;
+    // peak | shift | offset | status in one slot (each part a multiple of 256 bytes apart); the surface in one of its own
+    const size_t o_shift = up256(N * sizeof(double)), o_offset = o_shift + up256(2 * N * sizeof(double)), o_status = o_offset + up256(2 * N * sizeof(int32_t));
+    char *d_out = (char *)km_ws(c, WS_MISC1, o_status + up256(N));
+    double *d_surface = out_surface ? (double *)km_ws(c, WS_MISC2, N * SS * sizeof(double)) : nullptr;
+    if (!d_out || (out_surface && !d_surface)) return KM_E_NOMEM;
+    const float *src[4] = {x0, y0, dx, dy};
+    float *kp;
+    if ((rc = upload_columns(c, WS_MISC0, src, 4, n, &kp))) return rc;
+    const kzs_args a = {d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, Wref, Wmon, kp, kp + N, kp + 2 * N, kp + 3 * N, n, radius,
+                        (int32_t *)(d_out + o_offset), (double *)d_out, (double *)(d_out + o_shift), (uint8_t *)(d_out + o_status), d_surface};
+    {
+        c->evs_used[c->ev_cur][ST_ZNCC] = false;
+        km_stage_timer t(c, ST_ZNCC);
+        if ((rc = kzs_search(c, a))) return rc;
+    }
+    KM_D2H(c, out_peak, a.peak, N * sizeof(double));
+    KM_D2H(c, out_shift, a.shift, 2 * N * sizeof(double));
+    KM_D2H(c, out_offset, a.offset, 2 * N * sizeof(int32_t));
+    KM_D2H(c, out_status, a.status, N);
+    if (out_surface) KM_D2H(c, out_surface, d_surface, N * SS * sizeof(double));
+    KM_FLUSH(c);
+    return KM_OK;
+}
 
 int km_zncc_batch_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref,
                       ptrdiff_t smon, const float *d_x0, const float *d_y0, const float *d_dx, const float *d_dy, int n, double *d_out)
@@ -61,7 +133,11 @@ int km_zncc_windows(km_ctx *c, const void *img1, const void *img2, int dtype1, i
     uint8_t *d_fl = (uint8_t *)km_ws(c, WS_MISC2, (size_t)count);
     if (!d_uv || !d_out || !d_fl) return KM_E_NOMEM;
     { const int rch = h2d_now(c, d_uv, uv, (size_t)count * 4 * sizeof(int)); if (rch) return rch; }
-    if ((rc = kz_zncc_windows(c, d1, d2, dtype1, dtype2, H1, W1, H2, W2, W1, W2, d_uv, half_size, count, d_out, d_fl))) return rc;
+    {
+        c->evs_used[c->ev_cur][ST_ZNCC] = false;      // (timed like the other ZNCC kernels: tools/ubench/zncc_search.py reads it)
+        km_stage_timer t(c, ST_ZNCC);
+        if ((rc = kz_zncc_windows(c, d1, d2, dtype1, dtype2, H1, W1, H2, W2, W1, W2, d_uv, half_size, count, d_out, d_fl))) return rc;
+    }
     KM_D2H(c, out, d_out, (size_t)count * sizeof(double));
     if (out_outside) KM_D2H(c, out_outside, d_fl, (size_t)count);
     KM_FLUSH(c);

@@ -15,7 +15,7 @@ from pandas import DataFrame, Series
 
 from .. import ops
 from .._lib import _DTYPES
-from ..resident import keep_shared_across, shared_pair
+from ..resident import ZNCC_SEARCH_COLUMNS, keep_shared_across, search_columns, shared_pair
 
 logger = logging.getLogger(__name__)
 
@@ -59,6 +59,38 @@ def _chip_centres(df: DataFrame, margin: int, ref_shape, mon_shape):
     return cy0, cx0, cy1, cx1, inside
 
 
+def surface_peaks(surface: np.ndarray, radius: int, centres, inside) -> ops.ZnccSearch:
+    """The peak and the per-axis parabola of ZNCC surfaces, the numpy form of csrc/zncc_math.hpp (`finish`): float64, every operation
+    rounded on its own and in the header's order.  surface: n x S x S (NaN: no value); centres: (X0, Y0, X1, Y1) integer arrays;
+    inside: the rows that are scored at all (the others: status 1, NaN, offset 0)."""
+    z = np.asarray(surface, np.float64)
+    n, S = len(z), 2 * radius + 1
+    X0, Y0, X1, Y1 = (np.asarray(v, np.int64) for v in centres)
+    has = np.asarray(inside, bool) & ~np.isnan(z).all(axis=(1, 2))
+    best = np.zeros(n, np.int64)
+    if has.any():
+        best[has] = np.nanargmax(z[has].reshape(-1, S * S), axis=1)                    # the first of equal values
+    iy, ix = np.divmod(best, S)
+    zp = np.pad(z, ((0, 0), (1, 1), (1, 1)), constant_values=np.nan)
+    k = np.arange(n)
+    zc = zp[k, iy + 1, ix + 1]
+
+    def step(pos, zl, zr):
+        rim = (pos == 0) | (pos == S - 1) | np.isnan(zl) | np.isnan(zr)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            den = (zl - 2.0 * zc) + zr
+            s = 0.5 * (zl - zr) / den
+        return np.where(~rim & (den < 0.0), s, 0.0), rim
+
+    sx, rim_x = step(ix, zp[k, iy + 1, ix], zp[k, iy + 1, ix + 2])
+    sy, rim_y = step(iy, zp[k, iy, ix + 1], zp[k, iy + 2, ix + 1])
+    offset = np.where(has[:, None], np.stack([ix - radius, iy - radius], axis=1), 0).astype(np.int32)
+    shift = np.stack([(X1 + (ix - radius) - X0).astype(np.float64) + sx, (Y1 + (iy - radius) - Y0).astype(np.float64) + sy], axis=1)
+    shift[~has] = np.nan
+    status = np.where(has, ops.ZNCC_RIM_X * rim_x + ops.ZNCC_RIM_Y * rim_y, np.where(inside, ops.ZNCC_NO_VALUE, ops.ZNCC_SKIPPED)).astype(np.uint8)
+    return ops.ZnccSearch(offset, np.where(has, zc, np.nan), shift, status, z)
+
+
 def _kernel_ready(df: DataFrame, ref: np.ndarray, mon: np.ndarray) -> bool:
     """The fused 43x43 kernel applies the float32 rounding rule itself and reads one pixel type for both images."""
     return ref.dtype == mon.dtype and ref.dtype in _DTYPES and _frame_arithmetic_dtype(df) == np.float32
@@ -84,7 +116,41 @@ class ZNCCService:
         logger.info("NMI: %d key points scored", len(df))
         return Series(values, index=df.index, dtype=np.float64)
 
+    def search(self, df: DataFrame, monitored, reference, radius: int = 4) -> DataFrame:
+        """The ZNCC search around every row of `df`: the value of `_zncc2` at the offsets -radius .. radius around the centre
+        `compute_zncc` scores, the peak of that surface and its sub-pixel position (`ops.zncc_search`; the reference has no such
+        call).  -> a frame on `df.index`: zncc_dx, zncc_dy (the displacement the peak stands for, comparable with dx, dy), zncc_peak,
+        zncc_off_x, zncc_off_y (the peak's whole-pixel offset from the rounded KLT position), zncc_status (bit 1: row skipped, 2: no
+        offset has a value, 4 / 8: the peak lies on the rim of the square, or beside an offset without a value, in x / y)."""
+        ops.score._check_search("ZNCCService.search", len(df), radius)
+        columns = self._score(df, monitored, reference, lambda d, ref, mon: self._search_columns(d, ref, mon, int(radius)))
+        if len(df) == 0:
+            columns = search_columns(surface_peaks(np.empty((0, 3, 3)), 1, [np.empty(0)] * 4, np.empty(0, bool)))
+        logger.info("ZNCC search: %d key points, radius %d", len(df), radius)
+        return DataFrame(dict(zip(ZNCC_SEARCH_COLUMNS, columns)), index=df.index)
+
     # ------------------------------------------------------------------ internals
+    def _search_columns(self, df, ref, mon, radius):
+        if _kernel_ready(df, ref, mon):
+            cols = [df[c].to_numpy(dtype=np.float32, copy=False) for c in ("x0", "y0", "dx", "dy")]
+            if ref.shape == mon.shape:
+                return search_columns(shared_pair(mon, ref, self._ctx, rasters=getattr(self, "_rasters", ())).zncc_search(*cols, radius=radius))
+            return search_columns(ops.zncc_search(ref, mon, *cols, radius=radius, ctx=self._ctx))
+        # cross-sensor pairs / other pixel types / float64 frames: centres on the host, all (2R+1)^2 windows of every row by the generic
+        # kernel in one call, the peak and the parabola in numpy
+        u0, v0, u1, v1, inside = _chip_centres(df, self._chip_margin, ref.shape, mon.shape)
+        S = 2 * radius + 1
+        surface = np.full((len(df), S, S), np.nan)
+        if inside.any():
+            o = np.arange(-radius, radius + 1)
+            rows = (u1[inside, None, None] + o[None, :, None]) + 0 * o[None, None, :]
+            cols_ = (v1[inside, None, None] + o[None, None, :]) + 0 * o[None, :, None]
+            values, outside = ops.zncc_windows(ref, mon, np.repeat(u0[inside], S * S), np.repeat(v0[inside], S * S), rows.ravel(), cols_.ravel(),
+                                               WINDOW_HALF, ctx=self._ctx)
+            values = np.where(outside, np.nan, values)
+            surface[inside] = values.reshape(-1, S, S)
+        return search_columns(surface_peaks(surface, radius, (v0, u0, v1, u1), inside))
+
     def _score(self, df, monitored, reference, scorer) -> np.ndarray:
         try:
             if len(df) == 0:

@@ -1,11 +1,12 @@
 """The scores of the key points and the large-offset search (csrc/api_score.hip)."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from .. import _lib
 from .._lib import Context, KariosHipError, as_image, dtype_code, ptr, row_stride
-from ._place import _ctx
+from ._place import Place, _col_args, _ctx, _f32_columns, _raster_arg
 
 
 def zncc_batch(ref, mon, x0, y0, dx, dy, ctx: Context | None = None):
@@ -44,6 +45,44 @@ def zncc_windows(img1, img2, u1, v1, u2, v2, half_size: int, ctx: Context | None
                                       b.shape[0], b.shape[1], row_stride(a), row_stride(b), ptr(uv), int(half_size), count, ptr(out),
                                       ptr(outside)), "km_zncc_windows")
     return out, outside.astype(bool)
+
+
+ZnccSearch = namedtuple("ZnccSearch", "offset peak shift status surface")
+ZNCC_SKIPPED, ZNCC_NO_VALUE, ZNCC_RIM_X, ZNCC_RIM_Y = 1, 2, 4, 8          # bits of ZnccSearch.status
+
+
+def _check_search(what, n, radius):
+    if int(radius) != radius or not 1 <= radius <= _lib.ZNCC_SEARCH_MAX_RADIUS:
+        raise ValueError(f"{what}: radius {radius!r} (an integer, 1 .. {_lib.ZNCC_SEARCH_MAX_RADIUS})")
+    if n > _lib.ZNCC_SEARCH_MAX_ROWS:
+        raise ValueError(f"{what}: {n} rows (at most 2^20)")
+
+
+def zncc_search(ref, mon, x0, y0, dx, dy, radius: int = 4, surface: bool = False, ctx: Context | None = None):
+    """The ZNCC search around each key point: for oy, ox in -radius .. radius the value `_zncc2(ref, mon, Y0, X0, Y1 + oy, X1 + ox, 21)`
+    (zncc_service.py:45-126) around the centres `compute_zncc` scores (X0 = int(x0), X1 = round(x0 + dx) on the float32 sum), its
+    peak and the peak's sub-pixel position; the reference's call graph has no such search (include/karios_hip.h: km_zncc_search).
+    The rasters (one pixel type of uint8 / uint16 / int16 / float32) and the float32 columns are all numpy arrays or all device tensors.
+    -> ZnccSearch(offset int32[n, 2] = (bx, by), peak float64[n], shift float64[n, 2] = (x, y), status uint8[n] (ZNCC_* bits),
+    surface float64[n, S, S] or None), living where the inputs live."""
+    what = "zncc_search"
+    place = Place([ref, mon], what, "ref and mon")
+    place.require([x0, y0, dx, dy], what, "the rasters and x0, y0, dx, dy")
+    _, cols, n = _f32_columns((x0, y0, dx, dy), what, "x0, y0, dx, dy")
+    _check_search(what, n, radius)
+    radius, S = int(radius), 2 * int(radius) + 1
+    pr, dr, Hr, Wr, sr = _raster_arg(place, ref, what)
+    pm, dm, Hm, Wm, sm = _raster_arg(place, mon, what)
+    if dr != dm or dr not in _lib._DTYPES:
+        raise ValueError(f"{what}: rasters of {dr} / {dm} (one pixel type of uint8, uint16, int16, float32)")
+    out = ZnccSearch(place.empty((n, 2), np.int32), place.empty((n,), np.float64), place.empty((n, 2), np.float64), place.empty((n,), np.uint8),
+                     place.empty((n, S, S), np.float64) if surface else None)
+    if n:
+        place.call(_ctx(ctx), "km_zncc_search", pr, pm, _lib._DTYPES[dr], Hr, Wr, Hm, Wm, sr, sm, *_col_args(place, cols, n), n, radius,
+                   *(place.pointer(a) for a in out))
+        if place.dev:
+            _ctx(ctx).sync()
+    return out
 
 
 def mi_batch(ref, mon, x0, y0, dx, dy, ctx: Context | None = None):

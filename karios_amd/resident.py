@@ -18,6 +18,7 @@ from . import _lib
 from ._lib import Context, KariosHipError, as_image, default_context, dtype_code
 from . import frames, tiling
 from .ops import make_params
+from .ops.score import ZnccSearch, _check_search
 
 
 class DeviceBuffer:
@@ -246,6 +247,14 @@ def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False) ->
 def _clips(conf) -> bool:
     """The configuration asks for the tracker's outlier clip (klt.py:52-71)."""
     return bool(getattr(conf, "outliers_filtering", False))
+
+
+ZNCC_SEARCH_COLUMNS = ["zncc_dx", "zncc_dy", "zncc_peak", "zncc_off_x", "zncc_off_y", "zncc_status"]
+
+
+def search_columns(found: ZnccSearch):
+    """The six frame columns of a search result (ZNCC_SEARCH_COLUMNS), as arrays."""
+    return found.shift[:, 0], found.shift[:, 1], found.peak, found.offset[:, 0], found.offset[:, 1], found.status
 
 
 class ResidentPair:
@@ -689,6 +698,35 @@ class ResidentPair:
         c.sync()
         return scores.copy()
 
+    def zncc_search(self, x0, y0, dx, dy, radius: int = 4, surface: bool = False) -> ZnccSearch:
+        """`ops.zncc_search` on the resident rasters: the ZNCC surface over the offsets -radius .. radius around the centre `zncc`
+        scores, its peak and the peak's sub-pixel position, for key points given in image coordinates -> ZnccSearch of numpy arrays.
+        A windowed pair (row-band mode) raises KariosHipError: the search reads whole rasters."""
+        if self.window is not None:
+            raise KariosHipError("zncc_search: the pair holds a window of its rasters (row-band mode); a windowed search is not supported")
+        cols = [np.ascontiguousarray(v, np.float32) for v in (x0, y0, dx, dy)]
+        n = len(cols[0])
+        _check_search("zncc_search", n, radius)
+        radius = int(radius)
+        SS = (2 * radius + 1) ** 2
+        if n == 0:
+            return ZnccSearch(np.empty((0, 2), np.int32), np.empty(0, np.float64), np.empty((0, 2), np.float64), np.empty(0, np.uint8),
+                              np.empty((0, 2 * radius + 1, 2 * radius + 1), np.float64) if surface else None)
+        self._ready()
+        c = self.ctx
+        # one float64 slot per row for each of: peak | shift x, y | offset (2 x int32) | status (bytes, in the fifth) | the surface
+        kp, out, f, o = self._scratch(n, 5 + (SS if surface else 0))
+        np.concatenate(cols, out=kp)
+        c.check(c.lib.km_zncc_search_dev(c.handle, C.c_void_p(self.ref_ptr), C.c_void_p(self.mon_ptr), self.code, self.y_size, self.x_size,
+                                         self.y_size, self.x_size, self.x_size, self.x_size, C.c_void_p(f), C.c_void_p(f + 4 * n),
+                                         C.c_void_p(f + 8 * n), C.c_void_p(f + 12 * n), n, radius, C.c_void_p(o + 24 * n), C.c_void_p(o),
+                                         C.c_void_p(o + 8 * n), C.c_void_p(o + 32 * n), C.c_void_p(o + 40 * n) if surface else None),
+                "km_zncc_search_dev")
+        c.sync()
+        return ZnccSearch(out[3 * n:4 * n].view(np.int32).reshape(n, 2).copy(), out[:n].copy(), out[n:3 * n].reshape(n, 2).copy(),
+                          out[4 * n:5 * n].view(np.uint8)[:n].copy(),
+                          out[5 * n:].reshape(n, 2 * radius + 1, 2 * radius + 1).copy() if surface else None)
+
     def mutual_info(self, x0, y0, dx, dy):
         """(mutual_info_score, mi_score) per key point on the resident images: `MutualInfoService.compute_mutual_info`
         (mutual_info_service.py:73-130) and `ZNCCService.compute_mi` (zncc_service.py:240-287)."""
@@ -716,10 +754,12 @@ class ResidentPair:
         self._mi_memo = (digest, st, nmi)
         return st.copy(), nmi.copy()
 
-    def score_frame(self, frame: DataFrame, confidence_threshold: float = 0.4, mutual_info: bool = False) -> DataFrame:
+    def score_frame(self, frame: DataFrame, confidence_threshold: float = 0.4, mutual_info: bool = False,
+                    zncc_search_radius: int | None = None) -> DataFrame:
         """`_handle_klt_results` numeric columns (core.py:872-907): radial error, angle, the ZNCC of the rows with
         score >= confidence_threshold (NaN elsewhere) and, with `mutual_info`, the `mutual_info_score` / `mi_score`
-        columns of the same rows."""
+        columns of the same rows.  With `zncc_search_radius` the same rows also get the columns of `zncc_search`
+        (ZNCC_SEARCH_COLUMNS; NaN elsewhere); None, the default, adds nothing."""
         frame = frames.radial_angle_columns(frame)
         dx, dy, score = frame["dx"].to_numpy(), frame["dy"].to_numpy(), frame["score"].to_numpy()
         keep = score >= confidence_threshold
@@ -735,6 +775,12 @@ class ResidentPair:
                 st[keep], nmi[keep] = self.mutual_info(frame["x0"].to_numpy()[keep], frame["y0"].to_numpy()[keep], dx[keep], dy[keep])
             frame["mutual_info_score"] = st
             frame["mi_score"] = nmi
+        if zncc_search_radius is not None:
+            found = self.zncc_search(frame["x0"].to_numpy()[keep], frame["y0"].to_numpy()[keep], dx[keep], dy[keep], zncc_search_radius)
+            for name, values in zip(ZNCC_SEARCH_COLUMNS, search_columns(found)):
+                column = np.full(len(frame), np.nan, np.float64)
+                column[keep] = values
+                frame[name] = column
         return frame
 
     # ------------------------------------------------------------------ key-point chips

@@ -32,7 +32,7 @@ from ._lib import KariosHipError
 from .accuracy_analysis import GeometricStat
 from .core.configuration import AccuracyAnalysisConfiguration
 from .frames import radial_angle_columns
-from .resident import ResidentPair
+from .resident import ZNCC_SEARCH_COLUMNS, ResidentPair
 
 logger = logging.getLogger(__name__)
 
@@ -40,9 +40,11 @@ CSV_COLUMNS = ["x0", "y0", "dx", "dy", "score", "radial error", "angle", "zncc_s
 
 
 def handle_klt_results(results: Iterable[pd.DataFrame], csv_file, pair: ResidentPair, confidence_threshold: float = 0.4,
-                       large_shift_applied: bool = False) -> pd.DataFrame:
+                       large_shift_applied: bool = False, zncc_search_radius: int | None = None) -> pd.DataFrame:
     """`KariosAPI._handle_klt_results` (core.py:848-921) for the frames of `KLT.match` / `ResidentPair.match*`.
-    With `large_shift_applied` the scores are skipped like in the reference (core.py:909-910) and the CSV has 7 columns."""
+    With `large_shift_applied` the scores are skipped like in the reference (core.py:909-910) and the CSV has 7 columns.
+    With `zncc_search_radius` the scored rows also carry the columns of the ZNCC search (`ResidentPair.zncc_search`,
+    ZNCC_SEARCH_COLUMNS) behind the reference's; None, the default, leaves the frame and the CSV as the reference writes them."""
     csv_file = Path(csv_file)
     all_frame = pd.DataFrame()
     for frame in results:
@@ -51,8 +53,8 @@ def handle_klt_results(results: Iterable[pd.DataFrame], csv_file, pair: Resident
             if "zncc_score" in frame.columns:
                 frame = frame.drop(columns=["zncc_score"])
         else:
-            frame = pair.score_frame(frame, confidence_threshold, mutual_info=True)
-            frame = frame[CSV_COLUMNS]           # the reference's column order, whatever produced zncc_score first
+            frame = pair.score_frame(frame, confidence_threshold, mutual_info=True, zncc_search_radius=zncc_search_radius)
+            frame = frame[CSV_COLUMNS + (ZNCC_SEARCH_COLUMNS if zncc_search_radius is not None else [])]      # the reference's column order, whatever produced zncc_score first
         if not csv_file.exists():
             frame.to_csv(csv_file, sep=";", index=False)
         else:
