@@ -102,6 +102,11 @@ int km_set_profiling(km_ctx *ctx, int enable);
  *                  scan.  Initial value from the environment variable KARIOS_HIP_FUSED_EIG
  *   "eig3"         1 (default): the fused pass runs 8 pixels per lane (k_eig3.hip) on images >= 512 columns wide; 0: always the
  *                  2-pixels-per-lane kernel (k_eig2.hip).  Initial value from KARIOS_HIP_EIG3
+ *   "eig3_valid_items" 1 (default): in a batched submission (km_klt_units_frame_submit) with the automatic mask, a strip item of the
+ *                  8-pixel fused pass first reads the valid-pixel counts the Laplacian pass of the same submission left for the
+ *                  Laplacian items that overlap the item's mask rectangle: no valid pixel - the item returns at once; all valid -
+ *                  its interior rows run without the mask; otherwise, with a user mask, and with 0: every item reads the mask
+ *                  row by row.  km_eig3_item_classes counts the items of each class
  *   "lk2"          1 (default): LK on four resident patches per key point (two-level pyramids); 0: the first form (one patch per
  *                  direction and level), which also serves deeper pyramids and row bands
  *   "lk_reuse"     1 (default): an LK iteration of the "lk2" form reads the search patch (LDS) and cuts its byte pairs again only when
@@ -171,6 +176,9 @@ int km_set_option(km_ctx *ctx, const char *name, int value);
 int km_is_dev_build(void);
 /* development build only (KM_E_UNSUPPORTED otherwise): counters of the "eig3_count" option after a blocking tile call */
 int km_dev_counters(km_ctx *ctx, unsigned long long out[2]);
+/* out = {strip items without a valid pixel, all valid, general; tie rows (km_klt_stats.tie_rows)} of the 8-pixel fused eigenvalue pass
+ * for unit `unit` of the context's last km_klt_units_frame_submit.  Synchronises the context (km_ctx_sync) before it reads. */
+int km_eig3_item_classes(km_ctx *ctx, int unit, uint32_t out[4]);
 /* stage times (ms) of the last pipeline call; names via km_stage_name(i) */
 int km_get_stage_ms(km_ctx *ctx, float *out, int cap, int *n);
 const char *km_stage_name(int i);

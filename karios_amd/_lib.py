@@ -138,6 +138,7 @@ SIGNATURES = {
     "km_set_option": (_i, [_vp, C.c_char_p, _i]),
     "km_is_dev_build": (_i, []),
     "km_dev_counters": (_i, [_vp, C.POINTER(C.c_uint64)]),
+    "km_eig3_item_classes": (_i, [_vp, _i, C.POINTER(C.c_uint32)]),
     "km_get_stage_ms": (_i, [_vp, C.POINTER(C.c_float), _i, _pi]),
     "km_stage_name": (C.c_char_p, [_i]),
     "km_get_klt_stats": (_i, [_vp, C.POINTER(KltStats)]),
@@ -506,6 +507,13 @@ class Context:
     @property
     def frame_sink(self) -> tuple:
         return self.__dict__.get("_frame_sink", (None, 0, 0))
+
+    def eig3_item_classes(self, unit: int) -> dict:
+        """Strip items of the fused 8-pixel eigenvalue pass by class ("eig3_valid_items") and its tie rows, for unit `unit` of the last
+        batched submission (km_eig3_item_classes: the context is synchronised first)."""
+        out = (C.c_uint32 * 4)()
+        self.check(self.lib.km_eig3_item_classes(self.handle, int(unit), out), "km_eig3_item_classes")
+        return {"none": int(out[0]), "all": int(out[1]), "general": int(out[2]), "tie_rows": int(out[3])}
 
     def get_option(self, name: str, default: int = 0) -> int:
         """Last value given to `set_option` (the library's own defaults are not queried)."""

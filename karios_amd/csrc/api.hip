@@ -163,6 +163,7 @@ int km_set_option(km_ctx *c, const char *name, int value)
     // bit-identical (tests/test_gpu_forced_paths.py, tests/test_gpu_parity.py), or shrinks a capacity so that a retry path runs
     if (strcmp(name, "fused_eig") == 0) { c->fused_eig = value != 0; return KM_OK; }
     if (strcmp(name, "eig3") == 0) { c->opt_eig3 = value != 0; return KM_OK; }
+    if (strcmp(name, "eig3_valid_items") == 0) { c->opt_eig3_valid_items = value != 0; return KM_OK; }
     if (strcmp(name, "lk2") == 0) { c->opt_lk2 = value != 0; return KM_OK; }
     if (strcmp(name, "lk_reuse") == 0) { c->opt_lk_reuse = value != 0; return KM_OK; }
     if (strcmp(name, "speculative") == 0) { c->opt_speculative = value != 0; return KM_OK; }
@@ -224,6 +225,22 @@ int km_dev_counters(km_ctx *c, unsigned long long out[2])
     (void)out;
     return km_fail(c, KM_E_UNSUPPORTED, "km_dev_counters: development build only");
 #endif
+}
+
+// {no valid pixel, all valid, general} strip items of the fused 8-px eigenvalue pass and its tie rows, for unit `unit` of the last batched
+// submission: the context is synchronised first (a deferred tail included), then the unit's scalar block is read
+int km_eig3_item_classes(km_ctx *c, int unit, uint32_t out[4])
+{
+    if (!c || !out) return km_fail(c, KM_E_ARG, "km_eig3_item_classes: null argument");
+    if (unit < 0 || unit >= c->units_sc_n) return km_fail(c, KM_E_ARG, "km_eig3_item_classes: unit %d of %d", unit, c->units_sc_n);
+    { const int rs = km_ctx_sync(c); if (rs) return rs; }
+    const km_scalars *sc = c->units_sc[unit];
+    unsigned h[4];
+    { const int rq = km_d2h_queue(c, h, sc->eig3_items, 3 * sizeof(unsigned)); if (rq) return rq; }
+    { const int rq = km_d2h_queue(c, h + 3, &sc->tie_rows, sizeof(unsigned)); if (rq) return rq; }
+    { const int rq = km_d2h_flush(c); if (rq) return rq; }
+    for (int i = 0; i < 4; i++) out[i] = h[i];
+    return KM_OK;
 }
 
 // 1: the library was built with -DKM_DEV (development options and KARIOS_HIP_* tuning variables are live); 0: release build

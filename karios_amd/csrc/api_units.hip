@@ -257,6 +257,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         max_px = px > max_px ? px : max_px;
         pyr_off[u] = pyr_total; pyr_total += up256((size_t)((q.H + 1) / 2) * ((q.W + 1) / 2));
     }
+    c->units_sc_n = n;
     U.capk = max_px / 8 + 4096 * KM_NSHARD;
     const size_t sc_stride = up256(sizeof(km_scalars)), pb = up256((size_t)cap * 2 * sizeof(float));
     const km_frame_layout L(cap, with_zncc, with_mi);
@@ -276,6 +277,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
         U.p0[u] = (float *)(p0 + pb * u); U.p1[u] = (float *)(p1 + pb * u); U.p0r[u] = (float *)(p0r + pb * u);
         U.frame[u] = d_out + ob_al * u;
         U.eig_partial[u] = nullptr; U.eig_npartial[u] = 0;
+        c->units_sc[u] = U.sc[u];
         pyr_two_level(U.A[u], U.lap_ref[u], pyr_a + pyr_off[u], U.H[u], U.W[u]);
         pyr_two_level(U.B[u], U.lap_mon[u], pyr_b + pyr_off[u], U.H[u], U.W[u]);
     }
@@ -334,6 +336,14 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     {
         km_stage_timer t(c, ST_LAPLACIAN);
         if ((rc = kd_stretch_laplacian_units(c, U, prm->ksize_ref, prm->ksize_mon, prm->invert_mon, nodata_ref, nodata_mon, &vjob))) return rc;
+    }
+    // The eigenvalue pass of THIS submission reads the Laplacian pass's per-item counts (k_eig3.hip: item classes).  Stream order: E of
+    // submission n is enqueued on the main stream behind n.L, which wrote them, and the table lies in this lane's WS_LAP_VALID - the
+    // next submission's Laplacian pass, which may run before n.E, writes the OTHER lane's; the lane's own next one (n + 2) follows n.E on
+    // the main stream.  The sums on the second stream only read it.
+    if (c->opt_eig3_valid_items) {
+        for (int u = 0; u < n; u++) { U.lap_counts[u] = vjob.item_counts[u]; U.lap_nstrips[u] = vjob.item_nstrips[u]; }
+        U.lap_rows = vjob.item_rows; U.lap_strip_w = vjob.item_strip_w;
     }
     // ---- the valid-pixel sums and the pyramids (they depend on the Laplacians only) on the second stream
     {

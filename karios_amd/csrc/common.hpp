@@ -240,6 +240,8 @@ struct km_scalars {
     unsigned int pad1;
     unsigned long long skip_total; // development build, "eig3_count": (wavefront, row, pixel slot) triples of the fused 8-px eigenvalue pass ...
     unsigned long long skip_hit;   //   ... of which every lane satisfies min(S_xx, S_yy) scale^2 <= the running lower bound of the threshold
+    unsigned int eig3_items[4];    // k_eig3.hip, "eig3_valid_items": strip items by class - [0] no valid pixel (skipped), [1] all valid (interior trips
+                                   // without the mask), [2] general (the mask is read); [3] unused.  km_eig3_item_classes
 };
 #define KM_FLAG_SHARD_OVERFLOW 1u   // a key-buffer shard overflowed
 #define KM_FLAG_STAGE_OVERFLOW 2u   // the fused kernel's per-wave key stage overflowed (plateau image)
@@ -397,6 +399,9 @@ struct km_ctx {
     km_klt_stats stats;
     int phase_path = 0;            // last km_phase_shift*: 1 = float32 hand-written FFT, 2 = double precision (k_fft64.hip)
     double phase_margin = 0.0;     // (max - second largest) / max of |cc| seen by the float32 path
+    bool opt_eig3_valid_items = true;   // "eig3_valid_items" 1 (default): the fused 8-px eigenvalue pass classifies its items by the Laplacian pass's valid-pixel counts (0: every item reads the mask)
+    km_scalars *units_sc[KM_UNITS_MAX] = {};   // scalar blocks of the last batched submission's units (km_eig3_item_classes) ...
+    int units_sc_n = 0;                 //   ... and their number
     bool opt_eig3_count = false;   // (KM_DEV) "eig3_count": the fused 8-px eigenvalue pass counts the (wave, row, pixel slot) triples a bound could skip
     bool opt_prep_plain = false;   // (KM_DEV) "prep_hist_plain": the radix select adds one LDS atomic per pixel instead of one per run of equal bins (A/B of DESIGN 12)
     bool opt_defer_valid = true;   // "defer_valid" 0: the sum stays behind the Laplacian pass on the main stream
@@ -696,6 +701,12 @@ struct km_units {
     size_t capk = 0;                             // ... the same capacity for every unit (sized for the largest)
     const unsigned *eig_partial[KM_UNITS_MAX];   // per-wave maxima the fused eigenvalue pass leaves for the ranking's first launch
     unsigned eig_npartial[KM_UNITS_MAX];
+    // valid-pixel counts of the unit's Laplacian items (lap_items.hpp), written by the Laplacian pass of the SAME submission on the same
+    // stream and in the same lane's workspace: the fused eigenvalue pass classifies its items by them.  nullptr (the default): no such
+    // table - a user mask, a single tile - and every item reads the mask
+    const unsigned *lap_counts[KM_UNITS_MAX] = {};
+    int lap_nstrips[KM_UNITS_MAX] = {};
+    int lap_rows = 0, lap_strip_w = 0;
     km_pyr A[KM_UNITS_MAX], B[KM_UNITS_MAX];     // pyramids (ref, mon Laplacians)
     float *p0[KM_UNITS_MAX], *p1[KM_UNITS_MAX], *p0r[KM_UNITS_MAX];
     char *frame[KM_UNITS_MAX];                   // frame block (header | 6 cap float32 | score columns)
@@ -712,6 +723,11 @@ struct km_valid_units {
     const unsigned *partial[KM_UNITS_MAX];
     unsigned n_partial[KM_UNITS_MAX];
     unsigned long long *out[KM_UNITS_MAX];
+    // the automatic mask's counts item by item (lap_items.hpp: grid of item_rows x item_strip_w, item_nstrips[u] strips); nullptr where
+    // the counts are not per Laplacian item (user masks: mask_pack_units_kernel's workgroups)
+    const unsigned *item_counts[KM_UNITS_MAX] = {};
+    int item_nstrips[KM_UNITS_MAX] = {};
+    int item_rows = 0, item_strip_w = 0;
 };
 // batched launchers (KM_E_UNSUPPORTED without a message: the batch form does not cover the case - the caller submits the units one by one)
 int kd_minmax_units(km_ctx *c, const km_units &U, double *const *d_out, int ws_slot);

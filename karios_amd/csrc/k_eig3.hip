@@ -25,10 +25,19 @@
 //   * 24 of 512 columns are halo, and an item is ~120 rows tall (2-3 waves per SIMD hide the latencies: eight independent
 //     pixels per lane give the scheduler what four more resident waves gave the 2-px kernel).
 // The strips that touch the left / right image border (12 columns each) run eig2_item inside the same launch.
+//
+// Item classes ("eig3_valid_items").  In a batched submission the Laplacian pass has counted the valid pixels of each of ITS items
+// (lap_items.hpp) before this kernel starts.  A wave reads the counts of the Laplacian items that overlap its mask rectangle once:
+//   none valid: no pixel of the rectangle can count for the maximum or be a candidate - the item writes a zero maximum and returns;
+//   all valid:  every mask byte the item would read is non-zero - its interior trips run a form without the mask load, without the
+//               masked copy of the lambda row and with the column range as two constant wave masks (one per 4-pixel group);
+//   otherwise (and without a table: user masks, single tiles): the mask is read row by row.
+// The classes change no value: best, thr_run, the keys, tie_rows and the flush points are what the general form computes.
 #include <cstring>
 #include <string.h>
 
 #include "eig2_item.hpp"
+#include "lap_items.hpp"
 
 namespace {
 
@@ -82,7 +91,11 @@ template <class F, int... I> __device__ __forceinline__ void e3_for_impl(F &&f, 
 }
 template <int N, class F> __device__ __forceinline__ void e3_for(F &&f) { e3_for_impl(f, std::make_integer_sequence<int, N>{}); }   // f(0_c) .. f((N-1)_c)
 
-template <int BLOCK>
+// ALLV (wave-uniform, decided by the caller): every mask byte of rows ye0 .. ye1 x columns col_lo .. col_hi - 1 is non-zero, and
+// col_lo - xs, col_hi - xs are multiples of 4 - the interior trips run without the mask.  Two instantiations, not a run-time flag
+// inside one: with both interior loops in one body the compiler's wait-count bookkeeping merged their load queues and the general
+// loop waited for its rows sooner (vmcnt 3 - 4 where it stands at 5 - 8), 7 % on the kernel.
+template <int BLOCK, bool ALLV>
 __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const uint8_t *__restrict__ mask, int H, int W, double scale2,
                                           unsigned *__restrict__ max_partial, double quality, km_scalars *sc, unsigned long long *__restrict__ keys,
                                           size_t cap, unsigned stage_cap, int wave_id, int xs, int col_lo, int col_hi, int ye0, int ye1,
@@ -99,6 +112,9 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
 #pragma unroll
     for (int p = 0; p < 8; p++)
         if (c0 + p >= col_lo && c0 + p < col_hi) colmask[p >> 2] |= 0xffu << (8 * (p & 3));
+    // ... per 4-pixel group (lane constants: two wave masks), for the interior trips of an all-valid item, whose column range starts
+    // and ends on a group: pixels 0..3 of a lane are inside or outside together, and so are pixels 4..7
+    const bool colv[2] = {colmask[0] != 0u, colmask[1] != 0u};
     const uint8_t *mptr = mask ? mask : src;         // no mask: the loads still happen (fixed set of memory operations per row)
     const uint32_t mask_or = mask ? 0u : 0x01010101u;
 
@@ -218,6 +234,10 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
     };
 
     float best = -INFINITY;
+    // all-valid trips: the maxima of pixels 0..3 and 4..7 of every lambda row, column range not yet applied (it is constant over each
+    // group: fold_best) - two v_max per pixel group row instead of a select and a max per pixel
+    float best_lo = -INFINITY, best_hi = -INFINITY;
+    auto fold_best = [&]() { best = fmaxf(best, fmaxf(colv[0] ? best_lo : -INFINITY, colv[1] ? best_hi : -INFINITY)); };
     unsigned tie_rows = 0u;                           // (wave-uniform: a scalar register)
 #ifdef KM_DEV
     unsigned skip_total = 0u, skip_hit = 0u;          // "eig3_count" (VERDICT r4 item 5): how often could the eigenvalue formula be skipped?
@@ -264,8 +284,11 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
 
     // the part of a marching step behind the windows: product row m is accumulated, lambda row y = m - Rr completed,
     // candidate row y - 1 tested.  PH = step % 3; TRAIL / OUT / CAND: warm-up steps do less
-    auto compute = [&](auto ph_tag, int m, uint2 mkraw, bool trail, bool out, bool cand) {
+    // NOMASK (an interior trip of an all-valid item): row y-1 is read from E, the column range is ANDed into the tests as two wave masks, and
+    // row y goes into best_lo / best_hi; EM and mkraw are not touched
+    auto compute = [&](auto ph_tag, auto nomask_tag, int m, uint2 mkraw, bool trail, bool out, bool cand) {
         constexpr int PH = decltype(ph_tag)::value;
+        constexpr bool NOMASK = decltype(nomask_tag)::value;
         constexpr int S0 = PH, S1 = (PH + 1) % 3, S2 = (PH + 2) % 3;   // window rows: oldest, middle, newest
         uint32_t dx[8], dy[8];
         derivs(PW[S0], PW[S1], PW[S2], dx, dy);
@@ -301,10 +324,17 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
 #pragma unroll
             for (int p = 0; p < 8; p++) m3[p] = fmaxf(fmaxf(E[P2][p], E[P1][p]), E[C][p]);
             const float m3l = __int_as_float(e2_lane_m1(__float_as_int(m3[7]))), m3r = __int_as_float(e2_lane_p1(__float_as_int(m3[0])));
+            auto cv = [&](int p) -> float {              // row y-1 as the test and the keys read it
+                if constexpr (NOMASK) return E[P1][p];
+                else return EM[p];
+            };
             auto is_cand = [&](int p) {
                 const float left = p == 0 ? m3l : m3[(p + 7) & 7], right = p == 7 ? m3r : m3[(p + 1) & 7];
                 const float nb = fmaxf(fmaxf(left, right), m3[p]);
-                return EM[p] > thr_run && EM[p] >= nb;   // (thr_run >= +0 - qualityLevel > 0 is checked on entry - so OpenCV's `val != 0` is implied)
+                const bool is = cv(p) > thr_run && cv(p) >= nb;   // (thr_run >= +0 - qualityLevel > 0 is checked on entry - so OpenCV's `val != 0` is implied)
+                // (`&`, not `&&`: a short-circuit on the lane constant became a branch on EXEC per pixel)
+                if constexpr (NOMASK) return (bool)((int)is & (int)colv[p >> 2]);
+                else return is;
             };
             float selval = 0.f;
             unsigned selp = 0u, ncand = 0u;
@@ -312,7 +342,7 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
 #pragma unroll
             for (int p = 0; p < 8; p++) {
                 const bool is = isv[p] = is_cand(p);
-                selval = is ? EM[p] : selval;
+                selval = is ? cv(p) : selval;
                 selp = is ? (unsigned)p : selp;
                 ncand += is ? 1u : 0u;
             }
@@ -332,7 +362,7 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
                 unsigned fp = selp;
 #pragma unroll
                 for (int p = 6; p >= 0; p--) {
-                    fval = isv[p] ? EM[p] : fval;
+                    fval = isv[p] ? cv(p) : fval;
                     fp = isv[p] ? (unsigned)p : fp;
                 }
                 append(__ballot(ncand != 0u), ncand != 0u, selval, selp);
@@ -346,10 +376,15 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
                     const unsigned long long bal = __ballot(is);
                     const unsigned slot = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
                     st[min(is ? slot : ~0u, EIG3_STAGE + (unsigned)lane)] =
-                        ((unsigned long long)__float_as_uint(EM[p]) << 32) | (unsigned long long)(rowidx + (unsigned)p);
+                        ((unsigned long long)__float_as_uint(cv(p)) << 32) | (unsigned long long)(rowidx + (unsigned)p);
                     cnt += (unsigned)__popcll(bal);
                 }
             }
+        }
+        if constexpr (NOMASK) {
+#pragma unroll
+            for (int p = 0; p < 4; p++) { best_lo = fmaxf(best_lo, E[C][p]); best_hi = fmaxf(best_hi, E[C][p + 4]); }
+            return;
         }
         // row y: masked copy (the next step's candidates) and the running maximum
         const uint32_t mk[2] = {(mkraw.x | mask_or) & colmask[0], (mkraw.y | mask_or) & colmask[1]};
@@ -383,7 +418,7 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
         entering3(m, trail, ph_tag);
         const bool out = step >= BLOCK - 1;
         const uint2 mkraw = load8(mptr, clamp_row(m - Rr));
-        compute(ph_tag, m, mkraw, trail, out, out && (m - Rr) >= ye0 + 2);
+        compute(ph_tag, std::false_type{}, m, mkraw, trail, out, out && (m - Rr) >= ye0 + 2);
     };
     int m = m_first;
     auto general_until = [&](int m_end, bool align3) {
@@ -421,26 +456,38 @@ __device__ __forceinline__ void eig3_item(const uint8_t *__restrict__ src, const
                 constexpr int K = decltype(kt)::value;
                 const int step = m + K - m_first;
                 PW[(K + 2) % 3] = pack(ql[K], qt[K]);
-                compute(kt, m + K, qm[K], step >= BLOCK, step >= BLOCK - 1, step >= BLOCK - 1 && m + K - Rr >= ye0 + 2);
+                compute(kt, std::false_type{}, m + K, qm[K], step >= BLOCK, step >= BLOCK - 1, step >= BLOCK - 1 && m + K - Rr >= ye0 + 2);
                 ql[K] = load8(src, m + K + 3 + 1);
                 qt[K] = load8(src, max(m + K + 3 - BLOCK + 1, 0));
                 qm[K] = load8(mptr, max(m + K + 3 - Rr, 0));
             });
             m += 3;
         }
+        // the steady trips.  ALLV: the same trips without the mask - the warm-up left the lambda rows in E (the first trip reads row y-1
+        // there, not in EM), and the general steps behind the last trip find in EM what they would have found: E's newest row (phase 2)
+        // within the columns
+        const bool steady = m + 2 <= mi_hi;
         while (m + 2 <= mi_hi) {
             flush_if(EIG3_FLUSH_AT);
+            if constexpr (ALLV) fold_best();
             refresh_threshold(false);
             const int seg_end = min(mi_hi, m + EIG3_SEG * 3 - 1);
             for (; m + 2 <= seg_end; m += 3) {
                 e3_for<3>([&](auto kt) {
                     constexpr int K = decltype(kt)::value;
                     PW[(K + 2) % 3] = pack(ql[K], qt[K]);
-                    compute(kt, m + K, qm[K], true, true, true);
+                    compute(kt, std::integral_constant<bool, ALLV>{}, m + K, qm[K], true, true, true);
                     ql[K] = load8(src, m + K + 3 + 1);
                     qt[K] = load8(src, m + K + 3 - BLOCK + 1);
-                    qm[K] = load8(mptr, m + K + 3 - Rr);
+                    if constexpr (!ALLV) qm[K] = load8(mptr, m + K + 3 - Rr);
                 });
+            }
+        }
+        if constexpr (ALLV) {
+            if (steady) {
+                fold_best();
+#pragma unroll
+                for (int p = 0; p < 8; p++) EM[p] = colv[p >> 2] ? E[2][p] : -INFINITY;
             }
         }
     }
@@ -468,7 +515,12 @@ struct e3_units_args {
     int item0[KM_UNITS_MAX + 1];
     int n, rows2, rows3;
     int count_skips;      // (KM_DEV) "eig3_count"
+    // "eig3_valid_items": the Laplacian pass's valid-pixel counts per item (lap_items.hpp), nullptr: none - every item reads the mask
+    const unsigned *lap_counts[KM_UNITS_MAX];
+    int lap_nstrips[KM_UNITS_MAX];
+    int lap_rows, lap_strip_w;
 };
+enum { E3_NONE_VALID = 0, E3_ALL_VALID = 1, E3_GENERAL = 2 };
 template <int BLOCK>
 __global__ __launch_bounds__(256, 3) void eig3_units_kernel(e3_units_args U, double scale2, double quality, size_t cap, unsigned stage_cap2, unsigned stage_cap3)
 {
@@ -501,8 +553,36 @@ __global__ __launch_bounds__(256, 3) void eig3_units_kernel(e3_units_args U, dou
     const int xs = min(strip * EIG3_STRIDE, W - 512);
     const int col_lo = EIG3_MARGIN + strip * EIG3_STRIDE, col_hi = min(col_lo + EIG3_STRIDE, W - EIG3_MARGIN);
     const int ye0 = rowblock * U.rows3, ye1 = min(H - 1, ye0 + U.rows3 + 1);
-    eig3_item<BLOCK>(src, mask, H, W, scale2, max_partial, quality, sc, keys, cap, stage_cap3, wave_id, xs, col_lo, col_hi, ye0, ye1, stage[wv],
-                     U.count_skips);
+    // ---- the item's class: the mask bytes it reads are rows ye0 .. ye1 x columns col_lo .. col_hi - 1; the Laplacian items that overlap
+    // that rectangle (they overhang it: the classes are conservative) have counted their valid pixels.  Scalar loads, a dozen at most
+    int cls = E3_GENERAL;
+    if (const unsigned *counts = U.lap_counts[u]) {
+        const lap_item_grid G = {H, W, U.lap_rows, U.lap_strip_w, U.lap_nstrips[u]};
+        const lap_item_range R = lapi_items_of_rect(G, ye0, ye1, col_lo, col_hi);
+        bool none = true, all = true;
+        for (int rb = R.rb0; rb <= R.rb1; rb++)
+            for (int s = R.s0; s <= R.s1; s++) {
+                const unsigned n_valid = counts[lapi_index(G, s, rb)];
+                none = none && n_valid == 0u;
+                all = all && n_valid == lapi_area(G, s, rb);
+            }
+        // (the mask-free trips keep the running maximum per 4-pixel group of a lane: the column range must start and end on a group -
+        //  every strip that is not clamped to the right edge: col_lo - xs = 12, col_hi - xs = 500 or the image's last group)
+        const bool groups = ((col_lo - xs) & 3) == 0 && ((col_hi - xs) & 3) == 0;
+        cls = none ? E3_NONE_VALID : (all && groups && !U.count_skips) ? E3_ALL_VALID : E3_GENERAL;
+    }
+    if (cls == E3_NONE_VALID) {      // the masked lambda rows would be -inf everywhere: no candidate, no maximum
+        if ((threadIdx.x & 63) == 0) { max_partial[wave_id] = 0u; atomicAdd(&sc->eig3_items[cls], 1u); }
+        return;
+    }
+    if (cls == E3_ALL_VALID)
+        eig3_item<BLOCK, true>(src, mask, H, W, scale2, max_partial, quality, sc, keys, cap, stage_cap3, wave_id, xs, col_lo, col_hi, ye0, ye1, stage[wv], 0);
+    else
+        eig3_item<BLOCK, false>(src, mask, H, W, scale2, max_partial, quality, sc, keys, cap, stage_cap3, wave_id, xs, col_lo, col_hi, ye0, ye1,
+                                stage[wv], U.count_skips);
+    // (diagnostics: km_eig3_item_classes.  At the item's END, like tie_rows: a round of items starts at the same moment, its rows are loaded
+    //  behind whatever memory operation the wave issued before, and three thousand atomics on one address take 20 us to go through)
+    if ((threadIdx.x & 63) == 0) atomicAdd(&sc->eig3_items[cls], 1u);
 }
 
 // single: one tile (k3_eig_candidates) - its own row rule, below
@@ -511,9 +591,11 @@ int launch_eig3_units(km_ctx *c, km_units &U, double scale2, double quality, boo
 {
     e3_units_args A;
     A.n = U.n; A.rows2 = 64;
+    A.lap_rows = U.lap_rows; A.lap_strip_w = U.lap_strip_w;
     long border_total = 0;
     for (int u = 0; u < U.n; u++) {
         A.src[u] = U.lap_ref[u]; A.mask[u] = U.mask[u]; A.sc[u] = U.sc[u]; A.keys[u] = U.keys[u];
+        A.lap_counts[u] = U.lap_counts[u]; A.lap_nstrips[u] = U.lap_nstrips[u];
         A.H[u] = U.H[u]; A.W[u] = U.W[u];
         A.nstrips[u] = (U.W[u] - 2 * EIG3_MARGIN + EIG3_STRIDE - 1) / EIG3_STRIDE;
         A.n_border[u] = 2 * ((U.H[u] - 2 + A.rows2 - 1) / A.rows2);

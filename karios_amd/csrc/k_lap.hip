@@ -5,6 +5,7 @@
 // a single tile or pair runs as a batch of one unit.
 #include "k_pixel.hpp"
 #include "lap_coef.hpp"
+#include "lap_items.hpp"
 
 #include <algorithm>
 
@@ -400,7 +401,7 @@ template <class F, int... I> __device__ __forceinline__ void lapm_for_impl(F &&f
 }
 template <int N, class F> __device__ __forceinline__ void lapm_for(F &&f) { lapm_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
-#define LAPM_VALID_OF(R) ((R) == 5 ? 240 : 248)      // output columns of a strip: 64 lanes x 4 columns less the halo lanes (two either side for radius 5)
+// (LAPM_VALID_OF(R), the output columns of a strip, and the pixels an item counts: lap_items.hpp)
 #ifndef LAPM_PF
 #define LAPM_PF 3      // source rows in flight per wave (interior trips: really so; 2, 3 and 4 measure the same - profiles/lap_march_rows_kernel_stats.md)
 #endif
@@ -432,9 +433,11 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
     // 1 strip in 23 of a 5490-column unit, and + 22 % on the launch).  That strip is SHIFTED left instead so that its lane 63 starts
     // exactly at column W: it recomputes - and rewrites, byte for byte the same - columns of its left neighbour and counts valid
     // pixels only from `cnt_from` on.
-    const bool shifted = (W % 4 != 0) && strip == nstrips - 1 && W >= 256;      // (its lane 0 at column W - 252 lies inside the image)
+    // (which strip, and which pixels an item counts: lap_items.hpp - the fused eigenvalue pass reads valid_partial[] by the same rule)
+    const lap_item_grid grid = {H, W, rows_per_item, VALID, nstrips};
+    const bool shifted = lapi_shifted(W, strip, nstrips);                       // (its lane 0 at column W - 252 lies inside the image)
     const int gx0 = (shifted ? W - (256 - HALO) : strip * VALID - HALO) + 4 * lane;           // first of this lane's 4 columns
-    const int cnt_from = shifted ? (nstrips - 1) * VALID : 0;
+    const int cnt_from = lapi_count_from(grid, strip);
     const uint32_t cnt_mask = gx0 >= cnt_from ? 0xffffffffu : gx0 + 4 <= cnt_from ? 0u : (0xffffffffu << (8 * (cnt_from - gx0)));
     const unsigned ugx = (unsigned)gx0;                           // used by output lanes only (gx0 >= 0 there)
     // FAST path (W % 4 == 0, aligned rows): a lane left of the image or right of it loads the 4 columns of its
@@ -455,7 +458,7 @@ __device__ __forceinline__ void lap_march_item(const T *__restrict__ img0, const
 #pragma unroll
     for (int k = 0; k < 4; k++) rc[k] = km_reflect101(gx0 + k, W);
     const bool out_lane = lane >= HALO / 4 && lane <= 63 - HALO / 4 && gx0 < W;
-    const int y0 = rowblock * rows_per_item, y1 = min(H, y0 + rows_per_item);
+    const int y0 = lapi_row0(grid, rowblock), y1 = lapi_row1(grid, rowblock);
 
     // packed coefficients
     // (R = 4: nine taps = three dwords; the smoothing sum stays SIGNED there - sum ks (u - 128) spans [-32768, 32512], exactly an int16 -
@@ -884,7 +887,7 @@ static int launch_lap_march(km_ctx *c, int R, const T *a, const T *b, int H, int
     A.n = 1;
     A.img0[0] = a; A.img1[0] = b; A.s0[0] = sa; A.s1[0] = sb; A.mm[0] = mm;
     A.out0[0] = oa; A.out1[0] = ob; A.mask[0] = mask; A.valid[0] = nullptr;
-    A.H[0] = H; A.W[0] = W; A.nstrips[0] = (W + LAPM_VALID_OF(R) - 1) / LAPM_VALID_OF(R);
+    A.H[0] = H; A.W[0] = W; A.nstrips[0] = lapi_nstrips(W, LAPM_VALID_OF(R));
     const void *fn = lapm_kernel<T, MASK>(R);
     lapm_items(c, R, fn, A);                          // (the occupancy of the instantiation that runs)
     const unsigned nitems = (unsigned)A.item0[1];
@@ -986,7 +989,7 @@ static int launch_lap_march_units(km_ctx *c, int R, const km_units &U, const lap
     for (int u = 0; u < U.n; u++) {
         A.img0[u] = U.ref[u]; A.img1[u] = U.mon[u]; A.s0[u] = U.sref[u]; A.s1[u] = U.smon[u]; A.mm[u] = U.mm[u];
         A.out0[u] = U.lap_ref[u]; A.out1[u] = U.lap_mon[u]; A.mask[u] = U.mask[u];
-        A.H[u] = U.H[u]; A.W[u] = U.W[u]; A.nstrips[u] = (U.W[u] + LAPM_VALID_OF(R) - 1) / LAPM_VALID_OF(R);
+        A.H[u] = U.H[u]; A.W[u] = U.W[u]; A.nstrips[u] = lapi_nstrips(U.W[u], LAPM_VALID_OF(R));
     }
     lapm_items(c, R, lapm_kernel<T, true>(R), A);     // (the rows choice follows the MASK = true instantiation, with a user mask too)
     const int total = A.item0[U.n];
@@ -1011,7 +1014,10 @@ static int launch_lap_march_units(km_ctx *c, int R, const km_units &U, const lap
     for (int u = 0; u < U.n; u++) {
         A.valid[u] = valid + A.item0[u];
         job->partial[u] = A.valid[u]; job->n_partial[u] = (unsigned)(A.item0[u + 1] - A.item0[u]); job->out[u] = &U.sc[u]->valid;
+        // the counts item by item, for the eigenvalue pass of the same submission (lap_items.hpp says which pixels an entry counts)
+        job->item_counts[u] = A.valid[u]; job->item_nstrips[u] = A.nstrips[u];
     }
+    job->item_rows = A.rows; job->item_strip_w = LAPM_VALID_OF(R);
     return lapm_launch(c, lapm_kernel<T, true>(R), A, cf, invert1, nd);
 }
 
