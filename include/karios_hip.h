@@ -306,6 +306,31 @@ int km_pyrdown_u8(km_ctx *ctx, const uint8_t *src, int H, int W, uint8_t *dst);
 int km_pyrlk(km_ctx *ctx, const uint8_t *prev, const uint8_t *next, int H, int W,
              const float *pts, int n, int win_size, int max_level, int max_count,
              double epsilon, float *out_pts);
+/* ---- a geometric prior (no counterpart in the reference's call graph: it resamples the monitored raster instead;
+ * tests/lk_prior_restatement.py is the definition).  A prior is 9 float64 values P, row-major, that map
+ * reference pixel coordinates to monitored pixel coordinates: w = (P[6] x + P[7] y) + P[8], qx = ((P[0] x + P[1] y) + P[2]) / w,
+ * qy likewise, every float64 operation rounded on its own; the guess of a key point is ((float)qx, (float)qy); a position with w not
+ * finite or <= 0 has no guess.  For a box at (x_off, y_off) the map is applied to (x + x_off, y + y_off) and the offsets are
+ * subtracted from q.  A shift (sx, sy) is {1,0,sx, 0,1,sy, 0,0,1}.
+ *
+ * km_pyrlk_initial: cv2.calcOpticalFlowPyrLK(prev, next, pts, guess, ..., flags=OPTFLOW_USE_INITIAL_FLOW): km_pyrlk, but the search
+ * of point k starts at guess[k] (at guess[k] * 2^-maxLevel on the top level) where km_pyrlk starts it at pts[k]; out_pts are positions
+ * in `next`.  KM_E_ARG as km_pyrlk, and for a point or guess that is not finite; KM_E_UNSUPPORTED, nothing queued: max_level != 1,
+ * win_size > 40, an image without a pyramid level 1 ((W + 1) / 2 <= win_size or (H + 1) / 2 <= win_size), "lk2" 0 - the seeded tracker
+ * is the second LK form. */
+int km_pyrlk_initial(km_ctx *ctx, const uint8_t *prev, const uint8_t *next, int H, int W, const float *pts, const float *guess, int n,
+                     int win_size, int max_level, int max_count, double epsilon, float *out_pts);
+/* The corner mask under a prior: mask[y][x] = base[y][x] && has_guess && 0 <= rx < W && 0 <= ry < H && valid_mon(mon[ry][rx]), with
+ * (rx, ry) = (qx, qy) rounded half to even.  base: a user mask (!= 0: valid; stride in bytes) or, NULL, the reference's half of the
+ * automatic mask (klt.py:268-273): ref != 0, finite, != *nodata_ref; valid_mon is the monitored half.  Without this rule a guess
+ * outside the monitored box stays where it is in both directions and scores a perfect track.  Strides in pixels; mask: H x W bytes,
+ * 1 / 0, dense.  The device form leaves its work queued on the context stream. */
+int km_prior_mask(km_ctx *ctx, const void *ref, const void *mon, int dtype, int H, int W, ptrdiff_t stride_ref, ptrdiff_t stride_mon,
+                  const uint8_t *base, ptrdiff_t stride_base, const double *nodata_ref, const double *nodata_mon, const double prior[9],
+                  double x_off, double y_off, uint8_t *mask);
+int km_prior_mask_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t stride_ref,
+                      ptrdiff_t stride_mon, const uint8_t *d_base, ptrdiff_t stride_base, const double *nodata_ref,
+                      const double *nodata_mon, const double prior[9], double x_off, double y_off, uint8_t *d_mask);
 /* klt_tracker body up to the forward-backward distance (klt.py:103-142):
  * GFTT on ref (unless p0 given) + LK ref->mon + LK mon->ref.
  * Outputs, each 2*cap floats: p0, p1, p0r; *out_n = Ninit (0 <=> "No features"). */
@@ -408,6 +433,19 @@ int km_klt_tile_frame_zncc_dev(km_ctx *ctx, const void *d_ref, const void *d_mon
                                const km_klt_params *prm, float x_off, float y_off, const void *d_ref_full, const void *d_mon_full,
                                int H_full, int W_full, ptrdiff_t stride_ref_full, ptrdiff_t stride_mon_full,
                                double zncc_threshold, void *host_out, int cap);
+/* km_klt_tile_frame_zncc_dev under a prior (above): corners are selected under km_prior_mask's mask (base = d_mask, or the reference's
+ * half of the automatic mask), the forward pass of a key point p0 starts at its guess g, the backward pass at p1 - (g - p0) (float32,
+ * in that order; it never reads p0), the rasters are neither shifted nor resampled.  dx, dy are total displacements, the block layout
+ * is the same and the ZNCC column is scored at round(x0 + dx) on the full rasters.  The identity prior gives the unseeded call's bits.
+ * KM_E_UNSUPPORTED, nothing queued: an image window is set (km_set_image_window), "frame_clip" is 1 (under a prior the clip belongs on
+ * the residuals dx - (gx - x0): karios_amd applies it behind the frame), the box has no pyramid level 1 at this winSize, maxLevel != 1,
+ * winSize > 40 or "lk2" 0.  KM_E_ARG: a prior value that is not finite. */
+int km_klt_tile_frame_prior_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int H, int W,
+                                ptrdiff_t stride_ref, ptrdiff_t stride_mon, const uint8_t *d_mask,
+                                ptrdiff_t stride_mask, const double *nodata_ref, const double *nodata_mon,
+                                const km_klt_params *prm, float x_off, float y_off, const void *d_ref_full, const void *d_mon_full,
+                                int H_full, int W_full, ptrdiff_t stride_ref_full, ptrdiff_t stride_mon_full,
+                                double zncc_threshold, const double prior[9], void *host_out, int cap);
 /* Stream-of-tiles form of the two calls above (a KLT.match loop over tiles, klt.py:220-234, or the per-band loop of
  * KariosAPI, core.py:845-871): km_klt_tile_frame_submit returns once the last kernel and the copy of the frame block
  * are ENQUEUED; the next submission then queues its dense stages right behind this frame's tail.  d_ref_full == NULL:

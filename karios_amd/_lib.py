@@ -177,6 +177,11 @@ SIGNATURES = {
     "km_good_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _d, _d, _i, _vp, _i, _pi]),
     "km_pyrdown_u8": (_i, [_vp, _vp, _i, _i, _vp]),
     "km_pyrlk": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _d, _vp]),
+    "km_pyrlk_initial": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _d, _vp]),
+    "km_prior_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _sz, _pd, _pd, _pd, _d, _d, _vp]),
+    "km_prior_mask_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _sz, _pd, _pd, _pd, _d, _d, _vp]),
+    "km_klt_tile_frame_prior_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _sz, _pd, _pd, C.POINTER(KltParams), C.c_float,
+                                         C.c_float, _vp, _vp, _i, _i, _sz, _sz, _d, _pd, _vp, _i]),
     "km_klt_track": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(KltParams), _vp, _i, _vp, _vp, _vp, _i, _pi]),
     "km_klt_tile": (_i, [_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _pd, _pd, C.POINTER(KltParams), _vp, _vp,
                          _vp, _i, _pi]),

@@ -52,6 +52,7 @@ struct km_call_modes {
     bool mm_early_allowed = false;   // in: the entry point reads no min / max statistics back (km_klt_tile_frame_submit)
     bool spec_used = false;          // out: the call went through the speculative corner path
     unsigned spec_flags = 0;         // out: sc->flags of that run, once read back (read_stats)
+    const kl_seed *seed = nullptr;   // in: the tracker starts every key point at its guess under this prior (km_klt_tile_frame_prior_dev)
 };
 // what every user of the synchronisation-free corner path (k_select2.hip) asks of the options and parameters; each adds what is its own
 static inline bool spec_path_covers(const km_ctx *c, const km_klt_params *prm)

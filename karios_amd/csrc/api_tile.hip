@@ -3,7 +3,9 @@
 // device call) and the asynchronous submission.  Batched units: api_units.hip; the kernel-size search: api_auto.hip; the frame block's
 // slots and its way out: api_frame.hip.
 #include "api_internal.hpp"
+#include "k_prior.hpp"
 
+#include <cmath>
 #include <cstring>
 
 // pyramid of one image into caller-provided storage (levels >= 1 packed from `store`); returns the bytes used
@@ -269,8 +271,9 @@ static int klt_track_dev(km_ctx *c, km_call_modes &m, km_valid_job vjob, const u
             // measured slower, CHANGELOG.md round 4)
             if ((rc = mark_lk_start(c))) return rc;
         }
-        if ((rc = kl_track(c, A, B, d_p0, &sc->n_corners, n_max, prm->win_size, prm->max_count, prm->epsilon, true, d_p1, d_p0r)))
-            return rc;
+        if (m.seed) rc = kl_track_seeded(c, A, B, d_p0, &sc->n_corners, n_max, prm->win_size, prm->max_count, prm->epsilon, true, d_p1, d_p0r, *m.seed);
+        else rc = kl_track(c, A, B, d_p0, &sc->n_corners, n_max, prm->win_size, prm->max_count, prm->epsilon, true, d_p1, d_p0r);
+        if (rc) return rc;
     }
     return KM_OK;
 }
@@ -534,10 +537,37 @@ static int tile_frame_scores(km_ctx *c, const km_frame_layout &L, char *d_out, c
     return KM_OK;
 }
 
+// a prior's 9 values: finite, or KM_E_ARG
+static int check_prior(km_ctx *c, const char *who, const double *prior)
+{
+    if (!prior) return km_fail(c, KM_E_ARG, "%s: null prior", who);
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(prior[i])) return km_fail(c, KM_E_ARG, "%s: prior[%d] is not finite", who, i);
+    return KM_OK;
+}
+
+// the two-level tracker serves an H x W box: its pyramid has a level 1 (build_pyramid_pair's rule) and the window fits the second form
+static bool prior_tracker_covers(const km_ctx *c, int H, int W, int win, int max_level)
+{
+    return c->opt_lk2 && max_level == 1 && win > 2 && win <= 40 && (W + 1) / 2 > win && (H + 1) / 2 > win;
+}
+
+static void fill_mask_args(kp_mask_args &a, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon, const uint8_t *d_base,
+                           ptrdiff_t sbase, const double *nodata_ref, const double *nodata_mon, const double *prior, double x_off, double y_off, uint8_t *d_mask)
+{
+    a.ref = d_ref; a.mon = d_mon; a.dtype = dtype; a.H = H; a.W = W; a.sref = sref; a.smon = smon; a.base = d_base; a.sbase = sbase;
+    a.has_nd_ref = nodata_ref != nullptr; a.nd_ref = nodata_ref ? *nodata_ref : 0.0;
+    a.has_nd_mon = nodata_mon != nullptr; a.nd_mon = nodata_mon ? *nodata_mon : 0.0;
+    memcpy(a.P, prior, sizeof a.P);
+    a.x_off = x_off; a.y_off = y_off; a.mask = d_mask;
+}
+
+// prior != nullptr (km_klt_tile_frame_prior_dev): the corner mask is the prior's (k_prior.hip, taken by the
+// pre-filter as a user mask) and the tracker starts every key point at its guess; everything else is the unseeded call's
 static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
                            const uint8_t *d_mask, ptrdiff_t smask, const double *nodata_ref, const double *nodata_mon, const km_klt_params *prm, float x_off,
                            float y_off, const void *d_ref_full, const void *d_mon_full, int Hf, int Wf, ptrdiff_t sref_f, ptrdiff_t smon_f,
-                           bool with_zncc, double zncc_threshold, void *host_out, int cap, km_frame_slot *slot = nullptr)
+                           bool with_zncc, double zncc_threshold, void *host_out, int cap, km_frame_slot *slot = nullptr, const double *prior = nullptr)
 {
     // slot != nullptr: km_klt_tile_frame_submit - the block goes to the slot's pinned buffer and the call returns without
     // waiting for the tail of the pipeline (LK, FB test, ZNCC, copy), which then overlaps the caller's next submission
@@ -549,6 +579,18 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
     if ((rc = check_dtype(c, "klt_tile_frame_dev", dtype)) || (rc = check_frame_width(c, "klt_tile_frame_dev", "tile", W))) return rc;
     if ((!host_out && !slot) || cap <= 0) return km_fail(c, KM_E_ARG, "klt_tile_frame_dev: null output");
     if ((rc = check_capacity(c, prm, cap))) return rc;
+    kl_seed seed;
+    if (prior) {
+        // what a prior does not serve is refused here, in front of the first launch
+        if ((rc = check_prior(c, "klt_tile_frame_prior_dev", prior))) return rc;
+        if (d_mask && smask < W) return km_fail(c, KM_E_ARG, "mask stride %td < width %d", smask, W);
+        if (c->window.H) return km_fail(c, KM_E_UNSUPPORTED, "klt_tile_frame_prior_dev: an image window is set (km_set_image_window)");
+        if (c->opt_frame_clip) return km_fail(c, KM_E_UNSUPPORTED, "klt_tile_frame_prior_dev: \"frame_clip\" is on (the clip under a prior runs on the residuals, behind the frame)");
+        if (!prior_tracker_covers(c, H, W, prm->win_size, prm->max_level))
+            return km_fail(c, KM_E_UNSUPPORTED, "klt_tile_frame_prior_dev: a prior needs the two-level tracker (box %d x %d, winSize %d, maxLevel %d)", W, H,
+                           prm->win_size, prm->max_level);
+        seed.guess = nullptr; memcpy(seed.P, prior, sizeof seed.P); seed.x_off = (double)x_off; seed.y_off = (double)y_off;
+    }
     const bool with_clip = c->opt_frame_clip;
     if (with_clip && !frame_clip_covers(cap)) return km_fail(c, KM_E_UNSUPPORTED, "klt_tile_frame_dev: the outlier clip holds at most 32768 rows (capacity %d)", cap);
     memset(&c->stats, 0, sizeof c->stats);
@@ -561,6 +603,14 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
     float *d_p0 = (float *)km_ws(c, WS_PTS0, pb), *d_p1 = (float *)km_ws(c, WS_PTS1, pb), *d_p0r = (float *)km_ws(c, WS_PTS2, pb);
     char *d_out = (char *)km_ws(c, WS_FRAME, ob);
     if (!sc || !d_p0 || !d_p1 || !d_p0r || !d_out) return KM_E_NOMEM;
+    if (prior) {
+        uint8_t *pmask = (uint8_t *)km_ws(c, WS_MASK, (size_t)H * W);
+        if (!pmask) return KM_E_NOMEM;
+        kp_mask_args a;
+        fill_mask_args(a, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prior, (double)x_off, (double)y_off, pmask);
+        if ((rc = kp_prior_mask(c, a))) return rc;
+        d_mask = pmask; smask = W;
+    }
     for (int attempt = 0;; attempt++) {
         KM_HIP(c, hipMemsetAsync(sc, 0, sizeof *sc, c->stream));
         // corners without a host synchronisation where the case allows it; header word 2 of the frame block carries the flags of
@@ -569,6 +619,7 @@ static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int 
         km_call_modes m;
         m.spec_allowed = attempt == 0;
         m.mm_early_allowed = slot != nullptr;     // (the synchronous forms report min / max in their statistics: scalar block)
+        m.seed = prior ? &seed : nullptr;
         if ((rc = klt_tile_dev_impl(c, m, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, d_p0, d_p1, d_p0r, cap, sc))) return rc;
         const int n_max = corner_limit(prm, cap);
         if ((rc = frame_block_free(c))) return rc;
@@ -619,6 +670,90 @@ int km_klt_tile_frame_zncc_dev(km_ctx *c, const void *d_ref, const void *d_mon, 
 {
     return tile_frame_impl(c, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, x_off, y_off, d_ref_full, d_mon_full,
                            Hf, Wf, sref_f, smon_f, true, zncc_threshold, host_out, cap);
+}
+
+int km_klt_tile_frame_prior_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
+                                const uint8_t *d_mask, ptrdiff_t smask, const double *nodata_ref, const double *nodata_mon,
+                                const km_klt_params *prm, float x_off, float y_off, const void *d_ref_full, const void *d_mon_full, int Hf,
+                                int Wf, ptrdiff_t sref_f, ptrdiff_t smon_f, double zncc_threshold, const double prior[9], void *host_out, int cap)
+{
+    if (!c) return km_fail(nullptr, KM_E_ARG, "null context");
+    if (!prior) return km_fail(c, KM_E_ARG, "klt_tile_frame_prior_dev: null prior");
+    return tile_frame_impl(c, d_ref, d_mon, dtype, H, W, sref, smon, d_mask, smask, nodata_ref, nodata_mon, prm, x_off, y_off, d_ref_full, d_mon_full,
+                           Hf, Wf, sref_f, smon_f, true, zncc_threshold, host_out, cap, nullptr, prior);
+}
+
+// rule 4 of DESIGN.md section 21 on device rasters; the mask stays on the device (dense rows), the work queued on the context stream
+int km_prior_mask_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon, const uint8_t *d_base,
+                      ptrdiff_t sbase, const double *nodata_ref, const double *nodata_mon, const double prior[9], double x_off, double y_off, uint8_t *d_mask)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_image(c, d_ref, H, W, sref, "prior_mask")) || (rc = check_image(c, d_mon, H, W, smon, "prior_mask")) ||
+        (rc = check_dtype(c, "prior_mask", dtype)) || (rc = check_prior(c, "prior_mask", prior)))
+        return rc;
+    if (!d_mask) return km_fail(c, KM_E_ARG, "prior_mask: null output");
+    if (d_base && sbase < W) return km_fail(c, KM_E_ARG, "prior_mask: mask stride %td < width %d", sbase, W);
+    if (!std::isfinite(x_off) || !std::isfinite(y_off)) return km_fail(c, KM_E_ARG, "prior_mask: the origin is not finite");
+    kp_mask_args a;
+    fill_mask_args(a, d_ref, d_mon, dtype, H, W, sref, smon, d_base, sbase, nodata_ref, nodata_mon, prior, x_off, y_off, d_mask);
+    return kp_prior_mask(c, a);
+}
+
+int km_prior_mask(km_ctx *c, const void *ref, const void *mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon, const uint8_t *base,
+                  ptrdiff_t sbase, const double *nodata_ref, const double *nodata_mon, const double prior[9], double x_off, double y_off, uint8_t *mask)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_image(c, ref, H, W, sref, "prior_mask")) || (rc = check_image(c, mon, H, W, smon, "prior_mask")) ||
+        (rc = check_dtype(c, "prior_mask", dtype)) || (rc = check_prior(c, "prior_mask", prior)))
+        return rc;
+    if (!mask) return km_fail(c, KM_E_ARG, "prior_mask: null output");
+    if (base && sbase < W) return km_fail(c, KM_E_ARG, "prior_mask: mask stride %td < width %d", sbase, W);
+    if (!std::isfinite(x_off) || !std::isfinite(y_off)) return km_fail(c, KM_E_ARG, "prior_mask: the origin is not finite");
+    const size_t es = km_dtype_size(dtype), n = (size_t)H * W;
+    void *d_ref, *d_mon, *d_base = nullptr;
+    if ((rc = upload_image(c, WS_RAW_A, ref, es, H, W, sref, &d_ref)) || (rc = upload_image(c, WS_RAW_B, mon, es, H, W, smon, &d_mon))) return rc;
+    if (base && (rc = upload_image(c, WS_MASK_IN, base, 1, H, W, sbase, &d_base))) return rc;
+    uint8_t *d_mask = (uint8_t *)km_ws(c, WS_MASK, n);
+    if (!d_mask) return KM_E_NOMEM;
+    kp_mask_args a;
+    fill_mask_args(a, d_ref, d_mon, dtype, H, W, W, W, (const uint8_t *)d_base, W, nodata_ref, nodata_mon, prior, x_off, y_off, d_mask);
+    if ((rc = kp_prior_mask(c, a))) return rc;
+    KM_D2H(c, mask, d_mask, n);
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+// cv2.calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW: one direction, every point from its own guess
+int km_pyrlk_initial(km_ctx *c, const uint8_t *prev, const uint8_t *next, int H, int W, const float *pts, const float *guess, int n, int win,
+                     int max_level, int max_count, double epsilon, float *out_pts)
+{
+    int rc;
+    if ((rc = begin_call(c)) || (rc = check_image(c, prev, H, W, W, "pyrlk_initial")) || (rc = check_image(c, next, H, W, W, "pyrlk_initial"))) return rc;
+    if (n < 0 || (n > 0 && (!pts || !guess || !out_pts))) return km_fail(c, KM_E_ARG, "pyrlk_initial: bad points");
+    if (win <= 2 || max_level < 0) return km_fail(c, KM_E_ARG, "pyrlk_initial: winSize %d / maxLevel %d", win, max_level);
+    for (int i = 0; i < 2 * n; i++)
+        if (!std::isfinite(pts[i]) || !std::isfinite(guess[i])) return km_fail(c, KM_E_ARG, "pyrlk_initial: point %d is not finite", i / 2);
+    if (max_level != 1 || win > 40) return km_fail(c, KM_E_UNSUPPORTED, "pyrlk_initial: winSize %d / maxLevel %d (the seeded tracker: maxLevel 1, winSize <= 40)", win, max_level);
+    if (!prior_tracker_covers(c, H, W, win, max_level))
+        return km_fail(c, KM_E_UNSUPPORTED, "pyrlk_initial: a %d x %d image has no pyramid level 1 at winSize %d (or \"lk2\" is off)", W, H, win);
+    if (n == 0) return KM_OK;
+    void *d_prev, *d_next;
+    if ((rc = upload_image(c, WS_U8_A, prev, 1, H, W, W, &d_prev)) || (rc = upload_image(c, WS_U8_B, next, 1, H, W, W, &d_next))) return rc;
+    float *d_in = (float *)km_ws(c, WS_PTS0, (size_t)n * 2 * sizeof(float));
+    float *d_out = (float *)km_ws(c, WS_PTS1, (size_t)n * 2 * sizeof(float));
+    float *d_guess = (float *)km_ws(c, WS_PTS2, (size_t)n * 2 * sizeof(float));
+    if (!d_in || !d_out || !d_guess) return KM_E_NOMEM;
+    { const int rch = h2d_now(c, d_in, pts, (size_t)n * 2 * sizeof(float)); if (rch) return rch; }
+    { const int rch = h2d_now(c, d_guess, guess, (size_t)n * 2 * sizeof(float)); if (rch) return rch; }
+    km_pyr A, B;
+    if ((rc = build_pyramid_pair(c, (const uint8_t *)d_prev, (const uint8_t *)d_next, H, W, win, max_level, &A, &B))) return rc;
+    kl_seed seed;
+    memset(&seed, 0, sizeof seed);
+    seed.guess = d_guess;
+    if ((rc = kl_track_seeded(c, A, B, d_in, nullptr, n, win, max_count, epsilon, false, d_out, nullptr, seed))) return rc;
+    KM_D2H(c, out_pts, d_out, (size_t)n * 2 * sizeof(float));
+    KM_FLUSH(c);
+    return KM_OK;
 }
 
 // Asynchronous form of km_klt_tile_frame[_zncc]_dev for a stream of tiles / band pairs: returns as soon as the last

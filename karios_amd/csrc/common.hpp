@@ -662,6 +662,19 @@ struct km_pyr {
 int kl_track(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_pts_in, const int *d_n,
              int n_max, int win, int max_count, double epsilon, bool backward_too, float *d_p1,
              float *d_p0r, int *d_left_band = nullptr);
+// the second form from a start position per key point (k_prior.hpp: kl_seed); KM_E_UNSUPPORTED where that form does not serve the pyramids.
+// A compiler that is not hipcc has no tracker: its stand-in of kl_track stands in for this launch as well
+struct kl_seed;
+#if defined(__HIPCC__)
+int kl_track_seeded(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_pts_in, const int *d_n, int n_max, int win, int max_count,
+                    double epsilon, bool backward_too, float *d_p1, float *d_p0r, const kl_seed &seed);
+#else
+static inline int kl_track_seeded(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_pts_in, const int *d_n, int n_max, int win, int max_count,
+                                  double epsilon, bool backward_too, float *d_p1, float *d_p0r, const kl_seed &)
+{
+    return kl_track(c, A, B, d_pts_in, d_n, n_max, win, max_count, epsilon, backward_too, d_p1, d_p0r);
+}
+#endif
 int kl_oscillation_probe(km_ctx *c, const float *d_q, int n, uint8_t *d_out);   // test hook of the LK kernels' oscillation predicate
 // independent forward + backward tracker runs in one launch (k_lk.hip kl_jobs_launch; the kernel-size search of klt.py:465-545)
 #define KM_LK_JOBS_MAX 64

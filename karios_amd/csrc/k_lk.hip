@@ -11,6 +11,7 @@
 // The backward pass starts from the forward result of the same keypoint, so both passes run
 // back to back in the same wavefront.
 #include "common.hpp"
+#include "k_prior.hpp"
 
 #ifndef KM_LK_WAVES
 #define KM_LK_WAVES 0   // occupancy target (waves per SIMD); 0 = leave it to the register allocator
@@ -507,7 +508,9 @@ __device__ __forceinline__ int lk_dot2_k(lk_s2 a, lk_s2 b, int k)
     return d;
 }
 
-template <int NR, int WIN, int MAXIT>
+// SEEDED (a geometric prior): outx / outy carry the START position in - the search begins there at the top level,
+// where the unseeded form begins at the key point (cv2's rule for OPTFLOW_USE_INITIAL_FLOW); everything else is the same text.
+template <int NR, int WIN, int MAXIT, bool SEEDED = false>
 __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, uint8_t *pJ, int (&oI)[2][2], int (&oJ)[2][2], float px, float py,
                                 const lk2_geo<WIN> &geo, int max_count, double epsilon, const int (&run_desc)[NR], float &outx, float &outy, int general_templates, int lk_reuse)
 {
@@ -527,7 +530,10 @@ __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, u
         const float sc = level ? 0.5f : 1.f;
         float prx = px * sc, pry = py * sc;
         float nx, ny;
-        if (level == 1) { nx = prx; ny = pry; }
+        if (level == 1) {
+            if constexpr (SEEDED) { nx = outx * sc; ny = outy * sc; }
+            else { nx = prx; ny = pry; }
+        }
         else { nx = resx * 2.f; ny = resy * 2.f; }
         resx = nx; resy = ny;
         prx -= half; pry -= half;
@@ -757,8 +763,72 @@ __device__ void lk2_track_point(const km_pyr &I, const km_pyr &J, uint8_t *pI, u
 
 __device__ __forceinline__ float lk_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 
+// The seeded form of lk2_body's second half (a geometric prior).  The guess of a key point is either given
+// (seed.guess) or the prior evaluated on the key point - wave-uniform doubles, prior_math.hpp; a key point without a guess starts at
+// itself, as the unseeded form does (the mask of k_prior.hip keeps such pixels from becoming corners).  The A patches are staged around
+// the key point's window, the B patches around the GUESS's window - the search's first position - and all four loads are in flight
+// together when all four lie inside.  A level whose template lies outside the first image is skipped by the tracker (nothing to stage in
+// either image); a guess window the iteration loop would leave at once (inx < -win or >= W, likewise y) stages nothing in B.  The backward
+// pass starts at p1 - (g - p0): it never reads p0 itself, and its search patch is the forward template's, re-centred if p1 moved away.
 template <int NR, int WIN, int MAXIT>
-__device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict__ order)
+__device__ __forceinline__ void lk2_seeded_tracks(const lk_args &g, const kl_seed &seed, int p, float px, float py, const lk2_geo<WIN> &geo,
+                                                  const int (&run_desc)[NR])
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
+    const int win = geo.win, PS = geo.ps(), PP = geo.pp(), PB = geo.bytes();
+    uint8_t *pA = smem_all, *pB = smem_all + 2 * PB;
+    const float half = (float)(win - 1) * 0.5f;
+    float gx = px, gy = py;
+    if (seed.guess) { gx = lk_uniform(seed.guess[2 * p]); gy = lk_uniform(seed.guess[2 * p + 1]); }
+    else {
+        float tx, ty;
+        if (pm::guess(seed.P, seed.x_off, seed.y_off, px, py, tx, ty)) { gx = lk_uniform(tx); gy = lk_uniform(ty); }
+    }
+    int oA[2][2], oB[2][2];
+    bool wantA[2], wantB[2], inside = true;
+#pragma unroll
+    for (int l = 0; l < 2; l++) {
+        const float sc = l ? 0.5f : 1.f;
+        const int ipx = (int)floorf(px * sc - half), ipy = (int)floorf(py * sc - half);
+        const int jpx = (int)floorf(gx * sc - half), jpy = (int)floorf(gy * sc - half);
+        wantA[l] = !(ipx < -win || ipx >= g.A.W[l] || ipy < -win || ipy >= g.A.H[l]);
+        wantB[l] = wantA[l] && !(jpx < -win || jpx >= g.B.W[l] || jpy < -win || jpy >= g.B.H[l]);
+        oA[l][0] = wantA[l] ? ipx - LK2_M : LK2_INVALID; oA[l][1] = wantA[l] ? ipy - LK2_M : LK2_INVALID;
+        oB[l][0] = wantB[l] ? jpx - LK2_M : LK2_INVALID; oB[l][1] = wantB[l] ? jpy - LK2_M : LK2_INVALID;
+        inside = inside && wantB[l] && lk_patch_inside(g.A.W[l], g.A.H[l], oA[l][0], oA[l][1], PS, PS, MAXIT) &&
+                 lk_patch_inside(g.B.W[l], g.B.H[l], oB[l][0], oB[l][1], PS, PS, MAXIT);
+    }
+    if (inside) {
+        lk_patch_regs<MAXIT> r0, r1, r2, r3;
+        stage_patch_issue<MAXIT>(g.A.img[1], g.A.W[1], oA[1][0], oA[1][1], PS, PS, r0);
+        stage_patch_issue<MAXIT>(g.B.img[1], g.B.W[1], oB[1][0], oB[1][1], PS, PS, r1);
+        stage_patch_issue<MAXIT>(g.A.img[0], g.A.W[0], oA[0][0], oA[0][1], PS, PS, r2);
+        stage_patch_issue<MAXIT>(g.B.img[0], g.B.W[0], oB[0][0], oB[0][1], PS, PS, r3);
+        stage_patch_commit<MAXIT>(PS, PS, pA + PB, PP, r0);
+        stage_patch_commit<MAXIT>(PS, PS, pB + PB, PP, r1);
+        stage_patch_commit<MAXIT>(PS, PS, pA, PP, r2);
+        stage_patch_commit<MAXIT>(PS, PS, pB, PP, r3);
+    } else {
+#pragma unroll 1
+        for (int l = 1; l >= 0; l--) {
+            if (wantA[l]) lk2_restage<MAXIT>(g.A.img[l], g.A.W[l], g.A.H[l], oA[l][0], oA[l][1], geo, pA + l * PB);
+            if (wantB[l]) lk2_restage<MAXIT>(g.B.img[l], g.B.W[l], g.B.H[l], oB[l][0], oB[l][1], geo, pB + l * PB);
+        }
+    }
+    LK_WAVE_SYNC();
+    float fx = gx, fy = gy;
+    lk2_track_point<NR, WIN, MAXIT, true>(g.A, g.B, pA, pB, oA, oB, px, py, geo, g.max_count, g.epsilon, run_desc, fx, fy, g.general_templates, g.lk_reuse);
+    if ((threadIdx.x & 63) == 0) { g.p1[2 * p] = fx; g.p1[2 * p + 1] = fy; }
+    if (g.backward) {
+        const float sx = gx - px, sy = gy - py;
+        float rx = fx - sx, ry = fy - sy;
+        lk2_track_point<NR, WIN, MAXIT, true>(g.B, g.A, pB, pA, oB, oA, fx, fy, geo, g.max_count, g.epsilon, run_desc, rx, ry, g.general_templates, g.lk_reuse);
+        if ((threadIdx.x & 63) == 0) { g.p0r[2 * p] = rx; g.p0r[2 * p + 1] = ry; }
+    }
+}
+
+template <int NR, int WIN, int MAXIT, bool SEEDED = false>
+__device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict__ order, const kl_seed *seed = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
     // (what a wave reads through a pointer that itself came from the unit table arrives in vector registers: the corner count and the key
@@ -784,6 +854,10 @@ __device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict
     // one neighbourhood per image and level, centred on the key point's window: all loads of the key point in flight together
     int oA[2][2], oB[2][2];
     bool want[2], inside = true;
+    if constexpr (SEEDED) {
+        lk2_seeded_tracks<NR, WIN, MAXIT>(g, *seed, p, px, py, geo, run_desc);
+        return;
+    }
 #pragma unroll
     for (int l = 0; l < 2; l++) {
         const float sc = l ? 0.5f : 1.f;
@@ -841,6 +915,18 @@ __global__ __launch_bounds__(64) KM_LK_OCC void lk2_kernel(lk_args g, const int 
 __global__ __launch_bounds__(64) LK2_25_OCC void lk2_kernel_win25(lk_args g, const int *__restrict__ order)
 {
     lk2_body<2, 25, 4>(g, order);
+}
+
+// the seeded instantiations (kl_track_seeded below): kernels of their own - the arguments, the registers and the code of the unseeded
+// kernels do not know of them
+template <int NR, int WIN, int MAXIT>
+__global__ __launch_bounds__(64) KM_LK_OCC void lk2_seeded_kernel(lk_args g, kl_seed seed)
+{
+    lk2_body<NR, WIN, MAXIT, true>(g, nullptr, &seed);
+}
+__global__ __launch_bounds__(64) LK2_25_OCC void lk2_seeded_kernel_win25(lk_args g, kl_seed seed)
+{
+    lk2_body<2, 25, 4, true>(g, nullptr, &seed);
 }
 
 
@@ -971,6 +1057,41 @@ int kl_track(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_pts_in,
     case 3: lk_kernel<3><<<nblk, 64 * LK_WPB, sm_all, c->stream>>>(g, (int)smw); break;
     case 4: lk_kernel<4><<<nblk, 64 * LK_WPB, sm_all, c->stream>>>(g, (int)smw); break;
     default: lk_kernel<5><<<nblk, 64 * LK_WPB, sm_all, c->stream>>>(g, (int)smw); break;
+    }
+    KM_LAUNCH_CHECK(c);
+    return KM_OK;
+}
+
+// The second form from a start position per key point.  KM_E_UNSUPPORTED, nothing queued: a pyramid without
+// level 1 or a row band (the first form serves those, and it stays unseeded), the second form switched off.
+int kl_track_seeded(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_pts_in, const int *d_n, int n_max, int win, int max_count,
+                    double epsilon, bool backward_too, float *d_p1, float *d_p0r, const kl_seed &seed)
+{
+    if (n_max <= 0) return KM_OK;
+    if (win <= 2) return km_fail(c, KM_E_ARG, "winSize %d must be > 2", win);
+    if (win > 40) return km_fail(c, KM_E_UNSUPPORTED, "winSize %d (supported 3..40)", win);
+    if (!(c->opt_lk2 && A.levels == 1 && B.levels == 1 && A.Hres[0] == 0 && B.Hres[0] == 0))
+        return km_fail(c, KM_E_UNSUPPORTED, "a prior needs the two-level tracker on whole images (pyramid levels %d / %d)", A.levels, B.levels);
+    lk_args g;
+    g.A = A; g.B = B; g.pts_in = d_pts_in; g.d_n = d_n; g.n_max = n_max; g.win = win;
+    g.max_count = max_count < 0 ? 0 : max_count > 100 ? 100 : max_count;
+    g.backward = backward_too ? 1 : 0;
+    g.general_templates = km_dev_env("KARIOS_HIP_LK_GENERAL") ? 1 : 0;
+    g.lk_reuse = c->opt_lk_reuse ? 1 : 0;
+    const double e = epsilon < 0 ? 0 : epsilon > 10 ? 10 : epsilon;
+    g.epsilon = e * e;
+    g.p1 = d_p1; g.p0r = d_p0r; g.left_band = nullptr;
+    const int runs = win * ((win + LK_RUN - 1) / LK_RUN), nr = (runs + 63) / 64;
+    const lk2_geo<0> geo(win);
+    const size_t sm2 = (size_t)4 * geo.bytes();
+    const unsigned nblk2 = km_xcd_grid((unsigned)n_max);
+    if (win == 25) lk2_seeded_kernel_win25<<<nblk2, 64, sm2, c->stream>>>(g, seed);
+    else switch (nr) {
+    case 1: lk2_seeded_kernel<1, 0, 3><<<nblk2, 64, sm2, c->stream>>>(g, seed); break;
+    case 2: lk2_seeded_kernel<2, 0, 4><<<nblk2, 64, sm2, c->stream>>>(g, seed); break;
+    case 3: lk2_seeded_kernel<3, 0, 6><<<nblk2, 64, sm2, c->stream>>>(g, seed); break;
+    case 4: lk2_seeded_kernel<4, 0, 8><<<nblk2, 64, sm2, c->stream>>>(g, seed); break;
+    default: lk2_seeded_kernel<5, 0, 9><<<nblk2, 64, sm2, c->stream>>>(g, seed); break;
     }
     KM_LAUNCH_CHECK(c);
     return KM_OK;

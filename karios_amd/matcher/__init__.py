@@ -5,3 +5,4 @@ from .mutual_info_service import MutualInfoService  # noqa: F401
 from .zncc_service import ZNCCService  # noqa: F401
 from .global_align import GlobalAlignment, refine_global_alignment, render_global_alignment  # noqa: F401
 from .sift import KeyPoint, KeyPoints, Sift  # noqa: F401
+from . import prior  # noqa: F401

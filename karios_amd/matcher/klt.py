@@ -30,11 +30,49 @@ LAPLACIAN_AUTO_CANDIDATES = list(tiling.AUTO_KSIZE_CANDIDATES)
 _DEVICE_DTYPES = (np.uint8, np.uint16, np.int16, np.float32)
 
 
-def klt_tracker(ref_data, image_data, mask, conf, p0=None, ctx=None) -> tuple[DataFrame, int] | None:
+def _tracks_under_prior(ref_data, image_data, mask, conf, p0, prior, ctx):
+    """`ops.klt_track` from the guesses of a prior: corners under the mask restricted to the pixels whose guess lies inside the image,
+    the forward pass from the guess g, the backward pass from p1 - (g - p0) - two seeded launches."""
+    from . import prior as _prior
+    ref_data, image_data = np.ascontiguousarray(ref_data, np.uint8), np.ascontiguousarray(image_data, np.uint8)
+    if p0 is None:
+        # these are Laplacians: a zero is a pixel like any other, so only the geometric half of the mask rule applies
+        ones = np.ones(ref_data.shape, np.uint8)
+        inside = ops.prior_mask(ones, ones, prior, mask=mask, ctx=ctx)
+        p0 = ops.good_features_to_track(ref_data, conf.maxCorners, conf.qualityLevel, conf.minDistance, mask=inside, blockSize=conf.blocksize, ctx=ctx)
+        if p0 is None:
+            return None
+    p0 = np.ascontiguousarray(p0, np.float32).reshape(-1, 2)
+    if not len(p0):
+        return None
+    gx, gy, _ = _prior.guesses(prior, p0[:, 0], p0[:, 1])
+    g = np.stack([gx, gy], axis=1)
+    win = (int(conf.matching_winsize),) * 2
+    p1 = ops.pyrlk_initial(ref_data, image_data, p0, g, winSize=win, ctx=ctx).reshape(-1, 2)
+    back = (p1 - (g - p0)).astype(np.float32)
+    p0r = ops.pyrlk_initial(image_data, ref_data, p1, back, winSize=win, ctx=ctx).reshape(-1, 2)
+    return p0.reshape(-1, 1, 2), p1.reshape(-1, 1, 2), p0r.reshape(-1, 1, 2)
+
+
+def klt_tracker(ref_data, image_data, mask, conf, p0=None, ctx=None, prior=None) -> tuple[DataFrame, int] | None:
     """Corners of `ref_data` (or the given `p0`), tracked into `image_data` and back; the tracks whose return trip ends
     within 0.1 px of their start are scored (reference klt.py:83-172; the LK status flags are ignored there too).
+    `prior` (`karios_amd.matcher.prior`): every corner is tracked from its guess; the frame then carries `dx_prior, dy_prior` and the
+    outlier clip runs on the residuals.
 
     Returns (frame[x0, y0, dx, dy, score] float32 in corner order, number of corners), or None without corners."""
+    if prior is not None:
+        from . import prior as _prior
+        tracks = _tracks_under_prior(ref_data, image_data, mask, conf, p0, prior, ctx)
+        if tracks is None:
+            logger.info("klt_tracker: no corner found")
+            return None
+        cols, n_init = frames.track_columns(*tracks)
+        frame = frames.assemble(cols, ordered=False)
+        frame["dx_prior"], frame["dy_prior"] = _prior.prior_columns(frame, prior)
+        if getattr(conf, "outliers_filtering", False):
+            frame = _prior.clip_residuals(frame, ctx=ctx).reset_index(drop=True)
+        return frame, n_init
     tracks = ops.klt_track(ref_data, image_data, mask, conf, p0=p0, ctx=ctx)
     if tracks is None:
         logger.info("klt_tracker: no corner found")
@@ -83,8 +121,11 @@ class _TileSession:
         self._host = (mon_box, ref_box)
         self.valid_pixels = -1                     # unknown until a fixed-parameter trial has run
 
-    def fixed(self, ksizes: tuple[int, int], inverted: bool) -> _Trial | None:
-        frame = self.pair.match_tile(self.conf, ksizes=ksizes, invert_mon=inverted, origin=self.tile[:2])
+    def fixed(self, ksizes: tuple[int, int], inverted: bool, prior=None) -> _Trial | None:
+        if prior is None:
+            frame = self.pair.match_tile(self.conf, ksizes=ksizes, invert_mon=inverted, origin=self.tile[:2])
+        else:
+            frame = self.pair.match_tile(self.conf, ksizes=ksizes, invert_mon=inverted, origin=self.tile[:2], prior=prior)
         self.valid_pixels = int(self.pair.ctx.stats().valid_pixels)
         if frame is None:
             return None
@@ -167,8 +208,16 @@ class KLT:
         self._prefetched: dict = {}                 # identity of the rasters -> first tile session queued by `prefetch`
 
     # ------------------------------------------------------------------ public surface
-    def match(self, mon_img, ref_img, mask) -> Iterator[DataFrame]:
-        """Match every tile of the pair; yields the frames of the tiles that produced key points (klt.py:198-234)."""
+    def match(self, mon_img, ref_img, mask, prior=None) -> Iterator[DataFrame]:
+        """Match every tile of the pair; yields the frames of the tiles that produced key points (klt.py:198-234).
+        `prior` (9 values mapping reference to monitored pixel coordinates, `karios_amd.matcher.prior`): the coarse geometry the
+        pre-aligner or the align step found.  Every key point is tracked from its guess on the rasters as they are - nothing is
+        shifted or warped, dx / dy are total displacements, the frames carry `dx_prior, dy_prior`.  A tile only tracks the corners
+        whose guess lies inside the same tile of the monitored raster: for offsets that are not small against `tile_size`, match the
+        pair as one tile.  The Laplacian kernel-size search takes no prior."""
+        if prior is not None:
+            yield from self._match_under_prior(mon_img, ref_img, mask, prior)
+            return
         grid = self.tile_boxes(mon_img.x_size, mon_img.y_size)
         logger.info("KLT: %dx%d px in %d tile(s) of %d px, polarity %s, Laplacian kernel %s", mon_img.x_size, mon_img.y_size, len(grid),
                     self._conf.tile_size, self._describe_polarity(), self._conf.laplacian_kernel_size)
@@ -190,6 +239,29 @@ class KLT:
                 logger.info("polarity search: %s", ", ".join(f"{name} kept on {n}/{total} tiles" for name, n in self._polarity_votes.most_common()))
             else:
                 logger.info("polarity search: no tile produced key points")
+
+    def _match_under_prior(self, mon_img, ref_img, mask, prior) -> Iterator[DataFrame]:
+        from .._lib import KariosHipError
+        from . import prior as _prior
+        prior = _prior.as_prior(prior)
+        if self._conf.laplacian_kernel_size == "auto":
+            raise KariosHipError("KLT.match: the Laplacian kernel-size search takes no prior; give laplacian_kernel_size")
+        ksizes = tiling.kernel_sizes(self._conf.laplacian_kernel_size)
+        mode = self._conf.laplacian_invert_polarity
+        for tile in self.tile_boxes(mon_img.x_size, mon_img.y_size):
+            session = self._open(tile, mon_img, ref_img, mask)
+            trials = [t for t in (session.fixed(ksizes, inv, prior=prior) for inv in ((False, True) if mode == "auto" else (bool(mode),))) if t is not None]
+            if not trials:
+                logger.info("tile (%d, %d): no valid pixels or no corners - skipped", tile[0], tile[1])
+                continue
+            best = max(trials, key=lambda t: t.inlier_ratio)
+            if mode == "auto":
+                self._polarity_votes[best.polarity] += 1
+            if self._gen_laplacian:
+                self._dump(session, best)
+            best.frame.attrs.clear()
+            logger.info("tile (%d, %d): %d of %d corners kept under the prior", tile[0], tile[1], len(best.frame), best.n_init)
+            yield best.frame
 
     def prefetch(self, mon_img, ref_img, mask=None) -> None:
         """Not in the reference: start reading and uploading the first tile of the NEXT pair now.  Called before the current

@@ -5,7 +5,7 @@ import numpy as np
 
 from .. import _lib
 from .._lib import Context, KariosHipError, KltParams, as_image, dtype_code, ptr, row_stride
-from ._place import _ctx
+from ._place import Place, _ctx, _mask_arg, _raster_arg
 
 
 def to_uint8(arr, invert: bool = False, ctx: Context | None = None, return_minmax: bool = False):
@@ -103,6 +103,52 @@ def calc_optical_flow_pyr_lk(prev_img, next_img, prev_pts, winSize=(25, 25), max
     c.check(c.lib.km_pyrlk(c.handle, ptr(a), ptr(b), a.shape[0], a.shape[1], ptr(p), p.shape[0], int(winSize[0]),
                            int(maxLevel), int(maxCount), float(epsilon), ptr(out)), "km_pyrlk")
     return out.reshape(-1, 1, 2)
+
+
+def pyrlk_initial(prev_img, next_img, prev_pts, guess_pts, winSize=(25, 25), maxLevel=1, maxCount=30, epsilon=0.03,
+                  ctx: Context | None = None):
+    """cv2.calcOpticalFlowPyrLK(prev, next, pts, guess, winSize=, maxLevel=, criteria=, flags=cv2.OPTFLOW_USE_INITIAL_FLOW): the search
+    of every point starts at its own guess (a position in `next`), not at the point -> next points (N,1,2) float32.  The reference
+    never passes the flag; a geometric prior is built on it (include/karios_hip.h: km_pyrlk_initial).  maxLevel 1, winSize <= 40 and an
+    image with a pyramid level 1 only: anything else is refused, nothing runs."""
+    c = _ctx(ctx)
+    a = np.ascontiguousarray(prev_img, np.uint8)
+    b = np.ascontiguousarray(next_img, np.uint8)
+    if a.shape != b.shape or a.ndim != 2:
+        raise KariosHipError("pyrlk_initial: image shape mismatch")
+    if winSize[0] != winSize[1]:
+        raise KariosHipError("pyrlk_initial: only square windows (KARIOS uses (w, w))")
+    p = np.ascontiguousarray(prev_pts, np.float32).reshape(-1, 2)
+    g = np.ascontiguousarray(guess_pts, np.float32).reshape(-1, 2)
+    if g.shape != p.shape:
+        raise KariosHipError("pyrlk_initial: one guess per point")
+    out = np.empty_like(p)
+    c.check(c.lib.km_pyrlk_initial(c.handle, ptr(a), ptr(b), a.shape[0], a.shape[1], ptr(p), ptr(g), p.shape[0], int(winSize[0]),
+                                   int(maxLevel), int(maxCount), float(epsilon), ptr(out)), "km_pyrlk_initial")
+    return out.reshape(-1, 1, 2)
+
+
+def prior_mask(ref, mon, prior, mask=None, nodata_ref=None, nodata_mon=None, x_off=0.0, y_off=0.0, dtype=None, ctx: Context | None = None):
+    """The corner mask under a geometric prior (include/karios_hip.h: km_prior_mask): 1 where `mask` (or, without one, the reference's
+    half of the automatic mask, klt.py:268-273) is set, the pixel has a guess and the guess, rounded half to even, meets a valid
+    pixel of `mon` inside the box -> uint8 H x W.  `prior`: 9 float64 values (matcher.prior); `x_off, y_off`: origin of the boxes in the
+    coordinates the prior maps.  numpy arrays in, a numpy array out; device tensors (contiguous rows) in, a device tensor out."""
+    what = "prior_mask"
+    place = Place((ref, mon, mask), what, "ref, mon and the mask")
+    pr, dr, H, W, sr = _raster_arg(place, ref, what, dtype)
+    pm, dm, Hm, Wm, sm = _raster_arg(place, mon, what, dtype)
+    if (H, W) != (Hm, Wm) or dr != dm:
+        raise KariosHipError("prior_mask: ref/mon shape or dtype mismatch")
+    pk, sk = _mask_arg(place, mask, H, W, what)
+    P = np.ascontiguousarray(np.asarray(prior, np.float64).reshape(-1))
+    if P.size != 9:
+        raise KariosHipError("prior_mask: a prior has 9 values")
+    out = place.empty((H, W), np.uint8)
+    nr = C.byref(C.c_double(float(nodata_ref))) if nodata_ref is not None else None
+    nm = C.byref(C.c_double(float(nodata_mon))) if nodata_mon is not None else None
+    place.call(_ctx(ctx), "km_prior_mask", pr, pm, _lib._DTYPES[dr], H, W, sr, sm, pk, sk, nr, nm, P.ctypes.data_as(C.POINTER(C.c_double)),
+               float(x_off), float(y_off), place.pointer(out))
+    return out
 
 
 def lk_oscillation_probe(quads, ctx: Context | None = None):

@@ -431,15 +431,22 @@ class ResidentPair:
             c.check(c.lib.km_d2h(c.handle, pts[i].ctypes.data_as(C.c_void_p), C.c_void_p(d), n * 8), "km_d2h")
         return "ok", tuple(p.reshape(-1, 1, 2) for p in pts)
 
-    def match_tile(self, conf, box=None, zncc_threshold=None, ksizes=None, invert_mon=None, origin=None, mutual_info: bool = False) -> DataFrame | None:
+    def match_tile(self, conf, box=None, zncc_threshold=None, ksizes=None, invert_mon=None, origin=None, mutual_info: bool = False,
+                   prior=None) -> DataFrame | None:
         """One tile of `KLT.match` (reference klt.py:236-349) on resident data with fixed Laplacian kernel sizes and
         polarity: `ksizes` (mon, ref) / `invert_mon` default to the configuration's (its 'auto' values are the caller's
         business: `karios_amd.matcher.KLT`).  `origin` (x, y) is added to the key points (default: the box offset).
         With `zncc_threshold` the frame also carries the `zncc_score` column of `_handle_klt_results` (core.py:876-893)
-        computed in the same device call."""
+        computed in the same device call.
+        `prior` (9 float64 values that map reference to monitored pixel coordinates, `karios_amd.matcher.prior`; the coordinates are
+        those of the key points, `origin` included): every key point is tracked from its guess on the rasters as they are
+        (km_klt_tile_frame_prior_dev), the frame carries `dx_prior, dy_prior` behind its columns, and the outlier clip of
+        `conf.outliers_filtering` runs on the residuals dx - dx_prior, dy - dy_prior.  None, the default, changes nothing."""
         if ksizes is None and conf.laplacian_kernel_size == "auto" or invert_mon is None and conf.laplacian_invert_polarity == "auto":
             raise KariosHipError("ResidentPair.match_tile: 'auto' modes are resolved by karios_amd.matcher.KLT")
         x_off, y_off = origin if origin is not None else ((box[0], box[1]) if box is not None else (0, 0))
+        if prior is not None:
+            return self._match_tile_prior(conf, box, x_off, y_off, prior, zncc_threshold, ksizes, invert_mon, mutual_info)
         if _clips(conf) and self._frame_capacity(conf, box) > _lib.CLIP_MAX_ROWS:
             # more rows than the device clip holds (maxCorners 0 on a large tile): FB test, clip and ordering on the host
             return self._match_tile_host_clip(conf, box, x_off, y_off, zncc_threshold, ksizes, invert_mon)
@@ -532,6 +539,39 @@ class ResidentPair:
         frame = frames.block_to_frame(buf, cap, n_scores)
         if frame is not None:
             frame.attrs["Ninit"] = int(buf[:2].view(np.int32)[1])
+        return frame
+
+    def _match_tile_prior(self, conf, box, x_off, y_off, prior, zncc_threshold=None, ksizes=None, invert_mon=None, mutual_info: bool = False):
+        """`match_tile` under a geometric prior: one device call (mask under the prior, seeded tracker, frame, scores), then on the
+        host the two prior columns and - with `conf.outliers_filtering` - the clip of the residuals through `ops.sigma_clip`, in corner
+        order as the tracker's own clip runs (the device call keeps "frame_clip" off: that stage clips dx, dy themselves)."""
+        from .matcher import prior as _prior
+        c = self.ctx
+        if self.window is not None:
+            raise KariosHipError("ResidentPair.match_tile: a prior on a windowed pair is not supported")
+        P = _prior.as_prior(prior)
+        n_scores = 0 if zncc_threshold is None else (3 if mutual_info else 1)
+        _, _, bx, by, off = self._box(box)
+        prm = self._params(conf, ksizes, invert_mon)
+        cap = prm.max_corners if prm.max_corners > 0 else max(1, (bx * by) // 4)
+        buf = np.empty(frames.block_words(cap, 3), np.float32)
+        ref, mon, mask, nr, nm = self._image_args(off)
+        # (without a threshold no row is scored: a score never exceeds 1)
+        thr = 2.0 if zncc_threshold is None else float(zncc_threshold)
+        with self._frame_mi(n_scores == 3):
+            c.check(c.lib.km_klt_tile_frame_prior_dev(c.handle, ref, mon, self.code, by, bx, self.x_size, self.x_size, mask, self.x_size, nr, nm,
+                                                      C.byref(prm), float(x_off), float(y_off), C.c_void_p(self.ref_ptr), C.c_void_p(self.mon_ptr),
+                                                      self.y_size, self.x_size, self.x_size, self.x_size, thr,
+                                                      P.ctypes.data_as(C.POINTER(C.c_double)), buf.ctypes.data_as(C.c_void_p), cap),
+                    "km_klt_tile_frame_prior_dev")
+        frame = frames.block_to_frame(buf, cap, n_scores)
+        if frame is None:
+            return None
+        n_init = int(buf[:2].view(np.int32)[1])
+        frame["dx_prior"], frame["dy_prior"] = _prior.prior_columns(frame, P, x_off, y_off)
+        if _clips(conf):
+            frame = _prior.clip_residuals(frame, ctx=c)
+        frame.attrs["Ninit"] = n_init
         return frame
 
     def match_tile_auto_ksize(self, conf, box=None, invert_mon: bool = False, candidates=tiling.AUTO_KSIZE_CANDIDATES, origin=None):
