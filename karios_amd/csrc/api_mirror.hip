@@ -151,7 +151,7 @@ int km_pyrlk(km_ctx *c, const uint8_t *prev, const uint8_t *next, int H, int W, 
     return KM_OK;
 }
 
-// test hook: the oscillation predicate of the LK kernels (k_lk.hip: lk_oscillates) on n host quadruples (ddx, pdx, ddy, pdy)
+// test hook: the oscillation predicate of the LK kernels (lk_device.hpp: lk_oscillates) on n host quadruples (ddx, pdx, ddy, pdy)
 int km_lk_oscillation_probe(km_ctx *c, const float *quads, int n, uint8_t *out)
 {
     int rc;

@@ -146,7 +146,7 @@ enum km_slot {
     WS_F64_BLUEX,   //   ... and the tables of a Bluestein dimension
     WS_F64_BLUEY,
     WS_F64_MASK,    //   ... which columns / column tiles the inverse needs on the Hermitian half plane
-    WS_UNITS_LK,    // k_lk.hip: the per-unit argument table of a batched LK launch
+    WS_UNITS_LK,    // k_lk2.hip: the per-unit argument table of a batched LK launch
     WS_UNITS_MM,    // api_units.hip: early min / max results of a batch ({min_ref, max_ref, min_mon, max_mon} per unit)
     WS_AL_OUT,      // api_align.hip: destination of the host-API warp / Sobel forms
     WS_AL_WARP,     //   uint8 pre-warped mon of a refinement candidate
@@ -650,7 +650,7 @@ size_t kf_kept_capacity(int max_corners);
 int kf_rank(km_ctx *c, const unsigned long long *d_keys, size_t cap_keys, int H, int W, int max_corners, double quality, double min_distance,
             km_scalars *sc, km_eig_partials partials);
 int kf_select(km_ctx *c, int H, int W, int max_corners, double min_distance, float *d_xy, int cap, km_scalars *sc);
-// k_lk.hip
+// k_lk.hip, k_lk2.hip
 struct km_pyr {
     const uint8_t *img[5];
     int H[5], W[5];
@@ -676,7 +676,7 @@ static inline int kl_track_seeded(km_ctx *c, const km_pyr &A, const km_pyr &B, c
 }
 #endif
 int kl_oscillation_probe(km_ctx *c, const float *d_q, int n, uint8_t *d_out);   // test hook of the LK kernels' oscillation predicate
-// independent forward + backward tracker runs in one launch (k_lk.hip kl_jobs_launch; the kernel-size search of klt.py:465-545)
+// independent forward + backward tracker runs in one launch (k_lk2.hip kl_jobs_launch; the kernel-size search of klt.py:465-545)
 #define KM_LK_JOBS_MAX 64
 struct km_lk_job {
     km_pyr A, B;                  // pyramids of the image the points live in / the image they are tracked into

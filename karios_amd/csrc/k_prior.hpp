@@ -1,6 +1,6 @@
 // k_prior.hip: what a geometric prior (prior_math.hpp) adds to the tile path - the corner mask under a prior (rule 4 of DESIGN.md
 // section 21: a reference pixel may become a corner only where its guess meets a valid monitored pixel) and the seeded launch of the
-// tracker's second form (k_lk.hip).  tests/lk_prior_restatement.py is the definition.
+// tracker's second form (k_lk2.hip).  tests/lk_prior_restatement.py is the definition.
 // A compiler that is not hipcc (the host sanitizer build of the API files, the stand-alone program of tests/test_lk_prior_host.py) gets
 // the mask launcher defined here as plain loops over the same header - device memory is host memory there, `c` is not touched - and
 // the seeded tracker launch as the stand-in of the unseeded one (tests/hoststub: kernels are stand-ins there).

@@ -1,5 +1,5 @@
 // prior_math.hpp: a geometric prior of the tracker - 9 float64 values P (row-major) that map reference pixel coordinates to monitored
-// pixel coordinates - as plain C++ on doubles, shared by the seeded LK kernels (k_lk.hip: the start position of every key point), the
+// pixel coordinates - as plain C++ on doubles, shared by the seeded LK kernels (k_lk2.hip: the start position of every key point), the
 // mask kernel (k_prior.hip), the host form of its launcher (k_prior.hpp) and, transcribed, tests/lk_prior_restatement.py, which is the
 // definition.  Every operation rounds on its own, in the order written: this text needs -ffp-contract=off and a
 // correctly rounded division on every compiler that reads it.

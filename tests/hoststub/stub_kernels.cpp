@@ -49,7 +49,7 @@ struct launch : so::op {
 #define SC_CORNERS offsetof(km_scalars, max_eig_key), sizeof(km_scalars)      // everything behind the min / max and the valid-pixel count
 static size_t dtype_bytes(int dtype) { return km_any_dtype_size(dtype); }
 static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-enum { LK_TABLE_ENTRY = 512 };      // bytes of one entry of the LK argument table (k_lk.hip lk_args: two pyramids and a dozen words; the stand-in's own figure)
+enum { LK_TABLE_ENTRY = 512 };      // bytes of one entry of the LK argument table (lk_device.hpp lk_args: two pyramids and a dozen words; the stand-in's own figure)
 
 static bool is_pinned(const void *p)
 {
@@ -820,7 +820,7 @@ int kl_jobs_launch(km_ctx *c, const km_lk_job *jobs, int n_jobs, int n_max, int 
     if (stub().lk_jobs_unsupported) return KM_E_UNSUPPORTED;
     (void)win; (void)max_count; (void)eps;
     const launch L(c, "kl_jobs_launch");
-    L.slot(WS_UNITS_LK, LK_TABLE_ENTRY * KM_LK_JOBS_MAX);      // (k_lk.hip: the jobs' argument table, uploaded on c->stream)
+    L.slot(WS_UNITS_LK, LK_TABLE_ENTRY * KM_LK_JOBS_MAX);      // (k_lk2.hip: the jobs' argument table, uploaded on c->stream)
     for (int j = 0; j < n_jobs; j++) {
         lk_declare(L, jobs[j].A, jobs[j].B, jobs[j].pts_in, jobs[j].d_n, n_max, true, jobs[j].p1, jobs[j].p0r);
         const int rc = track_of(jobs[j].A, jobs[j].B, jobs[j].pts_in, jobs[j].d_n, n_max, true, jobs[j].p1, jobs[j].p0r);
@@ -838,7 +838,7 @@ int kf_count_kept_jobs(km_ctx *c, const km_count_jobs &J, int n_jobs, int n_max,
     return KM_OK;
 }
 static km_units g_lk_units[2];       // (per workspace lane: a pipelined submission prepares its table before the previous one's LK is launched)
-// (k_lk.hip: the per-unit argument table is uploaded into the lane's WS_UNITS_LK on c->stream; the launch reads it from there)
+// (k_lk2.hip: the per-unit argument table is uploaded into the lane's WS_UNITS_LK on c->stream; the launch reads it from there)
 int kl_units_prepare(km_ctx *c, const km_units &U, int, int, int, double)
 {
     const launch L(c, "kl_units_prepare");

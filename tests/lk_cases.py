@@ -1,4 +1,4 @@
-"""Inputs on which the LK tracker (csrc/k_lk.hip) can be wrong without the geometry tests noticing: saturated contrast (the integer
+"""Inputs on which the LK tracker (csrc/k_lk.hip, k_lk2.hip) can be wrong without the geometry tests noticing: saturated contrast (the integer
 ranges of the packed sums), windows at the eigenvalue cut, and start positions whose bilinear weights are degenerate or negative.
 tests/test_lk_cases_host.py proves on the CPU that every fixture does what it is there for (with tests/lk_restatement.py),
 tests/test_gpu_lk_extremes.py runs them through the kernels against `oracle.pyr_lk`.

@@ -1,4 +1,4 @@
-"""One level and one window of the LK tracker (csrc/k_lk.hip) in plain numpy with int64 sums - used ONLY to choose the fixtures of
+"""One level and one window of the LK tracker (csrc/k_lk.hip, k_lk2.hip) in plain numpy with int64 sums - used ONLY to choose the fixtures of
 tests/lk_cases.py and to prove in tests/test_lk_cases_host.py that each does what it is there for.  It is not a second oracle: what
 a kernel returns is always compared with `oracle.pyr_lk`.
 
@@ -14,12 +14,12 @@ F32 = np.float32
 FLT_SCALE = F32(1.0 / (1 << 20))
 FLT_EPSILON = F32(np.finfo(np.float32).eps)
 MIN_EIG = F32(1e-4)
-LK_RUN = 5                      # pixels of a run (k_lk.hip)
+LK_RUN = 5                      # pixels of a run (lk_device.hpp)
 WRAP = 1 << 31                  # an int32 holds sums of magnitude below this
 
 
 def lk_weights(a, b):
-    """The bilinear weights of `lk_weights` in k_lk.hip, float32 step by step -> (w00, w01, w10, w11)."""
+    """The bilinear weights of `lk_weights` in lk_device.hpp, float32 step by step -> (w00, w01, w10, w11)."""
     a, b = F32(a), F32(b)
     oma, omb = F32(1) - a, F32(1) - b
     t00, t01, t10 = oma * omb, a * omb, oma * b
@@ -56,7 +56,7 @@ def template(img, ipx, ipy, win, deriv=None):
 
 
 def cut_values(iA11, iA12, iA22, win):
-    """The float32 values of k_lk.hip lines 347-351 from the integer normal matrix (int64 scalars or arrays), every step rounded on
+    """The float32 values of the eigenvalue cut of `lk_track_point` (k_lk.hip) and `lk2_track_point` (k_lk2.hip) from the integer normal matrix (int64 scalars or arrays), every step rounded on
     its own -> dict; `tracked` is the outcome of the cut `minEig < 1e-4f || D < FLT_EPSILON`."""
     A11, A12, A22 = (np.asarray(v, np.int64).astype(F32) * FLT_SCALE for v in (iA11, iA12, iA22))
     D = A11 * A22 - A12 * A12
@@ -106,7 +106,7 @@ def mismatch_terms(tI, tIx, tIy, img_j, nx, ny):
 
 
 def lane_of(win):
-    """Lane of every window pixel as `lk2_body` deals them: run r = t * 64 + lane, row r / rpr, columns (r % rpr) * 5 .. + 4,
+    """Lane of every window pixel as `lk_run_desc` (lk_device.hpp) deals them: run r = t * 64 + lane, row r / rpr, columns (r % rpr) * 5 .. + 4,
     rpr = ceil(win / 5) -> (int array win x win, runs per lane NR)."""
     rpr = (win + LK_RUN - 1) // LK_RUN
     yy, xx = np.mgrid[0:win, 0:win]

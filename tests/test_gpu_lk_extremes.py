@@ -1,4 +1,4 @@
-"""The LK kernels (csrc/k_lk.hip) on the fixtures of tests/lk_cases.py: saturated contrast (mismatch sums that reach 2^31 over four
+"""The LK kernels (csrc/k_lk.hip, k_lk2.hip) on the fixtures of tests/lk_cases.py: saturated contrast (mismatch sums that reach 2^31 over four
 neighbouring lanes), windows at the eigenvalue cut, start positions with degenerate and negative bilinear weights.  Every comparison
 is `array_equal` against `oracle.pyr_lk` - forward only (`km_pyrlk`) and forward + backward in one launch (`km_klt_track` with given
 corners, against the oracle's two calls) - in both forms of the kernel ("lk2" 1 / 0) and, in the resident-patch form, with the byte

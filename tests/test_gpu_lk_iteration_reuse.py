@@ -1,4 +1,4 @@
-"""LK iteration loop of the resident-patch form (csrc/k_lk.hip, `lk2_track_point`): an iteration reads the search patch from LDS and
+"""LK iteration loop of the resident-patch form (csrc/k_lk2.hip, `lk2_track_point`): an iteration reads the search patch from LDS and
 cuts the runs' vertical byte pairs again only when the window's integer position moved since the previous iteration of the pass
 (km_set_option "lk_reuse", default 1); with 0 every iteration does.  The integers are the same either way, so every comparison here
 is `array_equal` - against the oracle, and between the two settings - on p1, p0r and the frame columns.

@@ -270,7 +270,7 @@ def test_good_features_flat_image_is_none(ops):
 
 @pytest.fixture(params=[1, 0], ids=["lk_resident_patches", "lk_first_form"])
 def lk_form(request, ops):
-    """Both forms of the LK kernel (k_lk.hip): four resident patches per key point (default for two-level pyramids) and the
+    """Both forms of the LK kernel (k_lk2.hip, k_lk.hip): four resident patches per key point (default for two-level pyramids) and the
     first form (per-level staging + derivative planes; deeper pyramids, row bands)."""
     ctx = ops._lib.default_context()
     ctx.set_option("lk2", request.param)

@@ -561,7 +561,7 @@ def test_inline_assembly_hazard_scan_of_the_device_code(tmp_path):
         pytest.skip("hipcc not available")
     csrc = os.path.join(ROOT, "karios_amd", "csrc")
     srcs = [f for f in sorted(os.listdir(csrc)) if f.endswith(".hip") and ("asm" in open(os.path.join(csrc, f)).read() or f in ("k_eig2.hip", "k_eig3.hip"))]
-    assert {"k_eig3.hip", "k_lk.hip", "k_lap.hip", "k_fft.hip"} <= set(srcs), srcs
+    assert {"k_eig3.hip", "k_lk.hip", "k_lk2.hip", "k_lap.hip", "k_fft.hip"} <= set(srcs), srcs
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
              "-fno-gpu-flush-denormals-to-zero", "-I/opt/rocm/include", "--cuda-device-only", "-S"]      # (the Makefile's flags)
 

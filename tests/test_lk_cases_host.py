@@ -1,6 +1,6 @@
 """The fixtures of tests/lk_cases.py do what they are there for (CPU only; run with -s to see the counts).
 
-`saturated`: the first level-0 iteration's mismatch sums, dealt to the lanes as `lk2_body` deals the window's runs, reach 2^31 over
+`saturated`: the first level-0 iteration's mismatch sums, dealt to the lanes as the kernels (`lk_run_desc`, lk_device.hpp) deal the window's runs, reach 2^31 over
 four neighbouring lanes where the fixture says so and nowhere else.  `cut`: windows on both sides of `minEig < 1e-4f`, within 1 % of
 it, and the oracle skips exactly the levels the restatement says it skips.  `weights`: every start position has the bilinear
 weights the fixture claims, the negative fourth weight among them.
