@@ -369,6 +369,10 @@ class Context:
         self._abandoned = []
         self._abandoned_lock = threading.Lock()
         self._alive = [True]      # shared with the finalizers of this context's page-locked arrays (`pinned_empty`)
+        self._pool, self._pool_bytes = {}, 0      # released device buffers by capacity (`dev_alloc`)
+        self._options = {}                        # last value given to `set_option`, by name
+        self._frame_sink = (None, 0, 0)           # (pointer, capacity, pitch) of `set_frame_sink`
+        self._kp_staging = None                   # page-locked staging of key-point columns (`ResidentPair._stage`), grow-only
         # development / A-B measurements: KARIOS_HIP_OPTIONS="lk2=0,eig3=0" applies `set_option` to every new context
         for item in filter(None, os.environ.get("KARIOS_HIP_OPTIONS", "").split(",")):
             name, _, value = item.partition("=")
@@ -382,8 +386,7 @@ class Context:
         """-> (device pointer, capacity).  Capacities are multiples of 2 MiB so that boxes of similar size share buffers."""
         self.drain()
         cap = max(1, (int(nbytes) + (2 << 20) - 1) >> 21) << 21
-        pool = self.__dict__.setdefault("_pool", {})
-        free = pool.get(cap)
+        free = self._pool.get(cap)
         if free:
             self._pool_bytes -= cap
             return free.pop(), cap
@@ -397,19 +400,18 @@ class Context:
         i-1 with the upload of pair i+1 that is travelling under pair i's compute)."""
         if not getattr(self, "handle", None):
             return
-        pool = self.__dict__.setdefault("_pool", {})
-        held = self.__dict__.setdefault("_pool_bytes", 0)
+        held = self._pool_bytes
         self.lib.km_ctx_sync(self.handle)
         if upload_in_flight:
             self.lib.km_upload_wait(self.handle)
         if held + cap <= self.POOL_LIMIT_BYTES:
-            pool.setdefault(cap, []).append(ptr_)
+            self._pool.setdefault(cap, []).append(ptr_)
             self._pool_bytes = held + cap
         else:
             self.lib.km_dev_free(self.handle, C.c_void_p(ptr_))
 
     def trim_pool(self):
-        for cap, ptrs in self.__dict__.get("_pool", {}).items():
+        for cap, ptrs in self._pool.items():
             for p in ptrs:
                 self.lib.km_dev_free(self.handle, C.c_void_p(p))
         self._pool, self._pool_bytes = {}, 0
@@ -453,7 +455,7 @@ class Context:
             self.drain()
             # page-locked arrays that outlive the context are released without it (km_host_free(NULL, p)); the staging area the
             # context itself owns goes first, while its streams still exist
-            self.__dict__.pop("_kp_staging", None)
+            self.__dict__.pop("_kp_staging", None)    # (removed, not reset: a closed context has no staging to grow)
             self._alive[0] = False
             self.trim_pool()
             self.lib.km_ctx_destroy(self.handle)
@@ -498,7 +500,7 @@ class Context:
         """Knob of include/karios_hip.h km_set_option, e.g. set_option("fused_eig", 0) or the test knobs "key_cap",
         "stage_cap", "topk_factor", "select_first", "defer" (0 restores a default)."""
         self.check(self.lib.km_set_option(self.handle, name.encode(), int(value)), "km_set_option")
-        self.__dict__.setdefault("_options", {})[name] = int(value)
+        self._options[name] = int(value)
 
     def set_frame_sink(self, ptr: int | None, nbytes: int = 0, pitch: int = 0) -> None:
         """km_set_frame_sink[_pitch]: every frame block the tile entry points produce from now on is also copied to device memory at
@@ -507,11 +509,11 @@ class Context:
         OFF - by then it belongs to a newer unit."""
         self.check(self.lib.km_set_frame_sink_pitch(self.handle, C.c_void_p(ptr) if ptr else None, int(nbytes) if ptr else 0, int(pitch) if ptr else 0),
                    "km_set_frame_sink_pitch")
-        self.__dict__["_frame_sink"] = (int(ptr), int(nbytes), int(pitch)) if ptr else (None, 0, 0)
+        self._frame_sink = (int(ptr), int(nbytes), int(pitch)) if ptr else (None, 0, 0)
 
     @property
     def frame_sink(self) -> tuple:
-        return self.__dict__.get("_frame_sink", (None, 0, 0))
+        return self._frame_sink
 
     def eig3_item_classes(self, unit: int) -> dict:
         """Strip items of the fused 8-pixel eigenvalue pass by class ("eig3_valid_items") and its tie rows, for unit `unit` of the last
@@ -522,7 +524,7 @@ class Context:
 
     def get_option(self, name: str, default: int = 0) -> int:
         """Last value given to `set_option` (the library's own defaults are not queried)."""
-        return self.__dict__.get("_options", {}).get(name, default)
+        return self._options.get(name, default)
 
     def phase_info(self) -> tuple[int, float]:
         """(path, margin) of the last phase correlation: path 1 = float32 hand-written FFT, 2 = double precision (hand-written too, k_fft64.hip)."""

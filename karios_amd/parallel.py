@@ -541,6 +541,7 @@ def match_tile_banded(mon_img, ref_img, mask_img, conf, zncc_threshold=None, hal
     from ._lib import NAN_OUTSIDE_WINDOW, KariosHipError, as_image, default_context, dtype_code
     from .ops import make_params
     from .resident import DeviceBuffer, ResidentPair
+    from .resident.calls import frame_capacity, no_data_pointers
     ws, rank = _world()
     ctx = ctx if ctx is not None else default_context()
     H, W = mon_img.y_size, mon_img.x_size
@@ -587,8 +588,7 @@ def match_tile_banded(mon_img, ref_img, mask_img, conf, zncc_threshold=None, hal
     prm = make_params(conf, *tiling.kernel_sizes(conf.laplacian_kernel_size), bool(conf.laplacian_invert_polarity))
     lap_ref, lap_mon, mask = (DeviceBuffer(ctx, hs * W) for _ in range(3))
     valid = C.c_int64()
-    nr = C.byref(C.c_double(float(pair.no_data_ref))) if pair.no_data_ref is not None else None
-    nm = C.byref(C.c_double(float(pair.no_data_mon))) if pair.no_data_mon is not None else None
+    nr, nm = no_data_pointers(pair)
     ctx.check(lib.km_band_prefilter_dev(h, C.c_void_p(pair.ref_ptr), C.c_void_p(pair.mon_ptr), code, hs, W, W, W, mm.ctypes.data_as(C.POINTER(C.c_double)),
                                         nr, nm, prm.ksize_ref, prm.ksize_mon, prm.invert_mon, y0 - ys, y1 - ys,
                                         C.c_void_p(pair.mask_ptr) if pair.mask_ptr else None, C.c_void_p(lap_ref.ptr), C.c_void_p(lap_mon.ptr),
@@ -605,7 +605,7 @@ def match_tile_banded(mon_img, ref_img, mask_img, conf, zncc_threshold=None, hal
     # ---- candidates: every rank contributes its strongest value bins; the merged list is cut where the weakest contribution ends
     max_corners = int(conf.maxCorners)
     sliced = max_corners > 0 and conf.minDistance >= 1
-    cap = max_corners if max_corners > 0 else max(1, (H * W) // 4)
+    cap = frame_capacity(max_corners, W, H)
     corners = None
     for k_target in ((8 * max_corners, 0) if sliced else (0,)):
         room = hs * W // 4 + 65536

@@ -130,88 +130,52 @@ class FrameStream:
             pass
 
     # ------------------------------------------------------------------ the two halves
-    def _host_half(self, pair: ResidentPair, pend):
-        """Worker thread: touches the frame slot (km_frame_wait) and numpy / pandas only."""
+    def _frame(self, pair: ResidentPair, raw: RawFrame):
+        """A unit's DataFrame with its score columns: numpy / pandas only (every column is in place: `score_frame` makes no library call).
+        Scored when the block carries score columns - for a repeated unit too: `match_tile_raw` adds them exactly when a threshold is set."""
+        frame = raw.to_frame(radial=self.score_columns)
+        if frame is not None and self.score_columns and raw.with_zncc:
+            frame = pair.score_frame(frame, self.threshold, mutual_info=self.mutual_info)
+        return frame
+
+    def _host_half(self, pairs, pend):
+        """Worker thread: touches the frame slot (km_frame_wait) and numpy / pandas only.  `pend`: a `PendingBatch` (the units' blocks
+        arrive together), a `PendingFrame`, or anything else: the finished block of a blocking call -> ([(raw, frame | None)] per unit, spans);
+        a flagged unit's frame is left to `_finish`."""
         import time
         t_cpu = time.thread_time()
         try:
-            return self._host_half_body(pair, pend)
+            if isinstance(pend, (PendingBatch, PendingFrame)):
+                raws = pend.wait() if isinstance(pend, PendingBatch) else [pend.wait()]
+                spans = pend.stage_ms() if self.want_spans else {}
+            else:
+                raws, spans = [pend], {}
+            return [(raw, None if raw.flags else self._frame(pair, raw)) for pair, raw in zip(pairs, raws)], spans
         finally:
             self.worker_cpu_s += time.thread_time() - t_cpu
 
-    def _host_half_body(self, pair: ResidentPair, pend):
-        raw = pend.wait() if isinstance(pend, PendingFrame) else pend
-        spans = pend.stage_ms() if self.want_spans and isinstance(pend, PendingFrame) else {}
-        frame = None
-        if not raw.flags:
-            frame = raw.to_frame(radial=self.score_columns)
-            if frame is not None and self.score_columns and raw.with_zncc:
-                frame = pair.score_frame(frame, self.threshold, mutual_info=self.mutual_info)     # every column is in place: pure numpy, no library call
-        return raw, spans, frame
-
-    def _batch_host_half(self, pairs, pend: PendingBatch):
-        """Worker thread, batched submission: the units' blocks arrive together."""
-        import time
-        t_cpu = time.thread_time()
-        try:
-            return self._batch_host_half_body(pairs, pend)
-        finally:
-            self.worker_cpu_s += time.thread_time() - t_cpu
-
-    def _batch_host_half_body(self, pairs, pend: PendingBatch):
-        raws = pend.wait()
-        spans = pend.stage_ms() if self.want_spans else {}
-        out = []
-        for pair, raw in zip(pairs, raws):
-            frame = None
-            if not raw.flags:
-                frame = raw.to_frame(radial=self.score_columns)
-                if frame is not None and self.score_columns and raw.with_zncc:
-                    frame = pair.score_frame(frame, self.threshold, mutual_info=self.mutual_info)
-            out.append((raw, frame))
-        return out, spans
-
-    def _collect_batch(self, item) -> list[StreamResult]:
-        pairs, pend, tags, fut = item
-        done, spans = fut.result()
-        out = []
-        for i, (pair, (raw, frame), tag) in enumerate(zip(pairs, done, tags)):
-            redone, flags = False, raw.flags
-            if raw.flags:                  # this unit alone through the exact path (the others of the batch stand)
-                raw = pend.redo(i)
-                frame = raw.to_frame(radial=self.score_columns)
-                if frame is not None and self.score_columns and self.threshold is not None:
-                    frame = pair.score_frame(frame, self.threshold, mutual_info=self.mutual_info)
-                redone = True
-                self.units_redone += 1
-            if frame is not None and self.host_stage is not None:
-                frame = self.host_stage(frame, pair)
-            # the batch's stage spans are attached to its FIRST unit (they cover all units: one set of launches)
-            out.append(StreamResult(frame, raw, tag, redone, spans if i == 0 else {}, flags))
-        return out
-
-    def _collect(self, item):
-        if isinstance(item[1], PendingBatch):
-            # the NEWEST submission of a pipelined context still lacks its tail: enqueue it before blocking on its frame
-            if self._piped:
-                item[1].ctx.flush(item[1].ticket)
-            return self._collect_batch(item)
-        return [self._collect_one(item)]
-
-    def _collect_one(self, item) -> StreamResult:
-        pair, pend, tag, fut = item
-        raw, spans, frame = fut.result()
+    def _finish(self, pair, pend, i, raw, frame, tag, spans) -> StreamResult:
+        """Submitting thread: unit `i` of `pend` becomes its result - repeated alone through the exact path when it did not fit the fixed
+        capacities of the synchronisation-free corner path (the others of a batch stand), then the host stage."""
         redone, flags = False, raw.flags
-        if raw.flags:                      # did not fit the fixed capacities of the synchronisation-free corner path: exact repeat, here
-            raw = pend.redo()
-            frame = raw.to_frame(radial=self.score_columns)
-            if frame is not None and self.score_columns and self.threshold is not None:
-                frame = pair.score_frame(frame, self.threshold, mutual_info=self.mutual_info)
+        if flags:
+            raw = pend.redo(i) if isinstance(pend, PendingBatch) else pend.redo()
+            frame = self._frame(pair, raw)
             redone = True
             self.units_redone += 1
         if frame is not None and self.host_stage is not None:
             frame = self.host_stage(frame, pair)
         return StreamResult(frame, raw, tag, redone, spans, flags)
+
+    def _collect(self, item) -> list[StreamResult]:
+        pairs, pend, tags, fut = item
+        # the NEWEST submission of a pipelined context still lacks its tail: enqueue it before blocking on its frame
+        if self._piped and isinstance(pend, PendingBatch):
+            pend.ctx.flush(pend.ticket)
+        done, spans = fut.result()
+        # a batch's stage spans are attached to its FIRST unit (they cover all units: one set of launches)
+        return [self._finish(pair, pend, i, raw, frame, tag, spans if i == 0 else {})
+                for i, (pair, (raw, frame), tag) in enumerate(zip(pairs, done, tags))]
 
     # ------------------------------------------------------------------ API
     def submit(self, pair: ResidentPair, conf, box=None, origin=None, tag=None, on_submitted=None) -> list[StreamResult]:
@@ -227,7 +191,7 @@ class FrameStream:
             pend = pair.match_tile_raw(conf, box, self.threshold, origin, mutual_info=self.mutual_info)    # (blocking; repeats a flagged tile itself)
         if on_submitted is not None:
             on_submitted(pend)
-        self._pending.append((pair, pend, tag, self._pool.submit(self._host_half, pair, pend)))
+        self._pending.append(([pair], pend, [tag], self._pool.submit(self._host_half, [pair], pend)))
         out = []
         while len(self._pending) > self.depth:
             out += self._collect(self._pending.popleft())
@@ -261,7 +225,7 @@ class FrameStream:
             if on_submitted is not None:
                 on_submitted(pend, i)
             pairs = [u[0] for u in chunk]
-            self._pending.append((pairs, pend, chunk_tags, self._pool.submit(self._batch_host_half, pairs, pend)))
+            self._pending.append((pairs, pend, chunk_tags, self._pool.submit(self._host_half, pairs, pend)))
             while len(self._pending) > self.depth:
                 out += self._collect(self._pending.popleft())
             i += len(chunk)

@@ -14,13 +14,13 @@ mon, ref = mon_t.cpu().numpy().view(np.uint16), ref_t.cpu().numpy().view(np.uint
 del mon_t, ref_t
 for rep in range(2):
     print("guard on ", round(legs.end_to_end(mon, ref, ctx, 10)["ms_per_pair"], 3), flush=True)
-    orig, orig_intact = resident._SharedEntry.__init__, resident._SharedEntry.intact
+    orig, orig_intact = resident.shared._SharedEntry.__init__, resident.shared._SharedEntry.intact
     def no_guard(self, pair, m, r, rasters):
         self.pair, self.mon, self.ref = pair, m, r
         self.raster_ids = tuple(id(x) for x in rasters if x is not None); self.rasters = tuple(x for x in rasters if x is not None); self.guarded = []
-    resident._SharedEntry.__init__ = no_guard
-    resident._SharedEntry.intact = lambda self, m, r: True
+    resident.shared._SharedEntry.__init__ = no_guard
+    resident.shared._SharedEntry.intact = lambda self, m, r: True
     print("guard off", round(legs.end_to_end(mon, ref, ctx, 10)["ms_per_pair"], 3), flush=True)
-    resident._SharedEntry.__init__ = orig
-    resident._SharedEntry.intact = orig_intact
+    resident.shared._SharedEntry.__init__ = orig
+    resident.shared._SharedEntry.intact = orig_intact
     resident.forget_shared_pairs()
