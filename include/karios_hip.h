@@ -266,6 +266,17 @@ typedef struct km_unit {
  * a shrunken test capacity): submit the units one by one then.  Either every unit carries a user mask (km_unit.d_mask) or none. */
 int km_klt_units_frame_submit(km_ctx *ctx, const km_unit *units, int n_units, int dtype, const double *nodata_ref, const double *nodata_mon,
                               const km_klt_params *prm, double zncc_threshold, int cap, int *ticket);
+/* km_klt_units_frame_submit under a geometric prior per unit (`priors`: n_units x 9 float64 in unit order, each as the `prior` of
+ * km_klt_tile_frame_prior_dev): every key point of unit u starts at its guess under priors + 9 u on the rasters as they are, and only
+ * pixels whose guess meets a valid monitored pixel of the unit's box may become corners.  Block u is bit for bit the block
+ * km_klt_tile_frame_prior_dev writes for unit u alone (same x_off, y_off, the unit's user mask as base, the same score columns; bare
+ * frames without full rasters); a block whose header word 2 != 0 is repeated alone through that call.  Tickets, km_frame_wait, the frame
+ * sink, km_frame_flush and "units_pipeline" behave as for km_klt_units_frame_submit, and the two kinds of submission may alternate.
+ * KM_E_ARG: null or non-finite priors (the text names unit and index).  KM_E_UNSUPPORTED: whatever km_klt_units_frame_submit does not
+ * cover, "frame_clip" 1 (under a prior the clip runs on the residuals, behind the frame) or a unit with a window (win_H != 0).  A refused
+ * call has queued nothing. */
+int km_klt_units_frame_prior_submit(km_ctx *ctx, const km_unit *units, int n_units, int dtype, const double *nodata_ref, const double *nodata_mon,
+                                    const km_klt_params *prm, double zncc_threshold, int cap, const double *priors, int *ticket);
 /* "units_pipeline": enqueue what the last km_klt_units_frame_submit deferred (its LK, frame stage, scores and copy-out) - if that
  * submission is frame `ticket` (ticket < 0: whichever it is).  Call it on the submitting thread when no further submission follows
  * before the frame is waited for; a no-op otherwise. */

@@ -156,6 +156,7 @@ SIGNATURES = {
     "km_set_frame_sink": (_i, [_vp, _vp, C.c_size_t]),
     "km_set_frame_sink_pitch": (_i, [_vp, _vp, C.c_size_t, C.c_size_t]),
     "km_klt_units_frame_submit": (_i, [_vp, C.POINTER(KmUnit), _i, _i, _pd, _pd, C.POINTER(KltParams), _d, _i, C.POINTER(C.c_int)]),
+    "km_klt_units_frame_prior_submit": (_i, [_vp, C.POINTER(KmUnit), _i, _i, _pd, _pd, C.POINTER(KltParams), _d, _i, _pd, C.POINTER(C.c_int)]),
     "km_stream_wait_frame": (_i, [_vp, _i, _vp]),
     "km_phase_info": (_i, [_vp, _pi, _pd]),
     "km_phase_plan": (_i, [_i, _i, _vp, _i, _pi, _pi, _vp]),

@@ -3,8 +3,10 @@
 // slots and its way out (api_frame.hip) - and the arena of the kernel-size search (api_auto.hip).
 #pragma once
 #include "common.hpp"
+#include "k_prior.hpp"
 
 #include <cstddef>
+#include <cstring>
 
 static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -21,6 +23,17 @@ int check_frame_width(km_ctx *c, const char *who, const char *what, int W);   //
 int check_capacity(km_ctx *c, const km_klt_params *prm, int cap);
 // a user mask as the kernels index it - dense rows: the mask itself, or the box of a larger resident mask packed into WS_MASK (1 B/px copy)
 int dense_mask(km_ctx *c, const uint8_t *d_mask, ptrdiff_t smask, int H, int W, const uint8_t **dense);
+// the arguments of the corner mask under a prior (k_prior.hpp) for one box: the tile call's, and every unit's of a batch under priors
+static inline void fill_mask_args(kp_mask_args &a, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,
+                                  const uint8_t *d_base, ptrdiff_t sbase, const double *nodata_ref, const double *nodata_mon, const double *prior,
+                                  double x_off, double y_off, uint8_t *d_mask)
+{
+    a.ref = d_ref; a.mon = d_mon; a.dtype = dtype; a.H = H; a.W = W; a.sref = sref; a.smon = smon; a.base = d_base; a.sbase = sbase;
+    a.has_nd_ref = nodata_ref != nullptr; a.nd_ref = nodata_ref ? *nodata_ref : 0.0;
+    a.has_nd_mon = nodata_mon != nullptr; a.nd_mon = nodata_mon ? *nodata_mon : 0.0;
+    memcpy(a.P, prior, sizeof a.P);
+    a.x_off = x_off; a.y_off = y_off; a.mask = d_mask;
+}
 static inline int corner_limit(const km_klt_params *prm, int cap) { return prm->max_corners > 0 && prm->max_corners < cap ? prm->max_corners : cap; }
 // the corner part of a scalar block back to zero; the min / max and the valid-pixel count in front of it stay
 static inline int clear_corner_scalars(km_ctx *c, km_scalars *sc)

@@ -552,16 +552,6 @@ static bool prior_tracker_covers(const km_ctx *c, int H, int W, int win, int max
     return c->opt_lk2 && max_level == 1 && win > 2 && win <= 40 && (W + 1) / 2 > win && (H + 1) / 2 > win;
 }
 
-static void fill_mask_args(kp_mask_args &a, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon, const uint8_t *d_base,
-                           ptrdiff_t sbase, const double *nodata_ref, const double *nodata_mon, const double *prior, double x_off, double y_off, uint8_t *d_mask)
-{
-    a.ref = d_ref; a.mon = d_mon; a.dtype = dtype; a.H = H; a.W = W; a.sref = sref; a.smon = smon; a.base = d_base; a.sbase = sbase;
-    a.has_nd_ref = nodata_ref != nullptr; a.nd_ref = nodata_ref ? *nodata_ref : 0.0;
-    a.has_nd_mon = nodata_mon != nullptr; a.nd_mon = nodata_mon ? *nodata_mon : 0.0;
-    memcpy(a.P, prior, sizeof a.P);
-    a.x_off = x_off; a.y_off = y_off; a.mask = d_mask;
-}
-
 // prior != nullptr (km_klt_tile_frame_prior_dev): the corner mask is the prior's (k_prior.hip, taken by the
 // pre-filter as a user mask) and the tracker starts every key point at its guess; everything else is the unseeded call's
 static int tile_frame_impl(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int H, int W, ptrdiff_t sref, ptrdiff_t smon,

@@ -13,7 +13,9 @@
 // the unit's own rasters, scalar block, key buffer and grid.  A unit the fixed capacities of the synchronisation-free corner path do
 // not fit is flagged in its block's header (word 2) and repeated exactly by the caller, as for km_klt_tile_frame_submit.
 #include "api_internal.hpp"
+#include "k_prior.hpp"
 
+#include <cmath>
 #include <cstring>
 
 // ---- software pipeline over consecutive submissions ("units_pipeline" 1; karios_amd.stream.FrameStream switches it on)
@@ -36,6 +38,7 @@ struct km_units_tail {
     km_klt_params prm;
     int n = 0, n_max = 0, cap = 0, dtype = 0;
     bool with_zncc = false, with_mi = false, with_clip = false, piped = false, profile_skip = false;
+    bool seeded = false;                  // its LK is the seeded family's, on the seeds beside its own lane's table (km_klt_units_frame_prior_submit)
     double zncc_threshold = 0.0;
     km_frame_layout L;
     char *d_out = nullptr;
@@ -70,7 +73,7 @@ static int units_tail(km_ctx *c, km_units_tail &T)
     {
         km_stage_timer t(c, ST_LK);
         if (!T.piped && (rc = mark_lk_start(c))) return rc;          // (unpipelined: the next submission's early min / max starts here)
-        if ((rc = kl_units_launch(c, n, T.n_max, T.prm.win_size))) return rc;
+        if ((rc = T.seeded ? kl_units_launch_seeded(c, n, T.n_max, T.prm.win_size) : kl_units_launch(c, n, T.n_max, T.prm.win_size))) return rc;
     }
     if (T.piped && ((rc = km_record(c, ev[EV_K_DONE], main_stream)) || (rc = km_wait(c, c->chain_stream, ev[EV_K_DONE])))) return rc;
     km_on_stream on(c, T.piped ? c->chain_stream : main_stream);
@@ -188,6 +191,23 @@ static int units_check_args(km_ctx *c, const km_unit *units, int n, int dtype, c
     return KM_OK;
 }
 
+// ... and of a submission under priors (km_klt_units_frame_prior_submit), in the same position: a refused call has queued nothing
+static int units_check_priors(km_ctx *c, const km_unit *units, int n, const double *priors)
+{
+    if (!priors) return km_fail(c, KM_E_ARG, "klt_units_frame_prior_submit: null priors");
+    for (int u = 0; u < n; u++)
+        for (int i = 0; i < 9; i++)
+            if (!std::isfinite(priors[9 * u + i])) return km_fail(c, KM_E_ARG, "klt_units_frame_prior_submit: unit %d: prior[%d] is not finite", u, i);
+    if (c->opt_frame_clip)
+        return km_fail(c, KM_E_UNSUPPORTED, "klt_units_frame_prior_submit: \"frame_clip\" is on (the clip under a prior runs on the residuals, behind the frame)");
+    for (int u = 0; u < n; u++)
+        if (units[u].win_H != 0) return km_fail(c, KM_E_UNSUPPORTED, "klt_units_frame_prior_submit: unit %d carries an image window", u);
+    return KM_OK;
+}
+
+static int units_submit(km_ctx *c, const km_unit *units, int n, int dtype, const double *nodata_ref, const double *nodata_mon, const km_klt_params *prm,
+                        double zncc_threshold, int cap, const double *priors, int *ticket);
+
 extern "C" {
 
 // Enqueue whatever a pipelined batched submission deferred (include/karios_hip.h).  The submitting thread calls it when no further
@@ -203,8 +223,29 @@ int km_frame_flush(km_ctx *c, int ticket)
 int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype, const double *nodata_ref, const double *nodata_mon,
                               const km_klt_params *prm, double zncc_threshold, int cap, int *ticket)
 {
+    return units_submit(c, units, n, dtype, nodata_ref, nodata_mon, prm, zncc_threshold, cap, nullptr, ticket);
+}
+
+// The batched submission under a geometric prior per unit: block u is the block km_klt_tile_frame_prior_dev writes for
+// unit u alone under priors + 9 u.  Two things differ from the unseeded submission: the corner mask of every unit is the prior's (one
+// launch in front of the Laplacian pass, which takes it as the unit's user mask), and LK is the seeded family on the seeds that travel
+// with the lane's table.
+int km_klt_units_frame_prior_submit(km_ctx *c, const km_unit *units, int n, int dtype, const double *nodata_ref, const double *nodata_mon,
+                                    const km_klt_params *prm, double zncc_threshold, int cap, const double *priors, int *ticket)
+{
     int rc;
-    if ((rc = units_check_args(c, units, n, dtype, prm, cap, ticket))) return rc;
+    if ((rc = units_check_args(c, units, n, dtype, prm, cap, ticket)) || (rc = units_check_priors(c, units, n, priors))) return rc;
+    return units_submit(c, units, n, dtype, nodata_ref, nodata_mon, prm, zncc_threshold, cap, priors, ticket);
+}
+
+}  // extern "C"
+
+// priors == nullptr: km_klt_units_frame_submit
+static int units_submit(km_ctx *c, const km_unit *units, int n, int dtype, const double *nodata_ref, const double *nodata_mon, const km_klt_params *prm,
+                        double zncc_threshold, int cap, const double *priors, int *ticket)
+{
+    int rc;
+    if (!priors && (rc = units_check_args(c, units, n, dtype, prm, cap, ticket))) return rc;
     const bool with_zncc = units[0].d_ref_full != nullptr;
     const bool user_mask = units[0].d_mask != nullptr;
     const bool with_mi = with_zncc && c->opt_frame_mi;
@@ -292,7 +333,8 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     const bool setup_on_aux = piped && dtype != KM_U8;
     auto setup = [&]() -> int {
         KM_HIP(c, hipMemsetAsync(sc, 0, sc_stride * n, c->stream));
-        return kl_units_prepare(c, U, n_max, prm->win_size, prm->max_count, prm->epsilon);
+        return priors ? kl_units_prepare_seeded(c, U, priors, n_max, prm->win_size, prm->max_count, prm->epsilon)
+                      : kl_units_prepare(c, U, n_max, prm->win_size, prm->max_count, prm->epsilon);
     };
     if (!setup_on_aux) {
         if ((rc = wait_lane_done(c, lane, c->stream)) || (rc = wait_lane_done(c, lane, c->aux_stream))) return rc;
@@ -330,6 +372,22 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
             km_stage_timer t(c, ST_MINMAX);
             if ((rc = kd_minmax_units(c, U, out, WS_PARTIAL))) return rc;
         }
+    }
+    // ---- under priors: every unit's corner mask (k_prior.hip), on the main stream directly in front of the pass that takes it.  It is
+    // written into the unit's slice of the lane's WS_MASK and handed on as the unit's user mask IN PLACE (stride W), as the tile call does:
+    // the pack kernel of the Laplacian pass reads and writes a byte in the same thread (k_lap.hip mask_pack_units_kernel), so source ==
+    // destination is a copy onto itself.  (That kernel declares both pointers __restrict__, which source == destination does not honour
+    // to the letter: what keeps it sound is that no thread reads a byte another thread - or an earlier iteration of its own - wrote, so
+    // no reordering the qualifier permits can change a value; the qualifiers stay, for the kernel's code is the parent's.)  Stream order: whatever ordered that pass's writes of the lane's mask orders these.
+    if (priors) {
+        kp_mask_units M;
+        M.n = n;
+        for (int u = 0; u < n; u++)
+            fill_mask_args(M.a[u], U.ref[u], U.mon[u], dtype, U.H[u], U.W[u], U.sref[u], U.smon[u], U.user_mask[u], U.user_smask[u], nodata_ref, nodata_mon,
+                           priors + 9 * u, (double)U.x_off[u], (double)U.y_off[u], U.mask[u]);
+        if ((rc = kp_prior_mask_units(c, M))) return rc;
+        for (int u = 0; u < n; u++) { U.user_mask[u] = U.mask[u]; U.user_smask[u] = U.W[u]; }
+        U.has_user_mask = true;
     }
     // ---- K2: stretch + Laplacians + automatic mask
     km_valid_units vjob;
@@ -381,7 +439,7 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     km_units_tail &T = *c->utail;
     T.lane = lane; T.slot = k; T.U = U; T.prm = *prm; T.n = n; T.n_max = n_max; T.cap = cap; T.dtype = dtype;
     T.with_zncc = with_zncc; T.with_mi = with_mi; T.with_clip = with_clip; T.piped = piped; T.zncc_threshold = zncc_threshold; T.profile_skip = c->profile_skip;
-    T.L = L; T.d_out = d_out;
+    T.L = L; T.d_out = d_out; T.seeded = priors != nullptr;
     T.sink = c->frame_sink; T.sink_pitch = c->frame_sink_pitch;
     slot->sunk_valid = false;
     if (piped) {
@@ -392,5 +450,3 @@ int km_klt_units_frame_submit(km_ctx *c, const km_unit *units, int n, int dtype,
     frame_slot_commit(c, k, ticket);
     return KM_OK;
 }
-
-}  // extern "C"

@@ -752,6 +752,18 @@ int kd_pyrdown_units(km_ctx *c, const km_units &U, int level);
 int kf_rank_select_units(km_ctx *c, const km_units &U, int max_corners, double quality, double min_distance, int cap);
 int kl_units_prepare(km_ctx *c, const km_units &U, int n_max, int win, int max_count, double epsilon);
 int kl_units_launch(km_ctx *c, int n_units, int n_max, int win);
+// ... every unit under a prior of its own (`priors`: U.n x 9 doubles, unit order; km_klt_units_frame_prior_submit): the seeds travel with
+// the lane's table.  A compiler that is not hipcc has no tracker: the stand-ins of the unseeded pair stand in for these as well
+#if defined(__HIPCC__)
+int kl_units_prepare_seeded(km_ctx *c, const km_units &U, const double *priors, int n_max, int win, int max_count, double epsilon);
+int kl_units_launch_seeded(km_ctx *c, int n_units, int n_max, int win);
+#else
+static inline int kl_units_prepare_seeded(km_ctx *c, const km_units &U, const double *, int n_max, int win, int max_count, double epsilon)
+{
+    return kl_units_prepare(c, U, n_max, win, max_count, epsilon);
+}
+static inline int kl_units_launch_seeded(km_ctx *c, int n_units, int n_max, int win) { return kl_units_launch(c, n_units, n_max, win); }
+#endif
 int kf_frame_units(km_ctx *c, const km_units &U, int n_max, int cap, float back_thr);
 int kz_zncc_units(km_ctx *c, const km_score_units &A, int n_units, int dtype, int n, float score_thr);
 int kmi_units(km_ctx *c, const km_score_units &A, int n_units, int dtype, int n, float score_thr);

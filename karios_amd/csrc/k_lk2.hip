@@ -16,6 +16,9 @@
 #include "lk_launch.hpp"
 #include "k_prior.hpp"
 
+#include <cstddef>
+#include <cstring>
+
 #define LK2_M 3                       // margin (px) of a patch around the window it was centred on
 #define LK2_INVALID (-(1 << 28))      // origin of a patch that holds nothing yet
 
@@ -342,15 +345,24 @@ __device__ __forceinline__ void lk2_stage_all(const lk_args &g, const lk2_geo<WI
 
 // Forward pass from (gx, gy) - the key point itself where nothing seeds the search -, p1 stored; backward pass from p1 - (g - p0), p0r
 // stored.  The backward pass never reads p0 itself; its search patch is the forward template's, re-centred if p1 moved away.
-template <int NR, int WIN, int MAXIT, bool SEEDED>
+// UNIFORM_SHIFT (the batched seeded kernels): g - p0, the same in every lane, is taken in front of the forward pass and waits for the
+// backward pass in scalar registers - the unit's arguments come through the table pointer there, and the guess's two vector registers,
+// live across the forward pass, were the ones the win-25 instance had to spill.
+template <int NR, int WIN, int MAXIT, bool SEEDED, bool UNIFORM_SHIFT = false>
 __device__ __forceinline__ void lk2_both_passes(const lk_args &g, int p, float px, float py, float gx, float gy, const lk2_geo<WIN> &geo,
                                                 const int (&run_desc)[NR], uint8_t *pA, uint8_t *pB, int (&oA)[2][2], int (&oB)[2][2])
 {
+    float sx = 0.f, sy = 0.f;
+    if constexpr (UNIFORM_SHIFT) {
+        int isx = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, gx - px)), isy = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, gy - py));
+        asm volatile("" : "+s"(isx), "+s"(isy));      // (HERE, in scalar registers: left alone the compiler sinks both behind the forward pass)
+        sx = __builtin_bit_cast(float, isx); sy = __builtin_bit_cast(float, isy);
+    }
     float fx = gx, fy = gy;
     lk2_track_point<NR, WIN, MAXIT, SEEDED>(g.A, g.B, pA, pB, oA, oB, px, py, geo, g.max_count, g.epsilon, run_desc, fx, fy, g.general_templates, g.lk_reuse);
     if ((threadIdx.x & 63) == 0) { g.p1[2 * p] = fx; g.p1[2 * p + 1] = fy; }
     if (g.backward) {
-        const float sx = gx - px, sy = gy - py;
+        if constexpr (!UNIFORM_SHIFT) { sx = gx - px; sy = gy - py; }
         float rx = fx - sx, ry = fy - sy;
         lk2_track_point<NR, WIN, MAXIT, SEEDED>(g.B, g.A, pB, pA, oB, oA, fx, fy, geo, g.max_count, g.epsilon, run_desc, rx, ry, g.general_templates, g.lk_reuse);
         if ((threadIdx.x & 63) == 0) { g.p0r[2 * p] = rx; g.p0r[2 * p + 1] = ry; }
@@ -398,7 +410,7 @@ __device__ __forceinline__ void lk2_body(const lk_args &g, const int *__restrict
 // k_prior.hip keeps such pixels from becoming corners).  The A patches are staged around the key point's window, the B patches around the
 // GUESS's window - the search's first position.  A level whose template lies outside the first image is skipped by the tracker (nothing to
 // stage in either image); a guess window the iteration loop would leave at once (inx < -win or >= W, likewise y) stages nothing in B.
-template <int NR, int WIN, int MAXIT>
+template <int NR, int WIN, int MAXIT, bool UNITS = false>
 __device__ __forceinline__ void lk2_seeded_body(const lk_args &g, const kl_seed &seed)
 {
     const int n = __builtin_amdgcn_readfirstlane(g.d_n ? min(*g.d_n, g.n_max) : g.n_max);      // (as lk2_body)
@@ -434,10 +446,10 @@ __device__ __forceinline__ void lk2_seeded_body(const lk_args &g, const kl_seed 
                  lk_patch_inside(g.B.W[l], g.B.H[l], oB[l][0], oB[l][1], PS, PS, MAXIT);
     }
     lk2_stage_all<MAXIT>(g, geo, oA, oB, wantA, wantB, inside, pA, pB);
-    lk2_both_passes<NR, WIN, MAXIT, true>(g, p, px, py, gx, gy, geo, run_desc, pA, pB, oA, oB);
+    lk2_both_passes<NR, WIN, MAXIT, true, UNITS>(g, p, px, py, gx, gy, geo, run_desc, pA, pB, oA, oB);
 }
 
-// ---- the kernels: three families (plain, seeded, batched units), each with one instance per NR class and one for the reference's
+// ---- the kernels: four families (plain, seeded, batched units, batched units under priors), each with one instance per NR class and one for the reference's
 // window (matching_winsize 25, processing_configuration.json:14) with every size a compile-time constant, pinned to 5 waves per SIMD
 #ifndef LK2_25_WAVES
 #define LK2_25_WAVES 5
@@ -462,11 +474,24 @@ __global__ __launch_bounds__(64) LK2_25_OCC void lk2_seeded_kernel_win25(lk_args
 template <int NR, int WIN, int MAXIT>
 __global__ __launch_bounds__(64) KM_LK_OCC void lk2_units_kernel(const lk_args *__restrict__ table) { lk2_body<NR, WIN, MAXIT>(table[blockIdx.y], nullptr); }
 __global__ __launch_bounds__(64) LK2_25_OCC void lk2_units_kernel_win25(const lk_args *__restrict__ table) { lk2_body<2, 25, 4>(table[blockIdx.y], nullptr); }
+// batched units under a prior each (km_klt_units_frame_prior_submit): the seeded body on unit blockIdx.y's arguments and seed.  Both
+// tables are read at an index that is the same in every lane, through pointers nothing else writes: scalar loads, and the seed stays in
+// scalar registers as the prologue of lk2_seeded_body assumes
+template <int NR, int WIN, int MAXIT>
+__global__ __launch_bounds__(64) KM_LK_OCC void lk2_seeded_units_kernel(const lk_args *__restrict__ table, const kl_seed *__restrict__ seeds)
+{
+    lk2_seeded_body<NR, WIN, MAXIT, true>(table[blockIdx.y], seeds[blockIdx.y]);
+}
+__global__ __launch_bounds__(64) LK2_25_OCC void lk2_seeded_units_kernel_win25(const lk_args *__restrict__ table, const kl_seed *__restrict__ seeds)
+{
+    lk2_seeded_body<2, 25, 4, true>(table[blockIdx.y], seeds[blockIdx.y]);
+}
 
 // ---- launches.  A family names its instances; lk2_launch picks the one lk_shape_of(win) says.
 struct lk2_plain { static constexpr auto win25 = lk2_kernel_win25; template <int NR, int MAXIT> static constexpr auto generic = lk2_kernel<NR, 0, MAXIT>; };
 struct lk2_seeded { static constexpr auto win25 = lk2_seeded_kernel_win25; template <int NR, int MAXIT> static constexpr auto generic = lk2_seeded_kernel<NR, 0, MAXIT>; };
 struct lk2_units { static constexpr auto win25 = lk2_units_kernel_win25; template <int NR, int MAXIT> static constexpr auto generic = lk2_units_kernel<NR, 0, MAXIT>; };
+struct lk2_seeded_units { static constexpr auto win25 = lk2_seeded_units_kernel_win25; template <int NR, int MAXIT> static constexpr auto generic = lk2_seeded_units_kernel<NR, 0, MAXIT>; };
 
 template <class F, class... Args>
 static int lk2_launch(km_ctx *c, dim3 grid, int win, const Args &...args)
@@ -501,37 +526,73 @@ int kl_track_seeded(km_ctx *c, const km_pyr &A, const km_pyr &B, const float *d_
     return lk2_launch<lk2_seeded>(c, km_xcd_grid((unsigned)n_max), win, g, seed);
 }
 
-// The argument table of n forward + backward runs (units of a batch, jobs of the kernel-size search), uploaded into WS_UNITS_LK on c->stream:
-// `entry(i, g)` sets pyramids, points and outputs of run i.  KM_E_UNSUPPORTED (no message): a run this form does not serve - kl_track run by run.
+// The argument table of n forward + backward runs (units of a batch, jobs of the kernel-size search): `entry(i, g)` sets pyramids, points
+// and outputs of run i.  KM_E_UNSUPPORTED (no message): a run this form does not serve - kl_track run by run.
 template <class Entry>
-static int lk2_upload_table(km_ctx *c, int n, int capacity, int n_max, int win, int max_count, double epsilon, Entry entry)
+static int lk2_fill_table(km_ctx *c, lk_args *host, int n, int n_max, int win, int max_count, double epsilon, Entry entry)
 {
-    lk_args host[KM_LK_JOBS_MAX > KM_UNITS_MAX ? KM_LK_JOBS_MAX : KM_UNITS_MAX];
     const lk_args shared = lk_fill_args(c, km_pyr(), km_pyr(), nullptr, nullptr, n_max, win, max_count, epsilon, true, nullptr, nullptr, nullptr);
     for (int i = 0; i < n; i++) {
         host[i] = shared;
         entry(i, host[i]);
         if (!lk2_serves(c, host[i].A, host[i].B)) return KM_E_UNSUPPORTED;
     }
+    return KM_OK;
+}
+// ... uploaded into WS_UNITS_LK on c->stream
+template <class Entry>
+static int lk2_upload_table(km_ctx *c, int n, int capacity, int n_max, int win, int max_count, double epsilon, Entry entry)
+{
+    lk_args host[KM_LK_JOBS_MAX > KM_UNITS_MAX ? KM_LK_JOBS_MAX : KM_UNITS_MAX];
+    if (const int rc = lk2_fill_table(c, host, n, n_max, win, max_count, epsilon, entry)) return rc;
     lk_args *table = (lk_args *)km_ws(c, WS_UNITS_LK, sizeof(lk_args) * (size_t)capacity);
     if (!table) return KM_E_NOMEM;
     return km_h2d_small(c, table, host, sizeof(lk_args) * (size_t)n);
 }
 
 // kl_units_prepare: validate + upload the table (early in the call: the small copy is then off the critical path); kl_units_launch: the launch
+static void lk2_unit_entry(const km_units &U, int u, lk_args &g)
+{
+    g.A = U.A[u]; g.B = U.B[u]; g.pts_in = U.p0[u]; g.d_n = &U.sc[u]->n_corners; g.p1 = U.p1[u]; g.p0r = U.p0r[u];
+}
 int kl_units_prepare(km_ctx *c, const km_units &U, int n_max, int win, int max_count, double epsilon)
 {
     if (n_max <= 0 || U.n <= 0) return KM_OK;
     { const int rc = lk_check_window(c, win); if (rc) return rc; }
-    return lk2_upload_table(c, U.n, KM_UNITS_MAX, n_max, win, max_count, epsilon, [&](int u, lk_args &g) {
-        g.A = U.A[u]; g.B = U.B[u]; g.pts_in = U.p0[u]; g.d_n = &U.sc[u]->n_corners; g.p1 = U.p1[u]; g.p0r = U.p0r[u];
-    });
+    return lk2_upload_table(c, U.n, KM_UNITS_MAX, n_max, win, max_count, epsilon, [&](int u, lk_args &g) { lk2_unit_entry(U, u, g); });
 }
 int kl_units_launch(km_ctx *c, int n_units, int n_max, int win)
 {
     if (n_max <= 0 || n_units <= 0) return KM_OK;
     const lk_args *table = (const lk_args *)km_ws_peek(c, WS_UNITS_LK);
     return lk2_launch<lk2_units>(c, dim3(km_xcd_grid((unsigned)n_max), n_units), win, table);
+}
+
+// ... under a prior per unit (`priors`: U.n x 9, unit order; the origin is the unit's).  The seeds lie behind the table's KM_UNITS_MAX
+// entries in the same slot and travel in the SAME small copy: whatever orders the table for the launch orders the seeds
+struct lk2_seeded_table {
+    lk_args args[KM_UNITS_MAX];
+    kl_seed seeds[KM_UNITS_MAX];
+};
+int kl_units_prepare_seeded(km_ctx *c, const km_units &U, const double *priors, int n_max, int win, int max_count, double epsilon)
+{
+    if (n_max <= 0 || U.n <= 0) return KM_OK;
+    { const int rc = lk_check_window(c, win); if (rc) return rc; }
+    lk2_seeded_table host = {};
+    if (const int rc = lk2_fill_table(c, host.args, U.n, n_max, win, max_count, epsilon, [&](int u, lk_args &g) { lk2_unit_entry(U, u, g); })) return rc;
+    for (int u = 0; u < U.n; u++) {
+        kl_seed &s = host.seeds[u];
+        s.guess = nullptr; memcpy(s.P, priors + 9 * u, sizeof s.P); s.x_off = (double)U.x_off[u]; s.y_off = (double)U.y_off[u];
+    }
+    lk2_seeded_table *table = (lk2_seeded_table *)km_ws(c, WS_UNITS_LK, sizeof(lk2_seeded_table));
+    if (!table) return KM_E_NOMEM;
+    return km_h2d_small(c, table, &host, offsetof(lk2_seeded_table, seeds) + sizeof(kl_seed) * (size_t)U.n);
+}
+int kl_units_launch_seeded(km_ctx *c, int n_units, int n_max, int win)
+{
+    if (n_max <= 0 || n_units <= 0) return KM_OK;
+    const lk2_seeded_table *table = (const lk2_seeded_table *)km_ws_peek(c, WS_UNITS_LK);
+    return lk2_launch<lk2_seeded_units>(c, dim3(km_xcd_grid((unsigned)n_max), n_units), win, table->args, table->seeds);
 }
 
 // Independent tracker runs in ONE launch (unit = blockIdx.y): the 25 (mon kernel, ref kernel) runs of the Laplacian kernel-size search (klt.py:465-545),

@@ -28,6 +28,15 @@ struct kp_mask_args {
 // every byte of the mask is written exactly once; KM_E_ARG: a pixel type the kernel does not read
 int kp_prior_mask(km_ctx *c, const kp_mask_args &a);
 
+// the masks of a batched submission's units (api_units.hip: km_klt_units_frame_prior_submit) in ONE launch: every unit its own boxes,
+// base, prior, origin and output; one pixel type.  The table travels by value in the kernel arguments (16 entries: 3 KB of the 4)
+#define KP_MASK_UNITS_MAX 16
+struct kp_mask_units {
+    int n;
+    kp_mask_args a[KP_MASK_UNITS_MAX];
+};
+int kp_prior_mask_units(km_ctx *c, const kp_mask_units &A);
+
 // the start positions of a seeded track: explicit guesses (n x 2 float32, device memory), or the prior evaluated per key point
 struct kl_seed {
     const float *guess;                // nullptr: from P
@@ -58,5 +67,12 @@ inline int kp_prior_mask(km_ctx *, const kp_mask_args &a)
     case KM_F32: kp_prior_mask_host<float>(a); return KM_OK;
     default: return KM_E_ARG;
     }
+}
+
+inline int kp_prior_mask_units(km_ctx *c, const kp_mask_units &A)
+{
+    for (int u = 0; u < A.n; u++)
+        if (const int rc = kp_prior_mask(c, A.a[u])) return rc;
+    return KM_OK;
 }
 #endif

@@ -248,6 +248,20 @@ class KLT:
             raise KariosHipError("KLT.match: the Laplacian kernel-size search takes no prior; give laplacian_kernel_size")
         ksizes = tiling.kernel_sizes(self._conf.laplacian_kernel_size)
         mode = self._conf.laplacian_invert_polarity
+        if mode != "auto" and not self._gen_laplacian and self._rasters_in_hbm(mon_img, ref_img, mask):
+            # rasters in HBM, fixed kernel size and polarity: the grid as batched submissions under the prior, frames
+            # in tile order - what the loop below yields tile by tile
+            grid = self.tile_boxes(mon_img.x_size, mon_img.y_size)
+            pair = self._whole_pair(mon_img, ref_img, mask)
+            for tile, frame in zip(grid, pair.match_pipelined(self._conf, boxes=[tuple(t) for t in grid], with_empty=True, prior=prior)):
+                if frame is None:
+                    logger.info("tile (%d, %d): no valid pixels or no corners - skipped", tile[0], tile[1])
+                    continue
+                n_init = int(frame.attrs.pop("Ninit", len(frame)))
+                frame.attrs.clear()
+                logger.info("tile (%d, %d): %d of %d corners kept under the prior", tile[0], tile[1], len(frame), n_init)
+                yield frame
+            return
         for tile in self.tile_boxes(mon_img.x_size, mon_img.y_size):
             session = self._open(tile, mon_img, ref_img, mask)
             trials = [t for t in (session.fixed(ksizes, inv, prior=prior) for inv in ((False, True) if mode == "auto" else (bool(mode),))) if t is not None]
@@ -307,12 +321,7 @@ class KLT:
     def _match_resident(self, grid, mon_img, ref_img, mask) -> Iterator[DataFrame]:
         """`match` on resident rasters: every tile of the grid is a box of the pair (pointer + stride), submitted through
         `karios_amd.stream.FrameStream` - tile i + 1 runs on the device while tile i becomes its DataFrame; frames in tile order."""
-        import torch
-        torch.cuda.synchronize(mon_img.tensor.device)               # the library works on its own streams
-        pair = ResidentPair.from_device_pointers(mon_img.tensor.data_ptr(), ref_img.tensor.data_ptr(), mon_img.dtype, mon_img.y_size, mon_img.x_size,
-                                                 ctx=self._ctx, mask_ptr=None if mask is None else mask.tensor.data_ptr(),
-                                                 no_data_mon=getattr(mon_img, "no_data_value", None), no_data_ref=getattr(ref_img, "no_data_value", None),
-                                                 keepalive=(mon_img.tensor, ref_img.tensor, None if mask is None else mask.tensor))
+        pair = self._whole_pair(mon_img, ref_img, mask)
         for tile, frame in zip(grid, pair.match_pipelined(self._conf, boxes=[tuple(t) for t in grid], with_empty=True)):
             if frame is None:
                 logger.info("tile (%d, %d): no valid pixels or no corners - skipped", tile[0], tile[1])
@@ -321,6 +330,15 @@ class KLT:
             frame.attrs.clear()
             logger.info("tile (%d, %d): %d of %d corners kept", tile[0], tile[1], len(frame), n_init)
             yield frame
+
+    def _whole_pair(self, mon_img, ref_img, mask) -> ResidentPair:
+        """The rasters in HBM as one pair (pointers + strides); a tile is a box of it."""
+        import torch
+        torch.cuda.synchronize(mon_img.tensor.device)               # the library works on its own streams
+        return ResidentPair.from_device_pointers(mon_img.tensor.data_ptr(), ref_img.tensor.data_ptr(), mon_img.dtype, mon_img.y_size, mon_img.x_size,
+                                                 ctx=self._ctx, mask_ptr=None if mask is None else mask.tensor.data_ptr(),
+                                                 no_data_mon=getattr(mon_img, "no_data_value", None), no_data_ref=getattr(ref_img, "no_data_value", None),
+                                                 keepalive=(mon_img.tensor, ref_img.tensor, None if mask is None else mask.tensor))
 
     # ------------------------------------------------------------------ one tile
     def _match_tile(self, x_off, y_off, mon_img, ref_img, mask) -> DataFrame | None:

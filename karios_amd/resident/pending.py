@@ -1,4 +1,5 @@
-"""Frame blocks and the tickets of submitted tiles: `RawFrame`, `PendingFrame`, `PendingBatch`."""
+"""Frame blocks and the tickets of submitted tiles: `RawFrame`, `PendingFrame`, `PendingBatch`; `PriorSteps`, the host half of a frame
+tracked under a geometric prior."""
 from __future__ import annotations
 
 import ctypes as C
@@ -37,6 +38,21 @@ class RawFrame:
     def to_frame(self, radial: bool = False) -> DataFrame | None:
         """The tile's DataFrame; `radial`: with the `radial error` / `angle` columns of `score_frame` already in place."""
         return frames.block_to_frame(self.block, self.cap, self.with_zncc, radial, own=True)   # (the block is this frame's private copy)
+
+
+class PriorSteps:
+    """What the host adds to a frame that was tracked under a prior (`ResidentPair.match_tile(prior=)`, `submit_units(priors=)`): the
+    `dx_prior, dy_prior` columns of the prior at the unit's origin and - `clip`: with `conf.outliers_filtering` - the outlier clip on the
+    residuals.  `apply` makes a library call when it clips: submitting thread only."""
+    __slots__ = ("P", "x_off", "y_off", "clip")
+
+    def __init__(self, P, x_off, y_off, clip: bool):
+        self.P, self.x_off, self.y_off, self.clip = P, x_off, y_off, bool(clip)
+
+    def apply(self, frame: DataFrame, ctx=None) -> DataFrame:
+        from ..matcher import prior as _prior
+        frame["dx_prior"], frame["dy_prior"] = _prior.prior_columns(frame, self.P, self.x_off, self.y_off)
+        return _prior.clip_residuals(frame, ctx=ctx) if self.clip else frame
 
 
 class _Ticket:
@@ -97,11 +113,14 @@ class PendingFrame(_Ticket):
 
 class PendingBatch(_Ticket):
     """Units submitted together with `submit_units` (km_klt_units_frame_submit): ONE device pipeline for all of them.
-    `wait()` (any thread) -> the units' `RawFrame`s in submission order; `redo(i)` repeats unit i alone through the exact path."""
+    `wait()` (any thread) -> the units' `RawFrame`s in submission order; `redo(i)` repeats unit i alone through the exact path - under
+    its prior when the batch was submitted with priors (km_klt_units_frame_prior_submit); `frame(i)` is then unit i's DataFrame with
+    `dx_prior, dy_prior`, clipped on the residuals."""
 
-    def __init__(self, ctx: Context, ticket: int, cap: int, with_zncc: int, redos):
+    def __init__(self, ctx: Context, ticket: int, cap: int, with_zncc: int, redos, prior_steps=None):
         super().__init__(ctx, ticket, cap, with_zncc)
         self._redos = redos
+        self.prior_steps = prior_steps          # a submission under priors: unit i's `PriorSteps`; None otherwise
         self._raws = None
         self._submitter = threading.get_ident()
 
@@ -120,3 +139,13 @@ class PendingBatch(_Ticket):
         """Unit i through the exact (synchronising) corner path (submitting thread only)."""
         self._raws[i] = self._redos[i]()
         return self._raws[i]
+
+    def frame(self, i: int) -> DataFrame | None:
+        """Unit i's DataFrame (submitting thread): `wait`, the repeat of a flagged unit, and the host half of its prior, if any."""
+        raw = self.wait()[i]
+        if raw.flags:
+            raw = self.redo(i)
+        frame = raw.to_frame()
+        if frame is not None and self.prior_steps is not None:
+            frame = self.prior_steps[i].apply(frame, self.ctx)
+        return frame

@@ -15,7 +15,7 @@ from .._lib import KariosHipError
 from ..ops import make_params
 from .buffers import DeviceBuffer
 from .calls import Scope, clips, frame_capacity, no_data_pointers, score_columns
-from .pending import PendingBatch, PendingFrame, RawFrame
+from .pending import PendingBatch, PendingFrame, PriorSteps, RawFrame
 
 
 def _origin(origin, box):
@@ -160,10 +160,22 @@ class TileCalls:
         host the two prior columns and - with `conf.outliers_filtering` - the clip of the residuals through `ops.sigma_clip`, in corner
         order as the tracker's own clip runs (the device call keeps "frame_clip" off: that stage clips dx, dy themselves)."""
         from ..matcher import prior as _prior
+        P = _prior.as_prior(prior)
+        raw = self._prior_tile_raw(conf, box, x_off, y_off, P, zncc_threshold, ksizes, invert_mon, mutual_info)
+        frame = frames.block_to_frame(raw.block, raw.cap, raw.with_zncc)
+        if frame is None:
+            return None
+        frame = PriorSteps(P, x_off, y_off, clips(conf)).apply(frame, self.ctx)
+        frame.attrs["Ninit"] = int(raw.block[:2].view(np.int32)[1])
+        return frame
+
+    def _prior_tile_raw(self, conf, box, x_off, y_off, P, zncc_threshold=None, ksizes=None, invert_mon=None, mutual_info: bool = False) -> "RawFrame":
+        """GPU half of `match_tile(prior=)`: km_klt_tile_frame_prior_dev on a box, the raw block as a private copy.  The call repeats a
+        flagged tile itself, so this is also the repeat of a flagged unit of a batch under priors (`submit_units`); the frame sink is
+        lifted around it as for `_exact_repeat`."""
         c = self.ctx
         if self.window is not None:
             raise KariosHipError("ResidentPair.match_tile: a prior on a windowed pair is not supported")
-        P = _prior.as_prior(prior)
         n_scores = score_columns(zncc_threshold, mutual_info)
         head, whole, bx, by = self._tile_args(box)
         prm = self._params(conf, ksizes, invert_mon)
@@ -171,19 +183,26 @@ class TileCalls:
         buf = np.empty(frames.block_words(cap, 3), np.float32)
         # (without a threshold no row is scored: a score never exceeds 1)
         thr = 2.0 if zncc_threshold is None else float(zncc_threshold)
-        with Scope(c, mi=n_scores == 3):
-            c.check(c.lib.km_klt_tile_frame_prior_dev(*head, C.byref(prm), float(x_off), float(y_off), *whole, thr,
-                                                      P.ctypes.data_as(C.POINTER(C.c_double)), buf.ctypes.data_as(C.c_void_p), cap),
-                    "km_klt_tile_frame_prior_dev")
-        frame = frames.block_to_frame(buf, cap, n_scores)
-        if frame is None:
-            return None
-        n_init = int(buf[:2].view(np.int32)[1])
-        frame["dx_prior"], frame["dy_prior"] = _prior.prior_columns(frame, P, x_off, y_off)
-        if clips(conf):
-            frame = _prior.clip_residuals(frame, ctx=c)
-        frame.attrs["Ninit"] = n_init
-        return frame
+        sink = c.frame_sink
+        if sink[0]:
+            c.set_frame_sink(None)
+        try:
+            with Scope(c, mi=n_scores == 3):
+                c.check(c.lib.km_klt_tile_frame_prior_dev(*head, C.byref(prm), float(x_off), float(y_off), *whole, thr,
+                                                          P.ctypes.data_as(C.POINTER(C.c_double)), buf.ctypes.data_as(C.c_void_p), cap),
+                        "km_klt_tile_frame_prior_dev")
+        finally:
+            if sink[0]:
+                c.set_frame_sink(*sink)
+        return RawFrame(buf[:frames.block_words(cap, n_scores)], cap, n_scores)
+
+    def match_tile_prior_raw(self, conf, box=None, zncc_threshold=None, origin=None, mutual_info: bool = False, prior=None) -> "RawFrame":
+        """`match_tile_raw` under a prior (blocking): the raw block; `PriorSteps` are its host half."""
+        from ..matcher import prior as _prior
+        if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto":
+            raise KariosHipError("ResidentPair.match_tile_prior_raw: 'auto' modes need ResidentPair.match_tile / matcher.KLT")
+        x_off, y_off = _origin(origin, box)
+        return self._prior_tile_raw(conf, box, x_off, y_off, _prior.as_prior(prior), zncc_threshold, mutual_info=mutual_info)
 
     def match_tile_auto_ksize(self, conf, box=None, invert_mon: bool = False, candidates=tiling.AUTO_KSIZE_CANDIDATES, origin=None):
         """The Laplacian kernel-size search of the reference (klt.py:465-545) for one tile of the resident pair in ONE
@@ -275,12 +294,14 @@ class TileCalls:
                                                    C.byref(ticket)), "km_klt_tile_frame_submit")
         return PendingFrame(c, ticket.value, cap, n_scores, redo=partial(self._exact_repeat, conf, box, zncc_threshold, (x_off, y_off), mutual_info))
 
-    def match_pipelined(self, conf, boxes=None, zncc_threshold=None, host_stage=None, with_empty: bool = False, split_small_grids: bool = True):
+    def match_pipelined(self, conf, boxes=None, zncc_threshold=None, host_stage=None, with_empty: bool = False, split_small_grids: bool = True,
+                        prior=None):
         """`match` as a pipeline (`karios_amd.stream.FrameStream`): tile i+1 is submitted to the device (`submit_tile`) while a
         worker thread waits for tile i and builds its DataFrame.  `host_stage(frame)` (e.g. `score_frame`) runs on the CALLING
         thread when the frame is collected: a context is not thread-safe, and a stage that calls back into the library (ZNCC /
         MI of rows the device call did not score) must not run beside `submit_tile`.  Yields the frames in tile order, like
-        `KLT.match`."""
+        `KLT.match`.  `prior` (`karios_amd.matcher.prior`): every tile under it, as `match_tile(prior=)` tile by tile - the batches go
+        through km_klt_units_frame_prior_submit, the frames carry `dx_prior, dy_prior` and are clipped on the residuals."""
         from ..stream import FrameStream
         if boxes is None:
             boxes = tiling.tile_grid(self.x_size, self.y_size, conf.tile_size, conf.xStart)
@@ -293,7 +314,7 @@ class TileCalls:
             units = [(self, box, None) for box in boxes]
             halves = [units[:len(units) // 2], units[len(units) // 2:]] if split_small_grids and 8 <= len(units) <= 16 else [units]
             for part in halves:
-                for done in stream.submit_many(part, conf):
+                for done in stream.submit_many(part, conf, priors=prior):
                     if done.frame is not None or with_empty:          # (with_empty: None for a tile without valid pixels / corners)
                         yield done.frame
             for done in stream.drain():
@@ -308,14 +329,34 @@ class TileCalls:
                 yield frame
 
 
-def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False) -> "PendingBatch | None":
+def _unit_priors(priors, n: int):
+    """None, one prior for all units (nine values: shape (9,) or (3, 3)), or one per unit (a sequence of n such) -> None | n arrays of
+    9 float64 (`matcher.prior.as_prior`).  The shape decides, not the number of values: `[P]` is one prior per unit of a one-unit list."""
+    from ..matcher import prior as _prior
+    if priors is None:
+        return None
+    try:
+        shape = np.shape(priors)
+    except ValueError:                      # (a ragged sequence: 3 x 3 matrices beside flat ones)
+        shape = None
+    if shape in ((9,), (3, 3)):
+        return [_prior.as_prior(priors)] * n
+    if len(priors) != n:
+        raise ValueError(f"priors: {len(priors)} for {n} units")
+    return [_prior.as_prior(p) for p in priors]
+
+
+def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False, priors=None) -> "PendingBatch | None":
     """`ResidentPair.submit_tile` for up to 16 independent units at once - `units` = [(pair, box | None, origin | None), ...], all on
     ONE context, one pixel type, all with a user mask or none: the tiles of `KLT.match` (klt.py:220-253), of one pair or of several bands.  Every
     dense kernel, the corner-selection chain, LK, the frame stage and the scores are launched ONCE for all units
     (csrc/api_units.hip); the frames are the unit-by-unit frames bit for bit.  Returns None when the batch form does not cover the
     case (the library answers KM_E_UNSUPPORTED: maxCorners 0, a unit narrower than 512 columns ...) or the
     units do not share a context / pixel type, or only some carry a user mask - submit them one by one then.  With
-    `conf.outliers_filtering` every unit's frame is clipped on the device (km_set_option "frame_clip") in front of its scores."""
+    `conf.outliers_filtering` every unit's frame is clipped on the device (km_set_option "frame_clip") in front of its scores.
+    `priors` (None, one prior for all units, or one per unit; `karios_amd.matcher.prior`): km_klt_units_frame_prior_submit - every unit is
+    tracked from its guesses as `match_tile(prior=)` tracks it alone, bit for bit; the device clip stays off (the clip under a prior runs
+    on the residuals: `PendingBatch.prior_steps`), a flagged unit is repeated under its prior, and a windowed pair is not covered."""
     if not units or len(units) > _lib.UNITS_PER_SUBMISSION:
         return None
     if conf.laplacian_kernel_size == "auto" or conf.laplacian_invert_polarity == "auto" or conf.maxCorners <= 0:
@@ -329,7 +370,8 @@ def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False) ->
     prm = TileCalls._params(conf)
     cap = prm.max_corners
     arr = (_lib.KmUnit * len(units))()
-    redos = []
+    redos, steps = [], []
+    P = _unit_priors(priors, len(units))
     for k, (pair, box, origin) in enumerate(units):
         bx_off, by_off, bx, by, off = pair._box(box)
         x_off, y_off = origin if origin is not None else (bx_off, by_off)
@@ -343,12 +385,24 @@ def submit_units(units, conf, zncc_threshold=None, mutual_info: bool = False) ->
             u.win_ox, u.win_oy, u.win_H, u.win_W = (int(v) for v in pair.window)
         if pair.mask_ptr:                     # the user mask of the box (klt.py:258-266): a uint8 raster of the pair's shape
             u.d_mask, u.smask = pair.mask_ptr + off, pair.x_size
-        redos.append(partial(pair._exact_repeat, conf, box, zncc_threshold, (x_off, y_off), mutual_info))
+        if P is None:
+            redos.append(partial(pair._exact_repeat, conf, box, zncc_threshold, (x_off, y_off), mutual_info))
+        else:
+            redos.append(partial(pair._prior_tile_raw, conf, box, x_off, y_off, P[k], zncc_threshold, None, None, mutual_info))
+            steps.append(PriorSteps(P[k], x_off, y_off, clips(conf)))
     nr, nm = no_data_pointers(first)
     ticket = C.c_int(-1)
-    with Scope(c, mi=n_scores == 3, clip=clips(conf)):        # (every unit carries its own window)
-        rc = c.lib.km_klt_units_frame_submit(c.handle, arr, len(units), first.code, nr, nm, C.byref(prm), float(zncc_threshold or 0.0), cap, C.byref(ticket))
+    if P is None:
+        with Scope(c, mi=n_scores == 3, clip=clips(conf)):        # (every unit carries its own window)
+            rc = c.lib.km_klt_units_frame_submit(c.handle, arr, len(units), first.code, nr, nm, C.byref(prm), float(zncc_threshold or 0.0), cap, C.byref(ticket))
+        name = "km_klt_units_frame_submit"
+    else:
+        table = np.ascontiguousarray(np.stack(P), np.float64)     # n x 9, unit order
+        with Scope(c, mi=n_scores == 3, clip=False):
+            rc = c.lib.km_klt_units_frame_prior_submit(c.handle, arr, len(units), first.code, nr, nm, C.byref(prm), float(zncc_threshold or 0.0), cap,
+                                                       table.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ticket))
+        name = "km_klt_units_frame_prior_submit"
     if rc == _lib.E_UNSUPPORTED:
         return None
-    c.check(rc, "km_klt_units_frame_submit")
-    return PendingBatch(c, ticket.value, cap, n_scores, redos)
+    c.check(rc, name)
+    return PendingBatch(c, ticket.value, cap, n_scores, redos, steps or None)

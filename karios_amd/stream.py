@@ -20,6 +20,8 @@ from dataclasses import dataclass, field
 from pandas import DataFrame
 
 from .resident import PendingBatch, PendingFrame, RawFrame, ResidentPair, submit_units
+from .resident.calls import clips
+from .resident.pending import PriorSteps
 
 
 # The interpreter's switch interval is process-global: open streams are counted, the original value is saved by the FIRST one
@@ -154,56 +156,71 @@ class FrameStream:
         finally:
             self.worker_cpu_s += time.thread_time() - t_cpu
 
-    def _finish(self, pair, pend, i, raw, frame, tag, spans) -> StreamResult:
+    def _finish(self, pair, pend, i, raw, frame, tag, spans, steps=None) -> StreamResult:
         """Submitting thread: unit `i` of `pend` becomes its result - repeated alone through the exact path when it did not fit the fixed
-        capacities of the synchronisation-free corner path (the others of a batch stand), then the host stage."""
+        capacities of the synchronisation-free corner path (the others of a batch stand), then the host half of its prior (`steps`: the
+        prior columns and the clip on the residuals, a library call), then the host stage."""
         redone, flags = False, raw.flags
         if flags:
             raw = pend.redo(i) if isinstance(pend, PendingBatch) else pend.redo()
             frame = self._frame(pair, raw)
             redone = True
             self.units_redone += 1
+        if frame is not None and steps is not None:
+            frame = steps.apply(frame, pair.ctx)
         if frame is not None and self.host_stage is not None:
             frame = self.host_stage(frame, pair)
         return StreamResult(frame, raw, tag, redone, spans, flags)
 
     def _collect(self, item) -> list[StreamResult]:
-        pairs, pend, tags, fut = item
+        pairs, pend, tags, fut, steps = item
         # the NEWEST submission of a pipelined context still lacks its tail: enqueue it before blocking on its frame
         if self._piped and isinstance(pend, PendingBatch):
             pend.ctx.flush(pend.ticket)
         done, spans = fut.result()
         # a batch's stage spans are attached to its FIRST unit (they cover all units: one set of launches)
-        return [self._finish(pair, pend, i, raw, frame, tag, spans if i == 0 else {})
+        return [self._finish(pair, pend, i, raw, frame, tag, spans if i == 0 else {}, None if steps is None else steps[i])
                 for i, (pair, (raw, frame), tag) in enumerate(zip(pairs, done, tags))]
 
     # ------------------------------------------------------------------ API
-    def submit(self, pair: ResidentPair, conf, box=None, origin=None, tag=None, on_submitted=None) -> list[StreamResult]:
+    def submit(self, pair: ResidentPair, conf, box=None, origin=None, tag=None, on_submitted=None, prior=None) -> list[StreamResult]:
         """Queue one unit on `pair`'s context; returns the units collected to keep at most `depth` pending (oldest first -
         possibly none).  `on_submitted(pending_frame)` runs on the calling thread right behind the submission (e.g. the hand-over
-        of the unit's block to a collective: `karios_amd.parallel.RankBlockExchange.issue`)."""
+        of the unit's block to a collective: `karios_amd.parallel.RankBlockExchange.issue`).  `prior` (`karios_amd.matcher.prior`): the
+        unit is tracked under it, as `ResidentPair.match_tile(prior=)` does - a blocking call, like the maxCorners 0 branch."""
         if self._pool is None:
             raise RuntimeError("FrameStream is closed")
+        steps = None
+        if prior is not None:
+            from .matcher.prior import as_prior
+            from .resident.tiles import _origin
+            pend = pair.match_tile_prior_raw(conf, box, self.threshold, origin, mutual_info=self.mutual_info, prior=prior)   # (repeats a flagged tile itself)
+            steps = [PriorSteps(as_prior(prior), *_origin(origin, box), clips(conf))]
         # maxCorners == 0 (unbounded) sizes the frame block for a quarter of the tile's pixels: no pinned 3-slot ring for that
-        if conf.maxCorners > 0:
+        elif conf.maxCorners > 0:
             pend = pair.submit_tile(conf, box, self.threshold, origin, mutual_info=self.mutual_info)
         else:
             pend = pair.match_tile_raw(conf, box, self.threshold, origin, mutual_info=self.mutual_info)    # (blocking; repeats a flagged tile itself)
         if on_submitted is not None:
             on_submitted(pend)
-        self._pending.append(([pair], pend, [tag], self._pool.submit(self._host_half, [pair], pend)))
+        self._pending.append(([pair], pend, [tag], self._pool.submit(self._host_half, [pair], pend), steps))
         out = []
         while len(self._pending) > self.depth:
             out += self._collect(self._pending.popleft())
         return out
 
-    def submit_many(self, units, conf, tags=None, on_submitted=None) -> list[StreamResult]:
+    def submit_many(self, units, conf, tags=None, on_submitted=None, priors=None) -> list[StreamResult]:
         """Queue several independent units - `units` = [(pair, box | None, origin | None), ...], e.g. the tiles of one `KLT.match`
         (klt.py:220-253) or a rank's share of a multi-band job - as BATCHED submissions (`karios_amd.resident.submit_units`: one set
         of device launches per <= 16 units; a batch counts as one pending submission for `depth`).  Units the batch form does not
         cover (another context, a user mask, maxCorners 0 ...) go one by one through `submit`, in order.  Returns the collected
-        results like `submit`; `on_submitted(pending_batch_or_frame, first_unit_index)` runs behind every submission."""
+        results like `submit`; `on_submitted(pending_batch_or_frame, first_unit_index)` runs behind every submission.
+        `priors` (None, one prior for all units, or one per unit): the batches go through km_klt_units_frame_prior_submit, a unit the batch
+        form does not cover through a blocking call under its prior; the frames carry `dx_prior, dy_prior` and, with
+        `conf.outliers_filtering`, are clipped on the residuals - what `ResidentPair.match_tile(prior=)` yields unit by unit."""
         from ._lib import UNITS_PER_SUBMISSION
+        from .resident.tiles import _unit_priors
+        priors = _unit_priors(priors, len(units))
         if self._pool is None:
             raise RuntimeError("FrameStream is closed")
         tags = list(tags) if tags is not None else [None] * len(units)
@@ -216,16 +233,18 @@ class FrameStream:
                 if id(ctx) not in self._piped:
                     self._piped[id(ctx)] = (ctx, ctx.get_option("units_pipeline", 0))
                     ctx.set_option("units_pipeline", 1)
-            pend = submit_units(chunk, conf, self.threshold, self.mutual_info) if len(chunk) > 1 else None
+            chunk_priors = None if priors is None else priors[i:i + UNITS_PER_SUBMISSION]
+            pend = submit_units(chunk, conf, self.threshold, self.mutual_info, priors=chunk_priors) if len(chunk) > 1 else None
             if pend is None:               # not batchable: unit by unit
-                for (pair, box, origin), tag in zip(chunk, chunk_tags):
-                    out += self.submit(pair, conf, box, origin, tag, None if on_submitted is None else (lambda p, k=i: on_submitted(p, k)))
+                for k, ((pair, box, origin), tag) in enumerate(zip(chunk, chunk_tags)):
+                    out += self.submit(pair, conf, box, origin, tag, None if on_submitted is None else (lambda p, k=i: on_submitted(p, k)),
+                                       prior=None if chunk_priors is None else chunk_priors[k])
                     i += 1
                 continue
             if on_submitted is not None:
                 on_submitted(pend, i)
             pairs = [u[0] for u in chunk]
-            self._pending.append((pairs, pend, chunk_tags, self._pool.submit(self._host_half, pairs, pend)))
+            self._pending.append((pairs, pend, chunk_tags, self._pool.submit(self._host_half, pairs, pend), pend.prior_steps))
             while len(self._pending) > self.depth:
                 out += self._collect(self._pending.popleft())
             i += len(chunk)
