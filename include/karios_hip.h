@@ -407,6 +407,36 @@ int km_mi_batch(km_ctx *ctx, const void *ref, const void *mon, int dtype, int Hr
                 int Hmon, int Wmon, ptrdiff_t stride_ref, ptrdiff_t stride_mon, const float *x0,
                 const float *y0, const float *dx, const float *dy, int n, double *out_studholme,
                 double *out_nmi);
+/* ---- the mutual-information search around each key point (no counterpart in the reference's call graph; tests/mi_search_restatement.py
+ * is the definition): km_zncc_search's counterpart for pairs whose contrast is non-linear or inverted.  Centres and skip rule are
+ * km_mi_batch's (and km_zncc_search's): X0 = int(x0), X1 = round(x0 + dx) on the float32 sum, the 57 x 57 bounds rule with margin 28 on
+ * both rasters.  For oy, ox in -radius .. radius (S = 2 radius + 1, 1 <= radius <= 8), surface[oy][ox] = MutualInfoService._mutual_info of
+ * the chip of `ref` at (X0, Y0) and the chip of `mon` at (X1 + ox, Y1 + oy): NaN where that centre fails the bounds rule on `mon`
+ * (X - 28 < 0 or X >= Wmon - 28, likewise in y), where one cell of the histogram is occupied, and, for float32, where the monitored chip
+ * holds a non-finite sample (a non-finite sample in the reference chip: the whole row).  The 32 x 32 table of counts is that of
+ * np.histogram2d(chip_ref, chip_mon, bins=32): the reference chip's bins are fixed per row, the monitored chip's range and bins are taken
+ * anew at every offset (integer types: bin = min(floor(32 (v - lo) / (hi - lo)), 31), a constant chip in bin 16; float32: numpy's edges
+ * i * step + lo on the float64 casts, the maximum folded into bin 31).
+ * From counts to value, exactly: T[c] = round_half_even(c ln c 2^36) for c = 0 .. 3249 as 64-bit integers (T[0] = T[1] = 0,
+ * csrc/mi_clogc_q36.inc), L = T[3249]; Sx, Sy, Sxy = the sums of T over the row marginals, the column marginals and the cells;
+ * num = 2 L - Sx - Sy, den = L - Sxy (all below 2^53).  surface = (double)num / (double)den, NaN iff den == 0; the mi_score formula
+ * (ZNCCService._mutual_information) is (double)(2 (num - den)) / (double)num, NaN iff num == 0.  A value is a function of the pixels
+ * alone: the same bits on the host and the device, for all four pixel types; within 1e-9 of km_mi_batch at offset (0, 0).
+ * The peak is the largest value of the surface, the first in raster order among equals; the sub-pixel step and the status bits are
+ * km_zncc_search's (bits 1, 2, 4, 8).
+ *   out_offset[k] = (bx, by); out_peak[k] = the surface at the peak; out_peak_mi[k] = the mi_score formula at the same offset;
+ *   out_shift[k] = (X1 + bx - X0 + sx, Y1 + by - Y0 + sy); out_status[k]; out_surface: NULL, or n x S x S
+ * Strides in pixels; 0 <= n <= 2^20 (n == 0: KM_OK, nothing launched).  KM_E_ARG: a bad dtype (the 32-bit integer and float64 types
+ * included), radius, n, or a null array with n > 0.  With an image window set (km_set_image_window) both forms return
+ * KM_E_UNSUPPORTED and queue nothing.  The device form leaves its work queued on the context stream. */
+int km_mi_search(km_ctx *ctx, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon,
+                 ptrdiff_t stride_ref, ptrdiff_t stride_mon, const float *x0, const float *y0, const float *dx, const float *dy,
+                 int n, int radius, int32_t *out_offset, double *out_peak, double *out_peak_mi, double *out_shift, uint8_t *out_status,
+                 double *out_surface);
+int km_mi_search_dev(km_ctx *ctx, const void *d_ref, const void *d_mon, int dtype, int Href, int Wref, int Hmon, int Wmon,
+                     ptrdiff_t stride_ref, ptrdiff_t stride_mon, const float *d_x0, const float *d_y0, const float *d_dx,
+                     const float *d_dy, int n, int radius, int32_t *d_offset, double *d_peak, double *d_peak_mi, double *d_shift,
+                     uint8_t *d_status, double *d_surface);
 /* skimage.registration.phase_cross_correlation(reference_image, moving_image)[0]
  * (matcher/large_offset.py:39): out_rc = [row, col] */
 int km_phase_shift(km_ctx *ctx, const void *reference_image, const void *moving_image,

@@ -1,24 +1,25 @@
 // Scoring entry points: ZNCCService.compute_zncc / _zncc2 (zncc_service.py:45-238), the ZNCC search around each key point
 // (k_zncc_search.hip; no counterpart in the reference's call graph), the mutual-information scores
-// (mutual_info_service.py:73-130, zncc_service.py:240-287), the DN-value filter of the key points (core.py:650-737).
+// (mutual_info_service.py:73-130, zncc_service.py:240-287) and their search (k_mi_search.hip), the DN-value filter of the key points (core.py:650-737).
 #include "api_internal.hpp"
+#include "k_mi_search.hpp"
 #include "k_zncc_search.hpp"
 
 namespace {
 
-// what km_zncc_search and km_zncc_search_dev refuse alike; n == 0 passes (nothing is launched then)
-int search_args(km_ctx *c, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref, ptrdiff_t smon,
+// what km_zncc_search, km_mi_search and their device forms refuse alike; n == 0 passes (nothing is launched then)
+int search_args(km_ctx *c, const char *what, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref, ptrdiff_t smon,
                 const float *x0, const float *y0, const float *dx, const float *dy, int n, int radius, const int32_t *offset, const double *peak,
                 const double *shift, const uint8_t *status)
 {
     int rc;
-    if ((rc = begin_call(c)) || (rc = check_image(c, ref, Href, Wref, sref, "zncc_search")) || (rc = check_image(c, mon, Hmon, Wmon, smon, "zncc_search")))
+    if ((rc = begin_call(c)) || (rc = check_image(c, ref, Href, Wref, sref, what)) || (rc = check_image(c, mon, Hmon, Wmon, smon, what)))
         return rc;
-    if (!km_dtype_size(dtype)) return km_fail(c, KM_E_ARG, "zncc_search: bad dtype %d", dtype);
-    if (radius < 1 || radius > zs::MAX_RADIUS) return km_fail(c, KM_E_ARG, "zncc_search: radius %d (1 .. %d)", radius, zs::MAX_RADIUS);
-    if (n < 0 || n > zs::MAX_ROWS) return km_fail(c, KM_E_ARG, "zncc_search: %d rows (0 .. 2^20)", n);
-    if (n > 0 && (!x0 || !y0 || !dx || !dy || !offset || !peak || !shift || !status)) return km_fail(c, KM_E_ARG, "zncc_search: null keypoint or output array");
-    if (c->window.H) return km_fail(c, KM_E_UNSUPPORTED, "zncc_search: an image window is set (km_set_image_window); the search reads whole rasters");
+    if (!km_dtype_size(dtype)) return km_fail(c, KM_E_ARG, "%s: bad dtype %d", what, dtype);
+    if (radius < 1 || radius > zs::MAX_RADIUS) return km_fail(c, KM_E_ARG, "%s: radius %d (1 .. %d)", what, radius, zs::MAX_RADIUS);
+    if (n < 0 || n > zs::MAX_ROWS) return km_fail(c, KM_E_ARG, "%s: %d rows (0 .. 2^20)", what, n);
+    if (n > 0 && (!x0 || !y0 || !dx || !dy || !offset || !peak || !shift || !status)) return km_fail(c, KM_E_ARG, "%s: null keypoint or output array", what);
+    if (c->window.H) return km_fail(c, KM_E_UNSUPPORTED, "%s: an image window is set (km_set_image_window); the search reads whole rasters", what);
     return KM_OK;
 }
 
@@ -31,7 +32,7 @@ int km_zncc_search_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtyp
                        int32_t *d_offset, double *d_peak, double *d_shift, uint8_t *d_status, double *d_surface)
 {
     int rc;
-    if ((rc = search_args(c, d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_shift, d_status)))
+    if ((rc = search_args(c, "zncc_search", d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_shift, d_status)))
         return rc;
     if (n == 0) return KM_OK;
     const kzs_args a = {d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_shift, d_status, d_surface};
@@ -45,7 +46,7 @@ int km_zncc_search(km_ctx *c, const void *ref, const void *mon, int dtype, int H
                    double *out_peak, double *out_shift, uint8_t *out_status, double *out_surface)
 {
     int rc;
-    if ((rc = search_args(c, ref, mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, x0, y0, dx, dy, n, radius, out_offset, out_peak, out_shift, out_status)))
+    if ((rc = search_args(c, "zncc_search", ref, mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, x0, y0, dx, dy, n, radius, out_offset, out_peak, out_shift, out_status)))
         return rc;
     if (n == 0) return KM_OK;
     const size_t es = km_dtype_size(dtype), N = (size_t)n, SS = (size_t)(2 * radius + 1) * (2 * radius + 1);
@@ -180,6 +181,60 @@ int km_mi_batch(km_ctx *c, const void *ref, const void *mon, int dtype, int Href
         return rc;
     if (out_st) KM_D2H(c, out_st, d_out, (size_t)n * sizeof(double));
     if (out_nmi) KM_D2H(c, out_nmi, d_out + n, (size_t)n * sizeof(double));
+    KM_FLUSH(c);
+    return KM_OK;
+}
+
+int km_mi_search_dev(km_ctx *c, const void *d_ref, const void *d_mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref,
+                     ptrdiff_t smon, const float *d_x0, const float *d_y0, const float *d_dx, const float *d_dy, int n, int radius,
+                     int32_t *d_offset, double *d_peak, double *d_peak_mi, double *d_shift, uint8_t *d_status, double *d_surface)
+{
+    int rc;
+    if ((rc = search_args(c, "mi_search", d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_shift, d_status)))
+        return rc;
+    if (n > 0 && !d_peak_mi) return km_fail(c, KM_E_ARG, "mi_search: null keypoint or output array");
+    if (n == 0) return KM_OK;
+    const kms_args a = {d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, d_x0, d_y0, d_dx, d_dy, n, radius, d_offset, d_peak, d_peak_mi, d_shift, d_status, d_surface};
+    c->evs_used[c->ev_cur][ST_MI] = false;
+    km_stage_timer t(c, ST_MI);
+    return kms_search(c, a);
+}
+
+int km_mi_search(km_ctx *c, const void *ref, const void *mon, int dtype, int Href, int Wref, int Hmon, int Wmon, ptrdiff_t sref,
+                 ptrdiff_t smon, const float *x0, const float *y0, const float *dx, const float *dy, int n, int radius, int32_t *out_offset,
+                 double *out_peak, double *out_peak_mi, double *out_shift, uint8_t *out_status, double *out_surface)
+{
+    int rc;
+    if ((rc = search_args(c, "mi_search", ref, mon, dtype, Href, Wref, Hmon, Wmon, sref, smon, x0, y0, dx, dy, n, radius, out_offset, out_peak, out_shift, out_status)))
+        return rc;
+    if (n > 0 && !out_peak_mi) return km_fail(c, KM_E_ARG, "mi_search: null keypoint or output array");
+    if (n == 0) return KM_OK;
+    const size_t es = km_dtype_size(dtype), N = (size_t)n, SS = (size_t)(2 * radius + 1) * (2 * radius + 1);
+    void *d_ref, *d_mon;
+    if ((rc = upload_image(c, WS_RAW_A, ref, es, Href, Wref, sref, &d_ref)) || (rc = upload_image(c, WS_RAW_B, mon, es, Hmon, Wmon, smon, &d_mon)))
+        return rc;
+    // peak | peak_mi | shift | offset | status in one slot (each part a multiple of 256 bytes apart); the surface in one of its own
+    const size_t o_mi = up256(N * sizeof(double)), o_shift = o_mi + up256(N * sizeof(double)), o_offset = o_shift + up256(2 * N * sizeof(double)),
+                 o_status = o_offset + up256(2 * N * sizeof(int32_t));
+    char *d_out = (char *)km_ws(c, WS_MISC1, o_status + up256(N));
+    double *d_surface = out_surface ? (double *)km_ws(c, WS_MISC2, N * SS * sizeof(double)) : nullptr;
+    if (!d_out || (out_surface && !d_surface)) return KM_E_NOMEM;
+    const float *src[4] = {x0, y0, dx, dy};
+    float *kp;
+    if ((rc = upload_columns(c, WS_MISC0, src, 4, n, &kp))) return rc;
+    const kms_args a = {d_ref, d_mon, dtype, Href, Wref, Hmon, Wmon, Wref, Wmon, kp, kp + N, kp + 2 * N, kp + 3 * N, n, radius,
+                        (int32_t *)(d_out + o_offset), (double *)d_out, (double *)(d_out + o_mi), (double *)(d_out + o_shift), (uint8_t *)(d_out + o_status), d_surface};
+    {
+        c->evs_used[c->ev_cur][ST_MI] = false;
+        km_stage_timer t(c, ST_MI);
+        if ((rc = kms_search(c, a))) return rc;
+    }
+    KM_D2H(c, out_peak, a.peak, N * sizeof(double));
+    KM_D2H(c, out_peak_mi, a.peak_mi, N * sizeof(double));
+    KM_D2H(c, out_shift, a.shift, 2 * N * sizeof(double));
+    KM_D2H(c, out_offset, a.offset, 2 * N * sizeof(int32_t));
+    KM_D2H(c, out_status, a.status, N);
+    if (out_surface) KM_D2H(c, out_surface, d_surface, N * SS * sizeof(double));
     KM_FLUSH(c);
     return KM_OK;
 }

@@ -103,6 +103,37 @@ def mi_batch(ref, mon, x0, y0, dx, dy, ctx: Context | None = None):
     return a, b
 
 
+MiSearch = namedtuple("MiSearch", "offset peak peak_mi shift status surface")      # status: the ZNCC_* bits
+
+
+def mi_search(ref, mon, x0, y0, dx, dy, radius: int = 4, surface: bool = False, ctx: Context | None = None):
+    """The mutual-information search around each key point, `zncc_search`'s counterpart for pairs whose contrast is non-linear or
+    inverted: for oy, ox in -radius .. radius Studholme's NMI (`MutualInfoService._mutual_info`, mutual_info_service.py:32-63) of the
+    57 x 57 chips at (X0, Y0) in `ref` and (X1 + ox, Y1 + oy) in `mon`, around the centres `compute_mutual_info` scores, its peak and
+    the peak's sub-pixel position (include/karios_hip.h: km_mi_search; exact from the counts, the same bits on every device).
+    The rasters (one pixel type of uint8 / uint16 / int16 / float32) and the float32 columns are all numpy arrays or all device tensors.
+    -> MiSearch(offset int32[n, 2] = (bx, by), peak float64[n], peak_mi float64[n] (the `mi_score` formula at the peak's offset),
+    shift float64[n, 2] = (x, y), status uint8[n] (ZNCC_* bits), surface float64[n, S, S] or None), living where the inputs live."""
+    what = "mi_search"
+    place = Place([ref, mon], what, "ref and mon")
+    place.require([x0, y0, dx, dy], what, "the rasters and x0, y0, dx, dy")
+    _, cols, n = _f32_columns((x0, y0, dx, dy), what, "x0, y0, dx, dy")
+    _check_search(what, n, radius)
+    radius, S = int(radius), 2 * int(radius) + 1
+    pr, dr, Hr, Wr, sr = _raster_arg(place, ref, what)
+    pm, dm, Hm, Wm, sm = _raster_arg(place, mon, what)
+    if dr != dm or dr not in _lib._DTYPES:
+        raise ValueError(f"{what}: rasters of {dr} / {dm} (one pixel type of uint8, uint16, int16, float32)")
+    out = MiSearch(place.empty((n, 2), np.int32), place.empty((n,), np.float64), place.empty((n,), np.float64), place.empty((n, 2), np.float64),
+                   place.empty((n,), np.uint8), place.empty((n, S, S), np.float64) if surface else None)
+    if n:
+        place.call(_ctx(ctx), "km_mi_search", pr, pm, _lib._DTYPES[dr], Hr, Wr, Hm, Wm, sr, sm, *_col_args(place, cols, n), n, radius,
+                   *(place.pointer(a) for a in out))
+        if place.dev:
+            _ctx(ctx).sync()
+    return out
+
+
 def phase_cross_correlation(reference_image, moving_image, ctx: Context | None = None):
     """skimage.registration.phase_cross_correlation(reference_image, moving_image)[0] with the 0.24
     defaults (large_offset.py:39) -> array([row, col]) float64 holding integers."""

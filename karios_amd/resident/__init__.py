@@ -16,7 +16,7 @@ from . import shared
 from .buffers import DeviceBuffer
 from .pair import ResidentPair
 from .pending import PendingBatch, PendingFrame, RawFrame
-from .scores import ZNCC_SEARCH_COLUMNS, search_columns
+from .scores import MI_SEARCH_COLUMNS, ZNCC_SEARCH_COLUMNS, mi_search_columns, search_columns
 from .shared import forget_shared_pairs, invalidate_raster, keep_shared_across, shared_pair
 from .tiles import submit_units
 

@@ -1,4 +1,4 @@
-"""The score entry points on a resident pair: `ScoreCalls` (ZNCC, its search, mutual information, `score_frame`)."""
+"""The score entry points on a resident pair: `ScoreCalls` (ZNCC, its search, mutual information, its search, `score_frame`)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -8,15 +8,21 @@ from pandas import DataFrame
 
 from .. import frames
 from .._lib import KariosHipError, pinned_empty
-from ..ops.score import ZnccSearch, _check_search
+from ..ops.score import MiSearch, ZnccSearch, _check_search
 from .calls import Scope
 
 ZNCC_SEARCH_COLUMNS = ["zncc_dx", "zncc_dy", "zncc_peak", "zncc_off_x", "zncc_off_y", "zncc_status"]
+MI_SEARCH_COLUMNS = ["mi_dx", "mi_dy", "mi_peak", "mi_peak_mi", "mi_off_x", "mi_off_y", "mi_status"]
 
 
 def search_columns(found: ZnccSearch):
     """The six frame columns of a search result (ZNCC_SEARCH_COLUMNS), as arrays."""
     return found.shift[:, 0], found.shift[:, 1], found.peak, found.offset[:, 0], found.offset[:, 1], found.status
+
+
+def mi_search_columns(found: MiSearch):
+    """The seven frame columns of a mutual-information search result (MI_SEARCH_COLUMNS), as arrays."""
+    return found.shift[:, 0], found.shift[:, 1], found.peak, found.peak_mi, found.offset[:, 0], found.offset[:, 1], found.status
 
 
 def _columns(x0, y0, dx, dy):
@@ -106,12 +112,37 @@ class ScoreCalls:
         self._mi_memo = (digest, st, nmi)
         return st.copy(), nmi.copy()
 
+    def mi_search(self, x0, y0, dx, dy, radius: int = 4, surface: bool = False) -> MiSearch:
+        """`ops.mi_search` on the resident rasters: the surface of Studholme's NMI over the offsets -radius .. radius around the centre
+        `mutual_info` scores, its peak, the `mi_score` formula there and the peak's sub-pixel position, for key points given in image
+        coordinates -> MiSearch of numpy arrays.  A windowed pair (row-band mode) raises KariosHipError: the search reads whole rasters."""
+        if self.window is not None:
+            raise KariosHipError("mi_search: the pair holds a window of its rasters (row-band mode); a windowed search is not supported")
+        cols = _columns(x0, y0, dx, dy)
+        n = len(cols[0])
+        _check_search("mi_search", n, radius)
+        radius = int(radius)
+        S = 2 * radius + 1
+        if n == 0:
+            return MiSearch(np.empty((0, 2), np.int32), np.empty(0, np.float64), np.empty(0, np.float64), np.empty((0, 2), np.float64),
+                            np.empty(0, np.uint8), np.empty((0, S, S), np.float64) if surface else None)
+        self._ready()
+        c = self.ctx
+        # one float64 slot per row for each of: peak | peak_mi | shift x, y | offset (2 x int32) | status (bytes, in the sixth) | the surface
+        args, out, o = self._stage(cols, 6 + (S * S if surface else 0))
+        c.check(c.lib.km_mi_search_dev(*args, radius, C.c_void_p(o + 32 * n), C.c_void_p(o), C.c_void_p(o + 8 * n), C.c_void_p(o + 16 * n),
+                                       C.c_void_p(o + 40 * n), C.c_void_p(o + 48 * n) if surface else None), "km_mi_search_dev")
+        c.sync()
+        return MiSearch(out[4 * n:5 * n].view(np.int32).reshape(n, 2).copy(), out[:n].copy(), out[n:2 * n].copy(), out[2 * n:4 * n].reshape(n, 2).copy(),
+                        out[5 * n:6 * n].view(np.uint8)[:n].copy(), out[6 * n:].reshape(n, S, S).copy() if surface else None)
+
     def score_frame(self, frame: DataFrame, confidence_threshold: float = 0.4, mutual_info: bool = False,
-                    zncc_search_radius: int | None = None) -> DataFrame:
+                    zncc_search_radius: int | None = None, mi_search_radius: int | None = None) -> DataFrame:
         """`_handle_klt_results` numeric columns (core.py:872-907): radial error, angle, the ZNCC of the rows with
         score >= confidence_threshold (NaN elsewhere) and, with `mutual_info`, the `mutual_info_score` / `mi_score`
         columns of the same rows.  With `zncc_search_radius` the same rows also get the columns of `zncc_search`
-        (ZNCC_SEARCH_COLUMNS; NaN elsewhere); None, the default, adds nothing."""
+        (ZNCC_SEARCH_COLUMNS; NaN elsewhere) and with `mi_search_radius` those of `mi_search` (MI_SEARCH_COLUMNS, behind them); None,
+        the default of both, adds nothing."""
         frame = frames.radial_angle_columns(frame)
         dx, dy, score = frame["dx"].to_numpy(), frame["dy"].to_numpy(), frame["score"].to_numpy()
         keep = score >= confidence_threshold
@@ -130,6 +161,12 @@ class ScoreCalls:
         if zncc_search_radius is not None:
             found = self.zncc_search(frame["x0"].to_numpy()[keep], frame["y0"].to_numpy()[keep], dx[keep], dy[keep], zncc_search_radius)
             for name, values in zip(ZNCC_SEARCH_COLUMNS, search_columns(found)):
+                column = np.full(len(frame), np.nan, np.float64)
+                column[keep] = values
+                frame[name] = column
+        if mi_search_radius is not None:
+            found = self.mi_search(frame["x0"].to_numpy()[keep], frame["y0"].to_numpy()[keep], dx[keep], dy[keep], mi_search_radius)
+            for name, values in zip(MI_SEARCH_COLUMNS, mi_search_columns(found)):
                 column = np.full(len(frame), np.nan, np.float64)
                 column[keep] = values
                 frame[name] = column

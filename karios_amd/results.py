@@ -32,7 +32,7 @@ from ._lib import KariosHipError
 from .accuracy_analysis import GeometricStat
 from .core.configuration import AccuracyAnalysisConfiguration
 from .frames import radial_angle_columns
-from .resident import ZNCC_SEARCH_COLUMNS, ResidentPair
+from .resident import MI_SEARCH_COLUMNS, ZNCC_SEARCH_COLUMNS, ResidentPair
 
 logger = logging.getLogger(__name__)
 
@@ -41,17 +41,20 @@ CSV_COLUMNS = ["x0", "y0", "dx", "dy", "score", "radial error", "angle", "zncc_s
 
 def handle_klt_results(results: Iterable[pd.DataFrame], csv_file, pair: ResidentPair, confidence_threshold: float = 0.4,
                        large_shift_applied: bool = False, zncc_search_radius: int | None = None, prior=None,
-                       outliers_filtering: bool = False) -> pd.DataFrame:
+                       outliers_filtering: bool = False, mi_search_radius: int | None = None) -> pd.DataFrame:
     """`KariosAPI._handle_klt_results` (core.py:848-921) for the frames of `KLT.match` / `ResidentPair.match*`.
     With `large_shift_applied` the scores are skipped like in the reference (core.py:909-910) and the CSV has 7 columns.
     With `zncc_search_radius` the scored rows also carry the columns of the ZNCC search (`ResidentPair.zncc_search`,
-    ZNCC_SEARCH_COLUMNS) behind the reference's; None, the default, leaves the frame and the CSV as the reference writes them.
+    ZNCC_SEARCH_COLUMNS) behind the reference's, and with `mi_search_radius` those of the mutual-information search
+    (`ResidentPair.mi_search`, MI_SEARCH_COLUMNS) behind both; None, the default, leaves the frame and the CSV as the reference writes them.
     With `prior` (the frames of `KLT.match(..., prior=)`, `karios_amd.matcher.prior`) the rasters were never shifted or resampled: the
     scores are computed although a large shift is in play (`large_shift_applied` is ignored), and `dx_prior, dy_prior` - the float32
     displacement the prior alone predicts - follow the reference's columns; `outliers_filtering` then clips the rows on the residuals
     dx - dx_prior, dy - dy_prior (`ops.sigma_clip`; frames that `KLT.match` already clipped lose nothing)."""
     from .matcher import prior as _prior
     csv_file = Path(csv_file)
+    searched = (ZNCC_SEARCH_COLUMNS if zncc_search_radius is not None else []) + (MI_SEARCH_COLUMNS if mi_search_radius is not None else [])
+    more = {} if mi_search_radius is None else {"mi_search_radius": mi_search_radius}      # (the default call is the one made before the argument existed)
     all_frame = pd.DataFrame()
     for frame in results:
         if prior is not None:
@@ -60,15 +63,15 @@ def handle_klt_results(results: Iterable[pd.DataFrame], csv_file, pair: Resident
                 frame["dx_prior"], frame["dy_prior"] = _prior.prior_columns(frame, prior)
             if outliers_filtering:
                 frame = _prior.clip_residuals(frame, ctx=pair.ctx)
-            frame = pair.score_frame(frame, confidence_threshold, mutual_info=True, zncc_search_radius=zncc_search_radius)
-            frame = frame[CSV_COLUMNS + _prior.PRIOR_COLUMNS + (ZNCC_SEARCH_COLUMNS if zncc_search_radius is not None else [])]
+            frame = pair.score_frame(frame, confidence_threshold, mutual_info=True, zncc_search_radius=zncc_search_radius, **more)
+            frame = frame[CSV_COLUMNS + _prior.PRIOR_COLUMNS + searched]
         elif large_shift_applied:
             frame = radial_angle_columns(frame)
             if "zncc_score" in frame.columns:
                 frame = frame.drop(columns=["zncc_score"])
         else:
-            frame = pair.score_frame(frame, confidence_threshold, mutual_info=True, zncc_search_radius=zncc_search_radius)
-            frame = frame[CSV_COLUMNS + (ZNCC_SEARCH_COLUMNS if zncc_search_radius is not None else [])]      # the reference's column order, whatever produced zncc_score first
+            frame = pair.score_frame(frame, confidence_threshold, mutual_info=True, zncc_search_radius=zncc_search_radius, **more)
+            frame = frame[CSV_COLUMNS + searched]      # the reference's column order, whatever produced zncc_score first
         if not csv_file.exists():
             frame.to_csv(csv_file, sep=";", index=False)
         else:
